@@ -12,6 +12,12 @@ energy.  For N > 1 the SAME 262 144-particle system is sharded by particle rows 
 scaling) with one all-gather of positions and one reduce-scatter of partial accelerations per step.
 Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the roofline of
+the timed steps' own HIP events, the energy check).  --full adds the secondary figures, each taking steps or runs of
+its own: the liquid and sampled-segment legs, the mixed-precision leg beside fp64 (BASELINE config 5), the CPU
+baselines, and the committed rocprofv3 / parity summaries.  --dump-outputs DIR writes what the timed steps returned
+(float64 .npy files) before the line is printed; the synthetic input is seeded, so two builds compare file for file.
+
 Multi-GPU launch ladder (N > 1).  The process the driver (or a user) starts never touches torch or the GPU: it is a
 WATCHDOG that runs each attempt as a fresh child process with a deadline, kills the child's whole process tree when
 the deadline passes or the child fails, and moves to the next rung:
@@ -510,6 +516,20 @@ def measure(args) -> None:
         eng.profile_enable(False)
         return el, profs, sim.collect(nsteps)
 
+    def final_state():
+        """-> {'r', 'ru', 'v', 'a': (3, n) float64} in the order of the arrays given to start(); in a
+        one-process-per-GPU run every rank calls it and contributes its shard"""
+        st = eng.get_state()
+        if role == "multi" or world == 1:
+            return {key: np.stack(val) for key, val in st.items()}
+        box = [None] * world
+        dist.all_gather_object(box, (sim.particle_ids(), {key: np.stack(val) for key, val in st.items()}))
+        out = {key: np.empty((3, n), dtype=np.float64) for key in st}
+        for ids, part in box:
+            for key in out:
+                out[key][:, ids] = part[key]
+        return out
+
     sim.start(r, v)
     if args.warmup > 0:
         sim.run(args.warmup)
@@ -518,12 +538,17 @@ def measure(args) -> None:
     slow = max(range(len(profs)), key=lambda g: profs[g]["pair_ms"])     # the slowest rank bounds the step
     prof = profs[slow]
     force_ms, launches = prof["pair_ms"], prof["launches"]
+    # what the timed steps hand a caller: the per-step series and the state after the last step (before any leg of
+    # --full moves it on)
+    outputs = None
+    if args.dump_outputs:
+        outputs = dict(final_state(), epot=epot, ekin=ekin, d_epot=d_epot, dd_epot=dd_epot)
 
     # production rate: the same K steps timed again after the lattice has melted (>= 300 steps from the start).
     # The tiles of a liquid are looser than those of the jittered lattice, so the tile mask keeps more pairs;
     # reported beside the headline, never as `value`.
     liquid = None
-    if not args.no_liquid and n >= 4096:
+    if args.full and not args.no_liquid and n >= 4096:
         done = args.warmup + args.steps
         while done < 300:
             k = min(100, 300 - done)
@@ -538,7 +563,7 @@ def measure(args) -> None:
     # forces-only pair kernel (ljmd_enqueue_steps_sampled).  The same K steps again as ONE sampled segment, in the
     # state the previous leg left; the trajectory is bit-identical.  Reported beside the headline, never as `value`.
     sampled = None
-    if not args.no_liquid and n >= 4096:
+    if args.full and not args.no_liquid and n >= 4096:
         el_s, profs_s, sc_s = timed(args.steps, sampled=True)
         sampled = (el_s, max(q["pair_ms"] for q in profs_s), bool(np.isfinite(sc_s[0][-1])),
                    int(np.count_nonzero(np.isnan(sc_s[0]))))
@@ -627,7 +652,7 @@ def measure(args) -> None:
             # two pair kernels (fp64 near, fp32 far) share the timed interval: no single-peak roofline applies
             line["roofline"].update({"bound": "fp64-valu (near pairs) + fp32-valu (far pairs)", "frac": None,
                                      "note": "achieved = reference-algorithm fp64 flop / time of both pair kernels"})
-            parity = committed_parity_summary()
+            parity = committed_parity_summary() if args.full else None
             if parity:
                 # config 5's accuracy beside its rate: measured deviations of ONE force call of this workload from
                 # the CPU oracle over all ordered pairs (tests/test_gpu_parity.py writes the summary)
@@ -644,9 +669,11 @@ def measure(args) -> None:
         # Counter evidence from the committed rocprofv3 PMC passes of this same command (FETCH_SIZE and WRITE_SIZE need
         # separate passes and cannot be read from inside the run).  A summary is quoted as evidence for THIS run only
         # when it was collected with the kernel sources this run was built from (kernel_source_sha16); otherwise its raw
-        # numbers appear under `stale_committed_profile` and nothing is derived from them.
+        # numbers appear under `stale_committed_profile` and nothing is derived from them.  Quoted with --full only.
         def committed(stem):
             """newest committed profile of that name (profiles/rNN_<stem>)"""
+            if not args.full:
+                return None
             hits = sorted((ROOT / "profiles").glob(f"r[0-9][0-9]_{stem}"))
             return hits[-1] if hits else None
 
@@ -727,12 +754,12 @@ def measure(args) -> None:
         # BASELINE config 5 beside the fp64 headline, in the same run: the same workload with the fp32 far-pair kernel
         # (LJMD_PRECISION_FP32_FORCE), K steps timed the same way from the same start, and what it costs in accuracy --
         # the energy series against this run's fp64 one, and the committed one-force-call parity against the CPU oracle
-        if n_ranks == 1 and args.mode == "fp64" and not args.no_liquid and n >= 16384:
+        if args.full and n_ranks == 1 and args.mode == "fp64" and not args.no_liquid and n >= 16384:
             try:
                 line["config5_mixed_precision"] = mixed_precision_leg(args, p, r, v, etot, barrier_extra=torch_gpu and torch)
             except Exception as exc:  # noqa: BLE001 - a secondary figure, never a reason to lose the bench line
                 line["config5_mixed_precision"] = {"value": None, "error": str(exc)}
-        if n_ranks == 1 and not args.no_cpu_baseline:
+        if args.full and n_ranks == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline()
             except Exception as exc:  # the baseline is a reported number, never a reason to lose the bench line
@@ -743,6 +770,8 @@ def measure(args) -> None:
             except Exception as exc:
                 line["cpu_baseline_all_cores"] = {"value": None, "unit": "steps/s", "cores": 0, "kind": "port",
                                                   "sample": f"failed: {exc}"}
+        if outputs is not None:
+            dump_outputs(Path(args.dump_outputs), outputs)
         print(json.dumps(line), flush=True)
 
     eng.close()
@@ -750,18 +779,48 @@ def measure(args) -> None:
         dist.destroy_process_group()
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, outputs: dict) -> None:
+    """--dump-outputs: every array as out_dir/<name>.npy, float64.  r, ru, v, a are (3, n) in the order of the
+    synthetic input; when all of them would not fit in DUMP_BUDGET_BYTES, the same seeded sample of particles is kept
+    (column indices in particle_index.npy), so that two builds compare output for output."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    series = {k: np.asarray(outputs[k], dtype=np.float64) for k in ("epot", "ekin", "d_epot", "dd_epot")}
+    state = {k: np.asarray(outputs[k], dtype=np.float64) for k in ("r", "ru", "v", "a")}
+    n = state["r"].shape[1]
+    room = DUMP_BUDGET_BYTES - sum(a.nbytes for a in series.values()) - 8 * n
+    if sum(a.nbytes for a in state.values()) > room:
+        keep = max(1, room // (8 * 3 * len(state) + 8))
+        idx = np.sort(np.random.default_rng(12345).choice(n, size=min(n, keep), replace=False))
+        state = {k: np.ascontiguousarray(a[:, idx]) for k, a in state.items()}
+        series["particle_index"] = idx.astype(np.float64)
+    for name, arr in {**state, **series}.items():
+        np.save(out_dir / f"{name}.npy", arr)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures: the liquid and sampled-segment legs, the mixed-precision leg beside "
+                         "fp64, the CPU baselines and the committed profile / parity summaries (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they returned (per-step epot, ekin, d_epot, dd_epot; "
+                         "r, ru, v, a after the last step) as DIR/<name>.npy")
     ap.add_argument("--particles", dest="n", type=int, default=N_PARTICLES, help="override the particle count (parity/debug only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-liquid", action="store_true",
                     help="skip the second, untimed-for-`value` measurement in the equilibrated liquid (300 extra steps)")
     ap.add_argument("--mode", choices=("fp64", "mixed"), default="fp64",
                     help="mixed = BASELINE config 5 (fp32 far pairs, fp64 near pairs + integrator); the headline metric is fp64")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def main() -> None:

@@ -65,9 +65,11 @@ if [[ -n "${LJMD_SHIM_DIR:-}" && -n "${LJMD_LIB_DIR:-}" ]]; then
   for m in physics/thermodynamic_coefs stats/stats_math stats/md_means stats/md_correlations; do
     o="${G}/obj/$(basename "${m}").o"; "${FC}" "${GF[@]}" -c "${S}/${m}.f90" -o "${o}"; GOBJS+=("${o}")
   done
+  # libljmd.so is found relative to the binary, so that _ref/ keeps working where the tree is checked out elsewhere
+  RPATH='$ORIGIN'/"$(realpath --relative-to="${OUT}" "${LJMD_LIB_DIR}")"
   "${FC}" "${GF[@]}" "${GOBJS[@]}" "${S}/md_simulation_program.f90" \
-      -L"${LJMD_LIB_DIR}" -lljmd -Wl,-rpath,"${LJMD_LIB_DIR}" -o "${OUT}/md_simulation_program_gpu"
+      -L"${LJMD_LIB_DIR}" -lljmd -Wl,-rpath,"${RPATH}" -o "${OUT}/md_simulation_program_gpu"
   "${FC}" "${GF[@]}" "${GOBJS[@]}" "${S}/md_initial_config_program.f90" \
-      -L"${LJMD_LIB_DIR}" -lljmd -Wl,-rpath,"${LJMD_LIB_DIR}" -o "${OUT}/md_initial_config_program_gpu"
+      -L"${LJMD_LIB_DIR}" -lljmd -Wl,-rpath,"${RPATH}" -o "${OUT}/md_initial_config_program_gpu"
 fi
 echo "[build_ref] OK -> ${OUT}"

@@ -130,3 +130,41 @@ def test_real_rungs_without_a_gpu_fail_loudly_and_quickly():
         assert f"rung '{mode}' gave no line" in out.stderr, mode
     assert "torch.distributed.run" in out.stderr and "--nproc-per-node=2" in out.stderr
     assert "no HIP device available" in out.stderr
+
+
+def test_dump_outputs_float64_files_and_a_seeded_sample_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: every array a float64 .npy; above the byte budget the same seeded particle sample every time,
+    its column indices in particle_index.npy, the whole set inside the budget."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(7)
+    n, k = 1000, 5
+    outputs = {key: rng.standard_normal((3, n)) for key in ("r", "ru", "v", "a")}
+    outputs.update({key: rng.standard_normal(k) for key in ("epot", "ekin", "d_epot", "dd_epot")})
+    bench.dump_outputs(tmp_path / "all", outputs)
+    files = sorted(p.name for p in (tmp_path / "all").iterdir())
+    assert files == sorted(f"{key}.npy" for key in outputs)
+    for key, want in outputs.items():
+        got = np.load(tmp_path / "all" / f"{key}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want), key
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 40_000)
+    for tag in ("s1", "s2"):
+        bench.dump_outputs(tmp_path / tag, outputs)
+    assert sum(p.stat().st_size for p in (tmp_path / "s1").iterdir()) <= 40_000 + 128 * 9     # + the .npy headers
+    idx = np.load(tmp_path / "s1" / "particle_index.npy")
+    assert idx.dtype == np.float64 and 0 < idx.size < n and np.all(np.diff(idx) > 0)
+    cols = idx.astype(np.int64)
+    for key in ("r", "ru", "v", "a"):
+        got = np.load(tmp_path / "s1" / f"{key}.npy")
+        assert np.array_equal(got, outputs[key][:, cols]) and np.array_equal(got, np.load(tmp_path / "s2" / f"{key}.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "epot.npy"), outputs["epot"])
+
+
+def test_bench_arguments():
+    import bench
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert args.steps == 7 and args.warmup == 2 and not args.full and args.dump_outputs is None
+    args = bench.parse_args(["--steps", "1", "--full", "--dump-outputs", "d"])
+    assert args.full and args.dump_outputs == "d"
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])

@@ -25,6 +25,11 @@ PKG = ROOT / "molecular-dynamics-simulation---lennard-jones-monoatomic-fluid_amd
 REF = ROOT / "oracle" / "_ref"
 
 
+def _ref_env():
+    """the drop-in binaries under oracle/_ref/ load THIS tree's libljmd.so, wherever _ref/ itself was built or lies"""
+    return dict(os.environ, LD_LIBRARY_PATH=os.pathsep.join(filter(None, [str(PKG), os.environ.get("LD_LIBRARY_PATH")])))
+
+
 def _workdir(tmp_path, tag):
     src = GOLDEN / (tag if tag.startswith("ref_run_") else f"ref_run_n108_{tag}")
     (tmp_path / "inputs").mkdir()
@@ -233,7 +238,7 @@ def test_reference_main_program_with_gpu_shim(tmp_path):
     """The reference's own md_simulation_program.f90 + md_means/md_correlations/..., with only
     lj_potential_energy.f90 and verlet.f90 swapped for our shim."""
     src = _workdir(tmp_path, "oi10")
-    subprocess.run([str(REF / "md_simulation_program_gpu")], cwd=tmp_path, check=True, timeout=300)
+    subprocess.run([str(REF / "md_simulation_program_gpu")], cwd=tmp_path, check=True, timeout=300, env=_ref_env())
     _compare_run(tmp_path, src, 90)
     # the reference's own summary file is produced by its own statistics code on our numbers
     mine = (tmp_path / "outputs" / "one_run" / "md_final_results.txt").read_text().split()
@@ -253,7 +258,7 @@ def test_reference_init_program_with_gpu_shim(tmp_path):
     ran3 velocities, rescale, 100 warm-up verlet_step calls -- through the GPU shim."""
     src = _workdir(tmp_path, "oi10")
     (tmp_path / "outputs" / "rv_init.dat").unlink()
-    subprocess.run([str(REF / "md_initial_config_program_gpu")], cwd=tmp_path, check=True, timeout=300)
+    subprocess.run([str(REF / "md_initial_config_program_gpu")], cwd=tmp_path, check=True, timeout=300, env=_ref_env())
     r1, v1 = io_formats.read_rv_init(tmp_path / "outputs" / "rv_init.dat", 108)
     r2, v2 = io_formats.read_rv_init(src / "rv_init.dat", 108)
     assert np.abs(r1 - r2).max() < 1e-10 and np.abs(v1 - v2).max() < 1e-9

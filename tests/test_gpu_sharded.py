@@ -251,12 +251,12 @@ def test_bench_two_processes_host_staged_exchange(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     env.update(LJMD_BENCH_SHARE_DEVICE="1", LJMD_BENCH_EXCHANGE="host")
     common = ["--steps", "4", "--warmup", "1", "--particles", "32768", "--no-cpu-baseline"]
-    out2 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2"] + common, env=env,
-                          capture_output=True, text=True, timeout=600)
+    out2 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2"] + common +
+                          ["--dump-outputs", str(tmp_path / "g2")], env=env, capture_output=True, text=True, timeout=600)
     assert out2.returncode == 0, out2.stderr[-2000:]
     line2 = json.loads([ln for ln in out2.stdout.splitlines() if ln.startswith("{")][-1])
-    out1 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1"] + common, capture_output=True,
-                          text=True, timeout=600)
+    out1 = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1"] + common +
+                          ["--dump-outputs", str(tmp_path / "g1")], capture_output=True, text=True, timeout=600)
     assert out1.returncode == 0, out1.stderr[-2000:]
     line1 = json.loads([ln for ln in out1.stdout.splitlines() if ln.startswith("{")][-1])
     assert len([ln for ln in out2.stdout.splitlines() if ln.strip()]) == 1          # stdout = the ONE JSON line
@@ -270,6 +270,12 @@ def test_bench_two_processes_host_staged_exchange(tmp_path):
         a, b = line2["energy_check"][key], line1["energy_check"][key]
         assert abs(a - b) <= 1e-11 * abs(b), (key, a, b)
     assert line2["value"] > 0 and line2["roofline"]["kernel"] == "pair_n3_kernel"
+    # --dump-outputs of the 2-rank run: the ranks' shards back in the input's particle order (the deal by position
+    # at the start moved them), equal to the 1-rank run's up to the summation order of the forces
+    for key in ("r", "ru", "v", "a"):
+        a, b = np.load(tmp_path / "g2" / f"{key}.npy"), np.load(tmp_path / "g1" / f"{key}.npy")
+        assert a.shape == b.shape == (3, 32768), key
+        assert np.abs(a - b).max() <= 1e-10 * np.abs(b).max(), (key, np.abs(a - b).max())
 
 
 # ---- ONE process, several ranks: ljmd_create_multi -----------------------------------------------------------
@@ -596,3 +602,36 @@ def test_multi_device_handle_poisoned_after_failed_batch_and_recovers(monkeypatc
         eng.set_state(r[0], r[1], r[2], v[0], v[1], v[2])
         assert eng.compute_forces() == e_ref
         assert np.array_equal(np.stack(eng.verlet_steps(12), axis=1), sc_ref)
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice_and_full_adds_the_legs(tmp_path):
+    """bench.py --gpus 1: a plain run is the headline alone and --dump-outputs writes what the timed steps returned
+    (the same bytes in a second process); --full adds the liquid and sampled-segment legs."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--particles", "4096"]
+    lines = []
+    for tag in ("d1", "d2"):
+        out = subprocess.run([sys.executable, str(ROOT / "bench.py")] + common + ["--dump-outputs", str(tmp_path / tag)],
+                             capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]))
+    line = lines[0]
+    assert line["metric"] == "md_steps_per_sec_n4096_fp64" and line["unit"] == "steps/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["steps"] == 3 and line["value"] > 0
+    assert abs(line["ms_per_step"] - 1e3 / line["value"]) <= 1e-9 * line["ms_per_step"]
+    assert not any(k in line for k in ("steps_per_s_liquid", "steps_per_s_sampled_segment", "cpu_baseline"))
+    for key in ("r", "ru", "v", "a", "epot", "ekin", "d_epot", "dd_epot"):
+        a, b = np.load(tmp_path / "d1" / f"{key}.npy"), np.load(tmp_path / "d2" / f"{key}.npy")
+        assert a.dtype == np.float64 and a.shape == ((3, 4096) if len(key) <= 2 else (3,)), key
+        assert np.array_equal(a, b), key
+    etot = np.load(tmp_path / "d1" / "epot.npy") + np.load(tmp_path / "d1" / "ekin.npy")
+    assert etot[-1] == line["energy_check"]["etot_last"] and etot[0] == line["energy_check"]["etot_first"]
+    out = subprocess.run([sys.executable, str(ROOT / "bench.py")] + common + ["--full", "--no-cpu-baseline"],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    full = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert full["steps_per_s_liquid"] > 0 and full["steps_per_s_sampled_segment"] > 0
+    assert full["energy_check"] == line["energy_check"]

@@ -31,5 +31,5 @@ if [ -n "$PFX" ] && [ "$PFX" != "$TAG" ]; then
   cp "$OUT/kernel_stats.csv" "profiles/${PFX}_final_kernel_stats.csv"
   cp "$OUT/pmc_instruction_mix.json" "profiles/${PFX}_final_pmc_instruction_mix.json"
 fi
-python3 bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --steps 20 --warmup 3 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 tail -5 "$OUT/summary.log"
