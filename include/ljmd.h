@@ -43,7 +43,9 @@ typedef enum ljmd_status {
     LJMD_ERR_HIP = -3,         /* a HIP runtime call failed */
     LJMD_ERR_STATE = -4,       /* call sequence error (e.g. step before set_state), or a handle poisoned by a
                                   batch of steps that failed half-way: ljmd_set_state makes it usable again */
-    LJMD_ERR_ALLOC = -5
+    LJMD_ERR_ALLOC = -5,
+    LJMD_ERR_RANGE = -6        /* reproducible mode: a term was not finite or |term| >= 2^40 (a pair closer than about
+                                  0.12 sigma, |v| >= 2^20); the handle is poisoned as after a failed batch */
 } ljmd_status;
 
 /* precision_mode for ljmd_create */
@@ -52,6 +54,30 @@ typedef enum ljmd_status {
                                        LJMD_FP32_SPLIT, default 5 sigma; 0 = all but the own row group) in
                                        fp32 tile-relative arithmetic, nearer pairs in fp64; fp64 accumulation
                                        and integrator.  Needs n >= 16384.  BASELINE config 5.             */
+/*
+ * LJMD_PRECISION_FP64_REPRODUCIBLE: results that are a function of the particle set alone -- bitwise independent of
+ * input order, of the number of ranks (both multi-GPU forms), of re-sorting, of every tiling knob and of the launch
+ * form, and bitwise equal to a CPU model of this definition (tests/reproducible_model.py).
+ *   Per ordered pair (i, j), j != i, the reference's arithmetic (lj_potential_energy.f90:109-183): minimum image with
+ *   round (half away from zero), r2 = (dx*dx + dy*dy) + dz*dz, r2 < rc2, u = 1/r2 (IEEE divide), u3 = (u*u)*u,
+ *   u6 = u3*u3, m = 2*u6 - u3, fx = (m*dx)*u; no contraction.  With Q(t) = RNE(t 2^64), an exact integer, and R one
+ *   round-to-nearest-even conversion to fp64:
+ *     a_x(i)  = 24 R(2^-64 sum_j Q(fx_ij))                          (and y, z)
+ *     S12 = sum_{i<j} Q(u6_ij),  S6 = sum_{i<j} Q(u3_ij)             (exact integers)
+ *     epot    =  4 R(2^-64 (S12 - S6))       + tail_e
+ *     d_epot  = 24 R(2^-64 (S6 - 2 S12))     + tail_d
+ *     dd_epot = 24 R(2^-64 (26 S12 - 7 S6))  + tail_dd
+ *     ekin    = 0.5 ((Kx + Ky) + Kz),  Kx = R(2^-64 sum_i Q(vx_i * vx_i))
+ *   The integrator is the fp64 mode's.  Range: every term must be finite with |t| < 2^40, else the call that returns
+ *   the step's results fails with LJMD_ERR_RANGE (never a silent wrap-around); n <= 2^23.  Per-particle sums are
+ *   128-bit, totals 192-bit.  The gather (full-matrix) pair kernel: no Newton-3 form, no fused two-launch step.
+ */
+#define LJMD_PRECISION_FP64_REPRODUCIBLE 2
+/* Exact per-rank step record of the reproducible mode (ljmd_read_partials_exact): five signed 192-bit integers as
+ * three little-endian 64-bit limbs each -- {S12, S6} over this rank's ORDERED pairs, {Kx, Ky, Kz} over its
+ * particles, all in units of 2^-64 -- then one flags word (1 = range error, 2 = forces-only step: no S12 / S6,
+ * 4 = no second half-kick: no Kx / Ky / Kz). */
+#define LJMD_EXACT_PARTIAL_WORDS 16
 
 /* Which state array: argument of ljmd_device_ptr / selectors of get_state. */
 enum { LJMD_R = 0, LJMD_RU = 1, LJMD_V = 2, LJMD_A = 3 };
@@ -188,7 +214,8 @@ int ljmd_kinetic_energy(ljmd_t *h, double *ekin);
 /*
  * Exact signature-level replacement of compute_lj_potential_energy: host arrays in,
  * host arrays out, the params fields passed by value.  Internally keeps one cached
- * engine per (n, L, rc) on device 0.
+ * engine per (n, L, rc) on device 0; LJMD_REPRODUCIBLE=1 in the environment makes it a
+ * LJMD_PRECISION_FP64_REPRODUCIBLE engine.
  */
 int ljmd_compute_lj_potential_energy(int32_t n, double box_length, double rc,
                                      const double *rx, const double *ry, const double *rz,
@@ -327,6 +354,13 @@ int ljmd_read_partials(ljmd_t *h, int32_t nsteps, double *partial);
  * order) into epot, ekin, d_epot, dd_epot incl. prefactors and tail corrections. */
 int ljmd_combine_scalars(const ljmd_t *h, const double *partials_by_rank, int32_t n_ranks,
                          double *epot, double *ekin, double *d_epot, double *dd_epot);
+
+/* The reproducible mode's form of the two calls above: records of LJMD_EXACT_PARTIAL_WORDS int64 words (ljmd_read_partials
+ * returns LJMD_ERR_STATE on such a handle), combined as integers before the single rounding of each scalar;
+ * LJMD_ERR_RANGE when a record carries the range flag. */
+int ljmd_read_partials_exact(ljmd_t *h, int32_t nsteps, int64_t *words);
+int ljmd_combine_scalars_exact(const ljmd_t *h, const int64_t *words_by_rank, int32_t n_ranks,
+                               double *epot, double *ekin, double *d_epot, double *dd_epot);
 
 /*
  * The reference's switch `use_tail_corrections` (scripts/physics/lj_potential_energy.f90:36, a compile-time

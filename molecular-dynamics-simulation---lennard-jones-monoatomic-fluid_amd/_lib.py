@@ -20,12 +20,15 @@ LJMD_ERR_NO_DEVICE = -2
 LJMD_ERR_HIP = -3
 LJMD_ERR_STATE = -4
 LJMD_ERR_ALLOC = -5
+LJMD_ERR_RANGE = -6
 
 PRECISION_FP64 = 0
 PRECISION_FP32_FORCE = 1
+PRECISION_FP64_REPRODUCIBLE = 2   # exact fixed-point sums: results independent of order, ranks and tiling (ljmd.h)
 
 R, RU, V, A = 0, 1, 2, 3
 PARTIAL_STRIDE = 8
+EXACT_PARTIAL_WORDS = 16
 COMM_ID_BYTES = 128
 
 c_double_p = C.POINTER(C.c_double)
@@ -95,6 +98,8 @@ PROTOTYPES = {
                                      C.POINTER(C.c_void_p), c_int64_p]),
     "ljmd_read_partials": (C.c_int, [C.c_void_p, C.c_int32, c_double_p]),
     "ljmd_combine_scalars": (C.c_int, [C.c_void_p, c_double_p, C.c_int32] + [c_double_p] * 4),
+    "ljmd_read_partials_exact": (C.c_int, [C.c_void_p, C.c_int32, c_int64_p]),
+    "ljmd_combine_scalars_exact": (C.c_int, [C.c_void_p, c_int64_p, C.c_int32] + [c_double_p] * 4),
     "ljmd_set_tail_corrections": (C.c_int, [C.c_void_p, C.c_int32]),
     "ljmd_stateless_set_tail_corrections": (None, [C.c_int32]),
     "ljmd_profile_enable": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -271,6 +271,32 @@ int enqueue_pair_forces(ljmd_t *h, EventSet *q)
     }
     const bool fast = fast_path_ok(h);
     if (q) LJMD_HIP(h, hipEventRecord(q->e[1], h->stream));
+    if (reproducible(h)) {
+        // exact fixed-point gather kernel: the tile-pair mask where the fast path's preconditions hold, every tile otherwise
+        if (fast) {
+            const GeometryArgs ga = geometry_args(h);
+            if (!h->boxes_valid) LJMD_HIP(h, launch_tile_boxes(ga, h->stream));
+            LJMD_HIP(h, launch_tile_mask(ga, h->stream));
+        }
+        h->boxes_valid = false;
+        if (q) LJMD_HIP(h, hipEventRecord(q->e[2], h->stream));
+        FixedArgs fa;
+        fa.pos = h->d_pos;
+        fa.mask = h->d_mask;
+        fa.fslab = h->d_fslab;
+        fa.fflag = h->d_fflag;
+        fa.walk_all = fast ? 0 : 1;
+        fa.S = h->S; fa.P = h->P; fa.G = h->G; fa.rank = h->rank; fa.TB = h->TB; fa.T = h->T; fa.W = h->W;
+        fa.chunk = h->chunk_t;
+        fa.energy = h->want_energy ? 1 : 0;
+        fa.L = h->L; fa.invL = h->invL; fa.rc2 = h->rc2;
+        LJMD_HIP(h, launch_pair_fixed(fa, dim3(h->TB / kWavesPerBlock, h->nslab_t), h->stream));
+        if (q) LJMD_HIP(h, hipEventRecord(q->e[3], h->stream));
+        h->pending_energy = h->want_energy;
+        h->reduce_deferred = false;
+        h->forces_pending = true;
+        return LJMD_OK;
+    }
     int nslab, n_wg;
     bool n3 = false;
     if (fast) {
@@ -362,6 +388,33 @@ int enqueue_pair_forces(ljmd_t *h, EventSet *q)
 // second half-kick, kinetic-energy partials and this step's partial record.
 int enqueue_kick(ljmd_t *h, bool kick, EventSet *q)
 {
+    if (reproducible(h)) {
+        // integer sum of the slices, one rounding, x24, kick, exact per-block partials; then ONE record (no force exchange:
+        // every rank owns its rows completely)
+        FixedTailArgs ta;
+        ta.fslab = h->d_fslab;
+        ta.fflag = h->d_fflag;
+        ta.nslab = h->nslab_t;
+        ta.P = h->P;
+        ta.TB = h->TB;
+        ta.a = h->d_a;
+        ta.v = h->d_v;
+        ta.dt_half = h->dt_half;
+        ta.blk = h->d_fblk;
+        LJMD_HIP(h, launch_fixed_tail(ta, kick, h->pending_energy, false, h->stream));
+        FixedFoldArgs fo;
+        fo.blk = h->d_fblk;
+        fo.n_blk = h->P / kBlock;
+        fo.rec = reinterpret_cast<int64_t *>(h->d_ring);
+        fo.ring_pos = h->d_ring_pos;
+        fo.ring_cap = kRingCap;
+        LJMD_HIP(h, launch_fixed_fold(fo, h->stream));
+        if (q) LJMD_HIP(h, hipEventRecord(q->e[4], h->stream));
+        h->ring_issued++;
+        h->have_accel = true;
+        h->forces_pending = false;
+        return LJMD_OK;
+    }
     if (h->reduce_deferred) {
         h->reduce_deferred = false;
         const bool drift = kick && h->next_drift_hint;
@@ -548,9 +601,9 @@ int fetch_ring(ljmd_t *h, unsigned count)
     while (done < count) {
         const unsigned pos = (h->ring_consumed + done) % kRingCap;
         const unsigned run = std::min(count - done, kRingCap - pos);
-        LJMD_HIP(h, hipMemcpyAsync(h->h_ring + (size_t)done * kPartialStride,
-                                   h->d_ring + (size_t)pos * kPartialStride,
-                                   (size_t)run * kPartialStride * sizeof(double),
+        LJMD_HIP(h, hipMemcpyAsync(h->h_ring + (size_t)done * h->rec_stride,
+                                   h->d_ring + (size_t)pos * h->rec_stride,
+                                   (size_t)run * h->rec_stride * sizeof(double),
                                    hipMemcpyDeviceToHost, h->stream));
         done += run;
     }
@@ -580,6 +633,122 @@ void combine_one(const ljmd_t *h, const double *recs, int n_ranks, double *epot,
     if (ekin) *ekin = 0.5 * (kx + ky + kz);                           // verlet.f90:93-95
 }
 
+namespace {
+void neg192(uint64_t (&x)[3])
+{
+    x[0] = ~x[0]; x[1] = ~x[1]; x[2] = ~x[2];
+    const uint64_t one[3] = {1, 0, 0};
+    add192(x, one);
+}
+
+// x k mod 2^192 (k > 0): two's complement wraps consistently, the admissible range never gets near the bound
+void scale192(uint64_t (&x)[3], uint64_t k)
+{
+    unsigned __int128 carry = 0;
+    for (int w = 0; w < 3; ++w) {
+        const unsigned __int128 p = (unsigned __int128)x[w] * k + carry;
+        x[w] = (uint64_t)p;
+        carry = p >> 64;
+    }
+}
+
+// arithmetic shift right by one (the ordered-pair sums are even: u^6_ij and u^6_ji have the same bits)
+void half192(uint64_t (&x)[3])
+{
+    x[0] = (x[0] >> 1) | (x[1] << 63);
+    x[1] = (x[1] >> 1) | (x[2] << 63);
+    x[2] = (uint64_t)((int64_t)x[2] >> 1);
+}
+}  // namespace
+
+static_assert(LJMD_EXACT_PARTIAL_WORDS == kExactWords, "exact record layout out of sync with include/ljmd.h");
+
+int combine_exact(const ljmd_t *h, const int64_t *recs, int n_ranks, double *epot, double *ekin, double *d_epot,
+                  double *dd_epot)
+{
+    uint64_t sum[5][3] = {};
+    int64_t flags = 0;
+    for (int g = 0; g < n_ranks; ++g) {          // integers: the rank order does not matter
+        const int64_t *r = recs + (size_t)g * kExactWords;
+        for (int k = 0; k < 5; ++k) {
+            const uint64_t o[3] = {(uint64_t)r[3 * k], (uint64_t)r[3 * k + 1], (uint64_t)r[3 * k + 2]};
+            add192(sum[k], o);
+        }
+        flags |= r[15];
+    }
+    if (flags & kFlagRange)
+        return fail(h, LJMD_ERR_RANGE, "reproducible mode: a pair or velocity term was not finite or |term| >= 2^40 "
+                                       "(particles closer than about 0.12 sigma?)");
+    half192(sum[0]);                             // ordered -> unordered pairs
+    half192(sum[1]);
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const double te = h->tail_on ? h->tail_e : 0.0, td = h->tail_on ? h->tail_d : 0.0, tdd = h->tail_on ? h->tail_dd : 0.0;
+    const bool have_e = !(flags & kFlagNoEnergy);
+    if (epot) {                                  // 4 R(S12 - S6) + tail_e
+        uint64_t x[3] = {sum[1][0], sum[1][1], sum[1][2]};
+        neg192(x);
+        add192(x, sum[0]);
+        *epot = have_e ? 4.0 * fixed_to_double(x) + te : nan;
+    }
+    if (d_epot) {                                // 24 R(S6 - 2 S12) + tail_d
+        uint64_t x[3] = {sum[0][0], sum[0][1], sum[0][2]};
+        scale192(x, 2);
+        neg192(x);
+        add192(x, sum[1]);
+        *d_epot = have_e ? 24.0 * fixed_to_double(x) + td : nan;
+    }
+    if (dd_epot) {                               // 24 R(26 S12 - 7 S6) + tail_dd
+        uint64_t x[3] = {sum[0][0], sum[0][1], sum[0][2]}, y[3] = {sum[1][0], sum[1][1], sum[1][2]};
+        scale192(x, 26);
+        scale192(y, 7);
+        neg192(y);
+        add192(x, y);
+        *dd_epot = have_e ? 24.0 * fixed_to_double(x) + tdd : nan;
+    }
+    if (ekin) {                                  // 0.5 ((Kx + Ky) + Kz)
+        const double kx = fixed_to_double(sum[2]), ky = fixed_to_double(sum[3]), kz = fixed_to_double(sum[4]);
+        *ekin = (flags & kFlagNoKinetic) ? nan : 0.5 * ((kx + ky) + kz);
+    }
+    return LJMD_OK;
+}
+
+int combine_records(ljmd_t *poison, const ljmd_t *h, const double *recs, int n_ranks, double *epot, double *ekin,
+                    double *d_epot, double *dd_epot)
+{
+    if (!reproducible(h)) {
+        combine_one(h, recs, n_ranks, epot, ekin, d_epot, dd_epot);
+        return LJMD_OK;
+    }
+    std::vector<int64_t> w((size_t)n_ranks * kExactWords);
+    std::memcpy(w.data(), recs, w.size() * sizeof(int64_t));
+    const int rc_ = combine_exact(h, w.data(), n_ranks, epot, ekin, d_epot, dd_epot);
+    if (rc_ == LJMD_ERR_RANGE && poison) {
+        poison->poisoned = true;
+        if (poison != h) poison->err = h->err;
+    }
+    return rc_;
+}
+
+int kinetic_exact(ljmd_t *h, int64_t *rec)
+{
+    FixedTailArgs ta{};
+    ta.P = h->P;
+    ta.TB = h->TB;
+    ta.v = h->d_v;
+    ta.blk = h->d_fblk;
+    LJMD_HIP(h, launch_fixed_tail(ta, false, false, true, h->stream));
+    FixedFoldArgs fo;
+    fo.blk = h->d_fblk;
+    fo.n_blk = h->P / kBlock;
+    fo.rec = h->d_frec;
+    fo.ring_pos = nullptr;
+    fo.ring_cap = 1;
+    LJMD_HIP(h, launch_fixed_fold(fo, h->stream));
+    LJMD_HIP(h, hipMemcpyAsync(rec, h->d_frec, kExactWords * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    LJMD_HIP(h, hipStreamSynchronize(h->stream));
+    return LJMD_OK;
+}
+
 void release(ljmd_t *h)
 {
     if (!h) return;
@@ -603,7 +772,7 @@ void release(ljmd_t *h)
                    h->d_perm, h->d_perm2, h->d_tmp3, h->d_cub, h->d_slab_j, h->d_flag_j, h->d_fpart, h->d_frecv, h->d_fall,
                    h->d_kd_offsets, h->d_kd_keys, h->d_kd_keys2, h->d_mask_far, h->d_slab_j2, h->d_flag_j2, h->d_fold, h->d_ticket,
                    h->d_desc, h->d_desc_far, h->d_desc2, h->d_ke_tile, h->d_pos_tc, h->d_gid0, h->d_mig, h->d_mig_idx, h->d_mig_idx2, h->d_mig_keys,
-                   h->d_mig_keys2, h->d_mig_offsets, h->d_mig_cub};
+                   h->d_mig_keys2, h->d_mig_offsets, h->d_mig_cub, h->d_fslab, h->d_fflag, h->d_fblk, h->d_frec};
     for (void *p : dev) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
     if (h->h_ring) (void)hipHostFree(h->h_ring);
@@ -838,8 +1007,11 @@ int ljmd_create(ljmd_t **out, int32_t n, double box_length, double dt, double rc
     if (rc >= 0.5 * box_length)
         return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_create: rc must be < L/2 (minimum image convention)");
     if (!(dt > 0.0)) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_create: dt must be > 0");
-    if (precision_mode != LJMD_PRECISION_FP64 && precision_mode != LJMD_PRECISION_FP32_FORCE)
+    if (precision_mode != LJMD_PRECISION_FP64 && precision_mode != LJMD_PRECISION_FP32_FORCE &&
+        precision_mode != LJMD_PRECISION_FP64_REPRODUCIBLE)
         return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_create: precision_mode %d not available", precision_mode);
+    if (precision_mode == LJMD_PRECISION_FP64_REPRODUCIBLE && n > kFixedMaxN)
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_create: LJMD_PRECISION_FP64_REPRODUCIBLE takes n <= %d", kFixedMaxN);
     if (n_ranks < 1 || rank < 0 || rank >= n_ranks)
         return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_create: bad rank %d of %d", rank, n_ranks);
     if (n % n_ranks != 0)
@@ -987,7 +1159,8 @@ int ljmd_create(ljmd_t **out, int32_t n, double box_length, double dt, double rc
         // (rc within 1e-9 of L/2 -- the reference accepts rc_over_L up to 0.5 and rejects only rc >= L/2 -- takes the exact
         //  generic kernel, which has no Newton-3 form: a multi-rank run then needs no force exchange at all, and every
         //  rank must know that when it allocates)
-        h->use_n3 = env_int("LJMD_N3", 1) != 0 && n >= n3_min && (h->G == 1 || h->rc_allows_fast);
+        h->use_n3 = env_int("LJMD_N3", 1) != 0 && n >= n3_min && (h->G == 1 || h->rc_allows_fast) &&
+                    precision_mode != LJMD_PRECISION_FP64_REPRODUCIBLE;   // (the fixed-point kernel is a gather kernel)
         // work items = (row group, slice of its units), N3Args::uchunk.  Large systems: slices of whole offsets (dchunk),
         // ~target_waves items; a system with fewer (row group, offset) pairs than that is cut finer, down to one pass per item.
         const int n_off = h->Dmax + h->wg_waves;          // offsets a workgroup walks (relative to its first row group)
@@ -1080,7 +1253,14 @@ int ljmd_create(ljmd_t **out, int32_t n, double box_length, double dt, double rc
             LJMD_HIP(h, hipMalloc(&h->d_ke_tile, 2 * 3 * (size_t)h->T * sizeof(double)));        // two buffers, as wg_part
             LJMD_HIP(h, hipMemsetAsync(h->d_ke_tile, 0, 2 * 3 * (size_t)h->T * sizeof(double), h->stream));
         }
-        LJMD_HIP(h, hipMalloc(&h->d_ring, (size_t)kRingCap * kPartialStride * sizeof(double)));
+        if (precision_mode == LJMD_PRECISION_FP64_REPRODUCIBLE) {
+            h->rec_stride = kExactWords;
+            LJMD_HIP(h, hipMalloc(&h->d_fslab, (size_t)h->nslab_t * kFixedQuantities * h->P * sizeof(__int128)));
+            LJMD_HIP(h, hipMalloc(&h->d_fflag, (size_t)h->nslab_t * h->TB * sizeof(unsigned)));
+            LJMD_HIP(h, hipMalloc(&h->d_fblk, (size_t)row_blocks * kExactWords * sizeof(int64_t)));
+            LJMD_HIP(h, hipMalloc(&h->d_frec, kExactWords * sizeof(int64_t)));
+        }
+        LJMD_HIP(h, hipMalloc(&h->d_ring, (size_t)kRingCap * h->rec_stride * sizeof(double)));
         LJMD_HIP(h, hipMalloc(&h->d_ring_pos, sizeof(unsigned)));
         LJMD_HIP(h, hipMalloc(&h->d_bbox, (size_t)h->T * kBoxStride * sizeof(double)));
         LJMD_HIP(h, hipMalloc(&h->d_mask, (size_t)h->TB * h->W * sizeof(uint64_t)));
@@ -1102,7 +1282,7 @@ int ljmd_create(ljmd_t **out, int32_t n, double box_length, double dt, double rc
         LJMD_HIP(h, hipMemsetAsync(h->d_a, 0, P3, h->stream));
         LJMD_HIP(h, hipMemsetAsync(h->d_ke_part, 0, 3 * (size_t)h->n_ke * sizeof(double), h->stream));
         LJMD_HIP(h, hipHostMalloc(&h->h_stage, P3 * std::max(h->G, 4), hipHostMallocDefault));   // G position blocks, or r, ru, v, a
-        LJMD_HIP(h, hipHostMalloc(&h->h_ring, (size_t)kRingCap * kPartialStride * sizeof(double),
+        LJMD_HIP(h, hipHostMalloc(&h->h_ring, (size_t)kRingCap * h->rec_stride * sizeof(double),
                                   hipHostMallocDefault));
         LJMD_HIP(h, hipStreamSynchronize(h->stream));
         return LJMD_OK;
@@ -1277,8 +1457,7 @@ int ljmd_compute_forces(ljmd_t *h, double *epot, double *d_epot, double *dd_epot
     if (rc_ != LJMD_OK) return rc_;
     rc_ = fetch_ring(h, 1);
     if (rc_ != LJMD_OK) return rc_;
-    combine_one(h, h->h_ring, 1, epot, nullptr, d_epot, dd_epot);
-    return LJMD_OK;
+    return combine_records(h, h, h->h_ring, 1, epot, nullptr, d_epot, dd_epot);
 }
 
 int ljmd_verlet_steps(ljmd_t *h, int32_t nsteps, double *epot, double *ekin, double *d_epot,
@@ -1327,10 +1506,12 @@ int ljmd_verlet_steps(ljmd_t *h, int32_t nsteps, double *epot, double *ekin, dou
         h->want_energy = keep;
         int rc_ = fetch_ring(h, (unsigned)batch);
         if (rc_ != LJMD_OK) return rc_;
-        for (int s = 0; s < batch; ++s)
-            combine_one(h, h->h_ring + (size_t)s * kPartialStride, 1, epot ? epot + done + s : nullptr,
-                        ekin ? ekin + done + s : nullptr, d_epot ? d_epot + done + s : nullptr,
-                        dd_epot ? dd_epot + done + s : nullptr);
+        for (int s = 0; s < batch; ++s) {
+            rc_ = combine_records(h, h, h->h_ring + (size_t)s * h->rec_stride, 1, epot ? epot + done + s : nullptr,
+                                  ekin ? ekin + done + s : nullptr, d_epot ? d_epot + done + s : nullptr,
+                                  dd_epot ? dd_epot + done + s : nullptr);
+            if (rc_ != LJMD_OK) return rc_;
+        }
         done += batch;
     }
     return LJMD_OK;
@@ -1409,9 +1590,12 @@ int ljmd_collect_steps(ljmd_t *h, int32_t nsteps, double *epot, double *ekin, do
     LJMD_HIP(h, hipSetDevice(h->device));
     const int rc_ = fetch_ring(h, (unsigned)nsteps);
     if (rc_ != LJMD_OK) return rc_;
-    for (int s = 0; s < nsteps; ++s)
-        combine_one(h, h->h_ring + (size_t)s * kPartialStride, 1, epot ? epot + s : nullptr,
-                    ekin ? ekin + s : nullptr, d_epot ? d_epot + s : nullptr, dd_epot ? dd_epot + s : nullptr);
+    for (int s = 0; s < nsteps; ++s) {
+        const int rc2_ = combine_records(h, h, h->h_ring + (size_t)s * h->rec_stride, 1, epot ? epot + s : nullptr,
+                                         ekin ? ekin + s : nullptr, d_epot ? d_epot + s : nullptr,
+                                         dd_epot ? dd_epot + s : nullptr);
+        if (rc2_ != LJMD_OK) return rc2_;
+    }
     return LJMD_OK;
 }
 
@@ -1484,6 +1668,12 @@ int ljmd_kinetic_energy(ljmd_t *h, double *ekin)
     if (!h->have_state) return fail(h, LJMD_ERR_STATE, "ljmd_kinetic_energy: no state has been set");
     if (h->multi) return ljmdm::kinetic_energy(h, ekin);
     LJMD_HIP(h, hipSetDevice(h->device));
+    if (reproducible(h)) {                       // 0.5 ((Kx + Ky) + Kz), exact sums; per-rank part when sharded
+        int64_t rec[kExactWords];
+        const int rc_ = kinetic_exact(h, rec);
+        if (rc_ != LJMD_OK) return rc_;
+        return combine_exact(h, rec, 1, nullptr, ekin, nullptr, nullptr);
+    }
     LJMD_HIP(h, launch_kinetic_fused(integrate_args(h), h->stream));
     std::vector<double> part(3 * (size_t)h->n_ke);
     LJMD_HIP(h, hipMemcpyAsync(part.data(), h->d_ke_part, part.size() * sizeof(double),
@@ -1602,6 +1792,8 @@ int ljmd_read_partials(ljmd_t *h, int32_t nsteps, double *partial)
     if (!h || !partial || nsteps < 0 || nsteps > (int)kRingCap)
         return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_read_partials: bad argument");
     if (h->multi) return fail(h, LJMD_ERR_STATE, "ljmd_read_partials: a multi-device handle combines its ranks itself");
+    if (reproducible(h))
+        return fail(h, LJMD_ERR_STATE, "ljmd_read_partials: reproducible handle; use ljmd_read_partials_exact");
     LJMD_HIP(h, hipSetDevice(h->device));
     int rc_ = fetch_ring(h, (unsigned)nsteps);
     if (rc_ != LJMD_OK) return rc_;
@@ -1609,11 +1801,37 @@ int ljmd_read_partials(ljmd_t *h, int32_t nsteps, double *partial)
     return LJMD_OK;
 }
 
+int ljmd_read_partials_exact(ljmd_t *h, int32_t nsteps, int64_t *words)
+{
+    if (!h || !words || nsteps < 0 || nsteps > (int)kRingCap)
+        return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_read_partials_exact: bad argument");
+    if (h->multi) return fail(h, LJMD_ERR_STATE, "ljmd_read_partials_exact: a multi-device handle combines its ranks itself");
+    if (!reproducible(h))
+        return fail(h, LJMD_ERR_STATE, "ljmd_read_partials_exact: not a LJMD_PRECISION_FP64_REPRODUCIBLE handle");
+    LJMD_HIP(h, hipSetDevice(h->device));
+    int rc_ = fetch_ring(h, (unsigned)nsteps);
+    if (rc_ != LJMD_OK) return rc_;
+    std::memcpy(words, h->h_ring, (size_t)nsteps * kExactWords * sizeof(int64_t));
+    return LJMD_OK;
+}
+
+int ljmd_combine_scalars_exact(const ljmd_t *h, const int64_t *words_by_rank, int32_t n_ranks, double *epot,
+                               double *ekin, double *d_epot, double *dd_epot)
+{
+    if (!h || !words_by_rank || n_ranks < 1)
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_combine_scalars_exact: bad argument");
+    if (!reproducible(h))
+        return fail(h, LJMD_ERR_STATE, "ljmd_combine_scalars_exact: not a LJMD_PRECISION_FP64_REPRODUCIBLE handle");
+    return combine_exact(h, words_by_rank, n_ranks, epot, ekin, d_epot, dd_epot);
+}
+
 int ljmd_combine_scalars(const ljmd_t *h, const double *partials_by_rank, int32_t n_ranks, double *epot,
                          double *ekin, double *d_epot, double *dd_epot)
 {
     if (!h || !partials_by_rank || n_ranks < 1)
         return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_combine_scalars: bad argument");
+    if (reproducible(h))
+        return fail(h, LJMD_ERR_STATE, "ljmd_combine_scalars: reproducible handle; use ljmd_combine_scalars_exact");
     combine_one(h, partials_by_rank, n_ranks, epot, ekin, d_epot, dd_epot);
     return LJMD_OK;
 }
@@ -1799,6 +2017,7 @@ const char *ljmd_pair_kernel_name(const ljmd_t *h)
 {
     if (!h) return "";
     if (h->multi) return ljmdm::pair_kernel_name(h);
+    if (reproducible(h)) return "pair_fixed_kernel";
     if (!fast_path_ok(h)) return "pair_rows_generic_kernel";
     if (h->use_n3 && h->mode == LJMD_PRECISION_FP32_FORCE) return "pair_n3_f32_kernel";
     return h->use_n3 ? "pair_n3_kernel" : "pair_tiles_kernel";
@@ -1945,7 +2164,8 @@ int cached_engine(int32_t n, double L, double dt, double rc, ljmd_t **out)
         g_last_valid = false;
     }
     if (!g_cached) {
-        int rc_ = ljmd_create(&g_cached, n, L, dt, rc, LJMD_PRECISION_FP64, env_int("LJMD_DEVICE", 0), 0, 1);
+        const int mode = env_int("LJMD_REPRODUCIBLE", 0) != 0 ? LJMD_PRECISION_FP64_REPRODUCIBLE : LJMD_PRECISION_FP64;
+        int rc_ = ljmd_create(&g_cached, n, L, dt, rc, mode, env_int("LJMD_DEVICE", 0), 0, 1);
         if (rc_ != LJMD_OK) return rc_;
         g_last_valid = false;
     }
@@ -2022,7 +2242,10 @@ int ljmd_verlet_step(int32_t n, double box_length, double dt, double rc, double 
         g_last_error = h->err;
         return rc_;
     }
-    combine_one(h, h->h_ring, 1, epot, ekin, d_epot, dd_epot);
+    if ((rc_ = combine_records(h, h, h->h_ring, 1, epot, ekin, d_epot, dd_epot)) != LJMD_OK) {
+        g_last_error = h->err;
+        return rc_;
+    }
     g_last_out.resize(9 * (size_t)n);
     for (int k = 0; k < 9; ++k) std::memcpy(g_last_out.data() + (size_t)k * n, arr[k], (size_t)n * sizeof(double));
     g_last_valid = true;

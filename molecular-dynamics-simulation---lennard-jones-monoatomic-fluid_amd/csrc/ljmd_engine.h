@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -115,7 +116,14 @@ struct ljmd {
     double *d_ke_tile = nullptr;      // [T][3] per-tile sums of v^2
     bool boxes_valid = false;     // d_bbox already holds the boxes of the current positions (written by the drift kernel)
     double *d_ke_part = nullptr;  // [n_ke][3]
-    double *d_ring = nullptr;     // [kRingCap][kPartialStride]
+    double *d_ring = nullptr;     // [kRingCap][rec_stride] (reproducible mode: int64 words)
+    int rec_stride = kPartialStride;  // 8-byte words per step record: kPartialStride, or kExactWords in the reproducible mode
+    // reproducible mode (LJMD_PRECISION_FP64_REPRODUCIBLE, ljmd_internal.h: FixedArgs)
+    __int128 *d_fslab = nullptr;  // [nslab_t][kFixedQuantities][P]
+    unsigned *d_fflag = nullptr;  // [nslab_t][TB]
+    int64_t *d_fblk = nullptr;    // [P / kBlock][kExactWords]
+    int64_t *d_frec = nullptr;    // [kExactWords]: the record of ljmd_kinetic_energy
+    bool pending_energy = true;   // the pending pair evaluation summed u^6, u^3
     unsigned *d_ring_pos = nullptr;
     double *d_bbox = nullptr;     // [T][kBoxStride]
     uint64_t *d_mask = nullptr;   // [TB][W]
@@ -242,6 +250,15 @@ int enqueue_forces(ljmd_t *h, bool kick, EventSet *q, bool next_drift = false);
 int fetch_ring(ljmd_t *h, unsigned count);
 void combine_one(const ljmd_t *h, const double *recs, int n_ranks, double *epot, double *ekin, double *d_epot,
                  double *dd_epot);
+inline bool reproducible(const ljmd_t *h) { return h->mode == LJMD_PRECISION_FP64_REPRODUCIBLE; }
+// the reproducible mode's combination of n_ranks exact records (kExactWords each); LJMD_ERR_RANGE on a range flag
+int combine_exact(const ljmd_t *h, const int64_t *recs, int n_ranks, double *epot, double *ekin, double *d_epot,
+                  double *dd_epot);
+// either mode: records of h->rec_stride words as fetch_ring leaves them; a range error poisons `poison`
+int combine_records(ljmd_t *poison, const ljmd_t *h, const double *recs, int n_ranks, double *epot, double *ekin,
+                    double *d_epot, double *dd_epot);
+// reproducible mode: this engine's exact record of sum v^2 (Kx, Ky, Kz words) of the resident velocities
+int kinetic_exact(ljmd_t *h, int64_t *rec /* [kExactWords] */);
 EventSet *next_events(ljmd_t *h);
 void release(ljmd_t *h);
 // ownership migration in three phases, all on the engine's stream: (1) the own block of the migration buffer <- ru, v, a,

@@ -144,6 +144,109 @@ struct GeometryArgs {
     int both_ties;          // tile_class: the tie d = NG / 2 is visited from both sides (N3Args::both_ties)
 };
 
+// ---- reproducible mode (LJMD_PRECISION_FP64_REPRODUCIBLE): exact fixed-point sums ----
+// Every per-pair term t (fx, fy, fz, u^6, u^3) and every v^2 enters as the integer Q(t) = RNE(t 2^64); |t| < 2^40 (else
+// the step fails with LJMD_ERR_RANGE), so |Q(t)| < 2^104.  A particle's sum of at most n - 1 < 2^23 terms fits a signed
+// 128-bit integer; totals over particles and ranks are 192-bit.  Integer sums do not depend on their order: results
+// are a function of the particle set alone.
+constexpr int kExactWords = 16;             // int64 words per exact step record (LJMD_EXACT_PARTIAL_WORDS)
+constexpr int kFixedQuantities = 5;         // per-particle sums of the pair kernel: ax, ay, az, u^6, u^3
+constexpr int kFixedMaxN = 1 << 23;         // largest n of the mode: (n - 1) 2^104 < 2^127
+constexpr double kFixedBound = 0x1p40;      // terms must satisfy |t| < kFixedBound
+// flags word of an exact record
+constexpr int64_t kFlagRange = 1;           // a term was not finite or |t| >= kFixedBound
+constexpr int64_t kFlagNoEnergy = 2;        // forces-only evaluation: S12, S6 not summed
+constexpr int64_t kFlagNoKinetic = 4;       // no second half-kick: Kx, Ky, Kz not summed
+
+struct FixedArgs {
+    const double *pos;      // exchange buffer [G][3][P]
+    const uint64_t *mask;   // [TB][W] tile-pair mask (tile_mask_kernel), unused with walk_all
+    __int128 *fslab;        // [nslab][kFixedQuantities][P] per-row sums of Q(term) of one column slice
+    unsigned *fflag;        // [nslab][TB] 1 = a term of this (slice, row tile) was out of range
+    int walk_all;           // 1: every column tile (positions / rc outside the fast path's preconditions)
+    int S, P, G, rank, TB, T, W;
+    int chunk;              // column tiles per grid.y slice
+    int energy;             // 0: forces-only instantiation (u^6, u^3 not summed)
+    double L, invL, rc2;
+};
+
+struct FixedTailArgs {
+    const __int128 *fslab;
+    const unsigned *fflag;
+    int nslab, P, TB;
+    double *a, *v;          // [3][P] of the owned rows
+    double dt_half;
+    int64_t *blk;           // [P / kBlock][kExactWords] per-block record partials
+};
+
+struct FixedFoldArgs {
+    const int64_t *blk;
+    int n_blk;
+    int64_t *rec;           // ring_pos != NULL: ring [ring_cap][kExactWords], record at *ring_pos; else ONE record
+    unsigned *ring_pos;
+    unsigned ring_cap;
+};
+
+// signed 192-bit integers as three little-endian 64-bit limbs (two's complement)
+__host__ __device__ inline void add192(uint64_t (&a)[3], const uint64_t (&b)[3])
+{
+    const uint64_t s0 = a[0] + b[0];
+    const uint64_t c0 = s0 < a[0];
+    const uint64_t s1 = a[1] + b[1];
+    uint64_t c1 = s1 < a[1];
+    const uint64_t s1c = s1 + c0;
+    c1 += s1c < s1;
+    a[2] = a[2] + b[2] + c1;
+    a[1] = s1c;
+    a[0] = s0;
+}
+
+__host__ __device__ inline void from128(uint64_t (&a)[3], __int128 x)
+{
+    a[0] = (uint64_t)x;
+    a[1] = (uint64_t)(x >> 64);
+    a[2] = x < 0 ? ~0ull : 0ull;
+}
+
+// RNE(x) * 2^-64 for a signed 192-bit x: ONE correctly rounded conversion (the scaling by 2^-64 is exact)
+__host__ __device__ inline double fixed_to_double(const uint64_t (&x)[3])
+{
+    uint64_t m[3] = {x[0], x[1], x[2]};
+    const bool neg = (int64_t)m[2] < 0;
+    if (neg) {                                      // magnitude: ~m + 1
+        m[0] = ~m[0]; m[1] = ~m[1]; m[2] = ~m[2];
+        const uint64_t one[3] = {1, 0, 0};
+        add192(m, one);
+    }
+    const int top = m[2] ? 2 : m[1] ? 1 : m[0] ? 0 : -1;
+    if (top < 0) return 0.0;
+    const int msb = 64 * top + 63 - __builtin_clzll(m[top]);
+    auto bits64 = [&](int s) -> uint64_t {         // bits [s, s + 64) of m, s >= 0
+        const int w = s >> 6, o = s & 63;
+        const uint64_t lo = w < 3 ? m[w] >> o : 0ull;
+        const uint64_t hi = (o && w + 1 < 3) ? m[w + 1] << (64 - o) : 0ull;
+        return lo | hi;
+    };
+    double r;
+    if (msb <= 52) {
+        r = (double)m[0];                           // exact
+        r = ldexp(r, -64);
+    } else {
+        const int sh = msb - 52;                    // bits below the 53-bit significand
+        uint64_t mant = bits64(sh) & ((1ull << 53) - 1ull);
+        const bool round_bit = (bits64(sh - 1) & 1ull) != 0;
+        bool sticky = false;                        // any of the bits [0, sh - 1)
+        for (int w = 0; w < 3; ++w) {
+            const int b0 = 64 * w, k = sh - 1 - b0;   // bits of word w below sh - 1
+            if (k <= 0) break;
+            sticky = sticky || (k >= 64 ? m[w] != 0 : (m[w] & ((1ull << k) - 1ull)) != 0);
+        }
+        if (round_bit && (sticky || (mant & 1ull))) ++mant;   // 2^53 at most: still exact
+        r = ldexp((double)mant, sh - 64);
+    }
+    return neg ? -r : r;
+}
+
 struct RdfArgs {
     const double *x, *y, *z;       // [n] one snapshot, wrapped coordinates
     unsigned long long *hist;      // [nbins] ordered-pair counts (added to)
@@ -175,6 +278,11 @@ hipError_t launch_finalize(const FinalizeArgs &a, double *fold_scratch /* [2 * k
 // block per tile; kick without drift = the last step of a batch, neither = a plain force evaluation
 hipError_t launch_tile_tail(const ReduceArgs &ra, const IntegrateArgs &a, const FinalizeArgs &f, const FinalizeArgs &prev, bool kick,
                             bool drift, hipStream_t s);
+// reproducible mode: pair kernel, then reduction + conversion + x24 (+ kick) with per-block exact partials, then the fold
+// of those into one exact record (ring slot or single record); ke_only: the per-block Kx, Ky, Kz of the resident velocities
+hipError_t launch_pair_fixed(const FixedArgs &a, dim3 grid, hipStream_t s);
+hipError_t launch_fixed_tail(const FixedTailArgs &a, bool kick, bool energy, bool ke_only, hipStream_t s);
+hipError_t launch_fixed_fold(const FixedFoldArgs &a, hipStream_t s);
 hipError_t launch_rdf_histogram(const RdfArgs &a, dim3 grid, hipStream_t s);
 hipError_t launch_time_origin(const TimeOriginArgs &a, bool vacf, int n_origins, hipStream_t s);
 hipError_t launch_tile_boxes(const GeometryArgs &a, hipStream_t s);

@@ -2228,9 +2228,275 @@ __global__ __launch_bounds__(kBlock) void time_origin_kernel(TimeOriginArgs a)
     if (threadIdx.x == 0) a.term[(size_t)blockIdx.y * (a.max_lag + 1) + lag] = s[0] / (double)a.n;
 }
 
+// ===========================================================================
+// REPRODUCIBLE mode (LJMD_PRECISION_FP64_REPRODUCIBLE, ljmd_internal.h: FixedArgs).  Per ordered pair the generic
+// kernel's arithmetic -- the reference's own terms -- and every term t enters an integer sum as Q(t) = RNE(t 2^64).
+// Integer sums are exact in any order, so the slice count, the tile order, the re-sort, the rank split and the launch
+// form cannot change a bit of the result.
+// ===========================================================================
+
+// acc += Q(t), |t| < 2^40.  v = RNE(t 2^64) is an integer-valued double, |v| < 2^104; split exactly at 2^62:
+// hi = trunc(v 2^-62), lo = v - hi 2^62 (|lo| < 2^62, a multiple of ulp(v): representable), both convert exactly.
+__device__ __forceinline__ void fixed_add(__int128 &acc, double t)
+{
+    const double v = __builtin_rint(t * 0x1p64);
+    const double hi = __builtin_trunc(v * 0x1p-62);
+    const double lo = v - hi * 0x1p62;
+    acc += ((__int128)(int64_t)hi << 62) + (__int128)(int64_t)lo;
+}
+
+__device__ __forceinline__ bool fixed_out_of_range(double t) { return !(__builtin_fabs(t) < kFixedBound); }
+
+template <bool ENERGY>
+__device__ __forceinline__ void pair_fixed(double xi, double yi, double zi, double xj, double yj, double zj, double L,
+                                           double invL, double rc2, bool is_self, __int128 &ax, __int128 &ay,
+                                           __int128 &az, __int128 &s12, __int128 &s6, bool &bad)
+{
+    const double dx0 = xi - xj, dy0 = yi - yj, dz0 = zi - zj;
+    const double dx = dx0 - L * __builtin_round(dx0 * invL);          // geometry_pbc.f90:86
+    const double dy = dy0 - L * __builtin_round(dy0 * invL);
+    const double dz = dz0 - L * __builtin_round(dz0 * invL);
+    const double r2 = dx * dx + dy * dy + dz * dz;                    // lj_potential_energy.f90:129
+    if (r2 < rc2 && !is_self) {                                       // :132
+        const double u = 1.0 / r2;                                    // :135
+        const double u3 = u * u * u;                                  // :136
+        const double u6 = u3 * u3;                                    // :137
+        const double mdu = 2.0 * u6 - u3;                             // :143
+        const double fx = mdu * dx * u, fy = mdu * dy * u, fz = mdu * dz * u;   // :148-155
+        // u^3 <= max(1, u^6): the u^6 test covers it, and both instantiations test the same terms
+        const bool oob = fixed_out_of_range(fx) || fixed_out_of_range(fy) || fixed_out_of_range(fz) ||
+                         fixed_out_of_range(u6);
+        bad = bad || oob;
+        fixed_add(ax, oob ? 0.0 : fx);
+        fixed_add(ay, oob ? 0.0 : fy);
+        fixed_add(az, oob ? 0.0 : fz);
+        if constexpr (ENERGY) {
+            fixed_add(s12, oob ? 0.0 : u6);
+            fixed_add(s6, oob ? 0.0 : u3);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Pair kernel of the reproducible mode: pair_tiles_kernel's structure -- one wave per 64-particle row tile, the
+// tile-pair mask walk, column coordinates through scalar loads, grid = (TB / 4, column-tile slices) -- with per-lane
+// 128-bit accumulators.  walk_all: every column tile (unwrapped positions, rc within 1e-9 of L/2: the mask's
+// precondition does not hold).  Output: the slice's integer row sums and one range flag per (slice, row tile).
+// ---------------------------------------------------------------------------
+template <bool ENERGY>
+__global__ __launch_bounds__(kBlock) void pair_fixed_kernel(FixedArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int Il = blockIdx.x * kWavesPerBlock + wave;          // own tile, wave-uniform
+    const int I = a.rank * a.TB + Il;
+    const int row = Il * kTile + lane;
+    const double *own = a.pos + (size_t)a.rank * 3 * a.P;
+    const double xi = own[row], yi = own[a.P + row], zi = own[2 * (size_t)a.P + row];   // NaN on padding
+
+    __int128 ax = 0, ay = 0, az = 0, s12 = 0, s6 = 0;
+    bool bad = false;
+
+    const uint64_t *mrow = a.mask + (size_t)Il * a.W;
+    const int J0 = blockIdx.y * a.chunk, J1 = min(J0 + a.chunk, a.T);
+    for (int w = J0 >> 6; w <= (J1 - 1) >> 6 && J0 < J1; ++w) {
+        uint64_t m = a.walk_all ? ~0ull : mrow[w];
+        const int lo = max(J0 - w * 64, 0), hi = min(J1 - w * 64, 64);      // bits of this word inside the slice
+        m &= (hi >= 64 ? ~0ull : ((1ull << hi) - 1ull)) & ~((1ull << lo) - 1ull);
+        while (m) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            const int J = w * 64 + b;
+            const int gj = (a.G == 1) ? 0 : J / a.TB;
+            const int jl = (J - gj * a.TB) * kTile;
+            const double *bx = a.pos + (size_t)gj * 3 * a.P + jl;
+            const double *by = bx + a.P, *bz = by + a.P;
+            const bool self_tile = J == I;
+            for (int j0 = 0; j0 < kTile; j0 += 8) {
+                double xj[8], yj[8], zj[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { xj[k] = bx[j0 + k]; yj[k] = by[j0 + k]; zj[k] = bz[j0 + k]; }
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    pair_fixed<ENERGY>(xi, yi, zi, xj[k], yj[k], zj[k], a.L, a.invL, a.rc2, self_tile && j0 + k == lane,
+                                       ax, ay, az, s12, s6, bad);
+            }
+        }
+    }
+
+    __int128 *s = a.fslab + (size_t)blockIdx.y * kFixedQuantities * a.P + row;
+    s[0] = ax;
+    s[a.P] = ay;
+    s[2 * (size_t)a.P] = az;
+    if constexpr (ENERGY) {
+        s[3 * (size_t)a.P] = s12;
+        s[4 * (size_t)a.P] = s6;
+    }
+    const uint64_t any_bad = __ballot(bad);
+    if (lane == 0) a.fflag[(size_t)blockIdx.y * a.TB + Il] = any_bad != 0ull ? 1u : 0u;
+}
+
+// Block-wide sum of five signed 192-bit values per thread; the result is valid in thread 0.
+__device__ __forceinline__ void block_sum192(uint64_t (&q)[5][3], uint64_t (*lds)[5][3] /* [kWavesPerBlock] */)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            uint64_t o[3];
+#pragma unroll
+            for (int w = 0; w < 3; ++w) o[w] = __shfl_down(q[k][w], off, 64);
+            add192(q[k], o);
+        }
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+#pragma unroll
+            for (int w = 0; w < 3; ++w) lds[wave][k][w] = q[k][w];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int v = 1; v < kWavesPerBlock; ++v)
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const uint64_t o[3] = {lds[v][k][0], lds[v][k][1], lds[v][k][2]};
+                add192(q[k], o);
+            }
+}
+
+// ---------------------------------------------------------------------------
+// Everything behind the pair kernel, one thread per slot: the integer sum of the slices, ONE rounding to fp64, x24
+// (lj_potential_energy.f90:189-191), the second half-kick (verlet.f90:86-88), Q(v^2) per axis, and this block's exact
+// partial record {S12, S6, Kx, Ky, Kz (192-bit each), flags}.  KE_ONLY: only Kx, Ky, Kz of the resident velocities
+// (t = 0, md_simulation_program.f90:238-240).  grid = P / 256.
+// ---------------------------------------------------------------------------
+template <bool KICK, bool ENERGY, bool KE_ONLY>
+__global__ __launch_bounds__(kBlock) void fixed_tail_kernel(FixedTailArgs a)
+{
+    __shared__ uint64_t red[kWavesPerBlock][5][3];
+    const int i = blockIdx.x * kBlock + threadIdx.x;            // < P: the grid is P / 256
+    const int lane = threadIdx.x & 63;
+    bool bad = false;
+    uint64_t q[5][3] = {};
+    if constexpr (!KE_ONLY) {
+        const int tile = i >> 6;
+        for (int c = lane; c < a.nslab; c += 64) bad = bad || a.fflag[(size_t)c * a.TB + tile] != 0u;
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            __int128 f = 0;
+            for (int c = 0; c < a.nslab; ++c) f += a.fslab[((size_t)c * kFixedQuantities + ax) * a.P + i];
+            uint64_t w[3];
+            from128(w, f);
+            const size_t o = (size_t)ax * a.P + i;
+            const double acc = 24.0 * fixed_to_double(w);
+            a.a[o] = acc;
+            if constexpr (KICK) {
+                const double v1 = a.v[o] + acc * a.dt_half;
+                a.v[o] = v1;
+                const double t = v1 * v1;
+                const bool oob = fixed_out_of_range(t);
+                bad = bad || oob;
+                __int128 k = 0;
+                fixed_add(k, oob ? 0.0 : t);
+                from128(q[2 + ax], k);
+            }
+        }
+        if constexpr (ENERGY) {
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                __int128 f = 0;
+                for (int c = 0; c < a.nslab; ++c) f += a.fslab[((size_t)c * kFixedQuantities + 3 + e) * a.P + i];
+                from128(q[e], f);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int ax = 0; ax < 3; ++ax) {
+            const double v = a.v[(size_t)ax * a.P + i];
+            const double t = v * v;
+            const bool oob = fixed_out_of_range(t);
+            bad = bad || oob;
+            __int128 k = 0;
+            fixed_add(k, oob ? 0.0 : t);
+            from128(q[2 + ax], k);
+        }
+    }
+    const bool any_bad = __syncthreads_or(bad);
+    block_sum192(q, red);
+    if (threadIdx.x == 0) {
+        int64_t *b = a.blk + (size_t)blockIdx.x * kExactWords;
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+#pragma unroll
+            for (int w = 0; w < 3; ++w) b[3 * k + w] = (int64_t)q[k][w];
+        b[15] = (any_bad ? kFlagRange : 0) | ((ENERGY && !KE_ONLY) ? 0 : kFlagNoEnergy) | ((KICK || KE_ONLY) ? 0 : kFlagNoKinetic);
+    }
+}
+
+// One block: the exact sum of the per-block partials = ONE record of this rank for this step.
+__global__ __launch_bounds__(kBlock) void fixed_fold_kernel(FixedFoldArgs a)
+{
+    __shared__ uint64_t red[kWavesPerBlock][5][3];
+    uint64_t q[5][3] = {};
+    unsigned long long flags = 0ull;
+    for (int b = threadIdx.x; b < a.n_blk; b += kBlock) {
+        const int64_t *p = a.blk + (size_t)b * kExactWords;
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const uint64_t o[3] = {(uint64_t)p[3 * k], (uint64_t)p[3 * k + 1], (uint64_t)p[3 * k + 2]};
+            add192(q[k], o);
+        }
+        flags |= (unsigned long long)p[15];
+    }
+    const unsigned long long all_flags = (__syncthreads_or((flags & kFlagRange) != 0) ? kFlagRange : 0) |
+                                         (__syncthreads_or((flags & kFlagNoEnergy) != 0) ? kFlagNoEnergy : 0) |
+                                         (__syncthreads_or((flags & kFlagNoKinetic) != 0) ? kFlagNoKinetic : 0);
+    block_sum192(q, red);
+    if (threadIdx.x == 0) {
+        int64_t *rec = a.rec;
+        unsigned pos = 0;
+        if (a.ring_pos) {
+            pos = *a.ring_pos;
+            rec += (size_t)(pos % a.ring_cap) * kExactWords;
+        }
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+#pragma unroll
+            for (int w = 0; w < 3; ++w) rec[3 * k + w] = (int64_t)q[k][w];
+        rec[15] = (int64_t)all_flags;
+        if (a.ring_pos) *a.ring_pos = pos + 1;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // host-callable launchers
 // ---------------------------------------------------------------------------
+hipError_t launch_pair_fixed(const FixedArgs &a, dim3 grid, hipStream_t s)
+{
+    if (a.energy)
+        hipLaunchKernelGGL(pair_fixed_kernel<true>, grid, dim3(kBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL(pair_fixed_kernel<false>, grid, dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_tail(const FixedTailArgs &a, bool kick, bool energy, bool ke_only, hipStream_t s)
+{
+    const dim3 grid(a.P / kBlock);
+    if (ke_only) hipLaunchKernelGGL((fixed_tail_kernel<false, false, true>), grid, dim3(kBlock), 0, s, a);
+    else if (kick && energy) hipLaunchKernelGGL((fixed_tail_kernel<true, true, false>), grid, dim3(kBlock), 0, s, a);
+    else if (kick) hipLaunchKernelGGL((fixed_tail_kernel<true, false, false>), grid, dim3(kBlock), 0, s, a);
+    else if (energy) hipLaunchKernelGGL((fixed_tail_kernel<false, true, false>), grid, dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL((fixed_tail_kernel<false, false, false>), grid, dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_fixed_fold(const FixedFoldArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(fixed_fold_kernel, dim3(1), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_pair_rows_generic(const PairArgs &a, dim3 grid, hipStream_t s)
 {
     hipLaunchKernelGGL(pair_rows_generic_kernel, grid, dim3(kBlock), 0, s, a);

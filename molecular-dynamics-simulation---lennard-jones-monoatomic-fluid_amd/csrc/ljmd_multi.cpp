@@ -454,13 +454,14 @@ int collect(ljmd_t *h, int count, double *epot, double *ekin, double *d_epot, do
         LJMD_HIP(h, hipSetDevice(m->dev[g]));
         LJMD_CHILD(h, m->eng[g], fetch_ring(m->eng[g], (unsigned)count));
     }
-    m->recs.resize((size_t)m->G * kPartialStride);
+    const int stride = m->eng[0]->rec_stride;     // reproducible mode: exact records, combined as integers
+    m->recs.resize((size_t)m->G * stride);
     for (int s = 0; s < count; ++s) {
         for (int g = 0; g < m->G; ++g)
-            std::memcpy(&m->recs[(size_t)g * kPartialStride], m->eng[g]->h_ring + (size_t)s * kPartialStride,
-                        kPartialStride * sizeof(double));
-        combine_one(h, m->recs.data(), m->G, epot ? epot + s : nullptr, ekin ? ekin + s : nullptr,
-                    d_epot ? d_epot + s : nullptr, dd_epot ? dd_epot + s : nullptr);
+            std::memcpy(&m->recs[(size_t)g * stride], m->eng[g]->h_ring + (size_t)s * stride, stride * sizeof(double));
+        const int rc_ = combine_records(h, h, m->recs.data(), m->G, epot ? epot + s : nullptr, ekin ? ekin + s : nullptr,
+                                        d_epot ? d_epot + s : nullptr, dd_epot ? dd_epot + s : nullptr);
+        if (rc_ != LJMD_OK) return rc_;
     }
     return LJMD_OK;
 }
@@ -525,7 +526,7 @@ int create(ljmd_t **out, int32_t n, double box_length, double dt, double rc, int
     }
     // the parent carries the parameters the scalar combination needs (tail constants) and what callers query
     const ljmd_t *e0 = m->eng[0];
-    h->n = n; h->G = n_gpus; h->S = e0->S; h->P = e0->P; h->mode = precision_mode;
+    h->n = n; h->G = n_gpus; h->S = e0->S; h->P = e0->P; h->mode = precision_mode; h->rec_stride = e0->rec_stride;
     m->owner.resize(n);
     for (int k = 0; k < n; ++k) m->owner[k] = k;
     // LJMD_MULTI_MIGRATE_EVERY: steps between two ownership migrations (0 = never).  Default 2000: at n = 65536 and 8
@@ -889,6 +890,15 @@ int snapshot_end(ljmd_t *h, double *const p[12])
 
 int kinetic_energy(ljmd_t *h, double *ekin)
 {
+    if (reproducible(h)) {                 // the ranks' exact records, combined as integers
+        std::vector<int64_t> recs(h->multi->eng.size() * kExactWords);
+        for (size_t g = 0; g < h->multi->eng.size(); ++g) {
+            ljmd_t *e = h->multi->eng[g];
+            LJMD_HIP(h, hipSetDevice(e->device));
+            LJMD_CHILD(h, e, kinetic_exact(e, recs.data() + g * kExactWords));
+        }
+        return combine_exact(h, recs.data(), (int)h->multi->eng.size(), nullptr, ekin, nullptr, nullptr);
+    }
     double total = 0.0;
     for (ljmd_t *e : h->multi->eng) {      // rank order
         double part = 0.0;

@@ -118,6 +118,16 @@ class ShardedSimulation:
         else:
             self.engine.forces_partial()
 
+    @property
+    def _reproducible(self) -> bool:
+        return bool(getattr(self.engine, "reproducible", False))     # (engines without the mode: the plain records)
+
+    def _read_partials(self, nsteps: int) -> np.ndarray:
+        """this rank's step records: doubles, or the reproducible mode's exact int64 words"""
+        if self._reproducible:
+            return self.engine.read_partials_exact(nsteps)
+        return self.engine.read_partials(nsteps)
+
     def _gather_partials(self, mine: np.ndarray) -> np.ndarray:
         """mine: [k, PARTIAL_STRIDE] -> [world, k, PARTIAL_STRIDE] (host, tiny)."""
         if self.world == 1:
@@ -133,7 +143,8 @@ class ShardedSimulation:
         k = parts.shape[1]
         cols = [np.empty(k) for _ in range(4)]
         for s in range(k):
-            vals = self.engine.combine_scalars(np.ascontiguousarray(parts[:, s, :]))
+            combine = self.engine.combine_scalars_exact if self._reproducible else self.engine.combine_scalars
+            vals = combine(np.ascontiguousarray(parts[:, s, :]))
             for c, val in zip(cols, vals):
                 c[s] = val
         return tuple(cols)
@@ -177,7 +188,7 @@ class ShardedSimulation:
         if self.migrate_every > 0:
             self.migrate()             # the first deal is by position too
         self._finish(False)
-        parts = self._gather_partials(self.engine.read_partials(1))
+        parts = self._gather_partials(self._read_partials(1))
         e, _k, d, dd = self._combine(parts)
         return e[0], d[0], dd[0]
 
@@ -198,7 +209,7 @@ class ShardedSimulation:
 
     def collect(self, nsteps: int):
         """-> (epot, ekin, d_epot, dd_epot) arrays of the last nsteps enqueued steps."""
-        return self._combine(self._gather_partials(self.engine.read_partials(nsteps)))
+        return self._combine(self._gather_partials(self._read_partials(nsteps)))
 
     def run(self, nsteps: int):
         self.enqueue_steps(nsteps)

@@ -24,6 +24,7 @@ module ljmd_c_api
 
   integer(c_int), parameter, public :: LJMD_OK = 0
   integer(c_int32_t), parameter, public :: LJMD_PRECISION_FP64 = 0
+  integer(c_int32_t), parameter, public :: LJMD_PRECISION_FP64_REPRODUCIBLE = 2   ! exact fixed-point sums (ljmd.h)
   integer(c_int32_t), parameter, public :: LJMD_MAX_PENDING_STEPS = 4096
 
   interface

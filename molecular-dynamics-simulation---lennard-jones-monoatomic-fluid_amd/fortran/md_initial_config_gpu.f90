@@ -5,7 +5,7 @@
 !   target total energy: module md_init_host (host arithmetic exactly as written in the reference)
 !   the two force evaluations (:91, :104) and the warm-up loop (:113-116): the library, resident
 !   outputs/rv_init.dat: record 1 = rx ry rz, record 2 = vx vy vz             :285-286
-! Environment: LJMD_DEVICE (default 0).
+! Environment: LJMD_DEVICE (default 0), LJMD_REPRODUCIBLE (default 0; 1: LJMD_PRECISION_FP64_REPRODUCIBLE).
 !==============================================================================
 program md_initial_config_gpu
   use, intrinsic :: iso_c_binding
@@ -23,7 +23,7 @@ program md_initial_config_gpu
   real(kind=dp_kind) :: rc_over_L, target_total_energy
   real(kind=dp_kind) :: epot, d_epot, dd_epot
   type(c_ptr) :: engine
-  integer(c_int32_t) :: device
+  integer(c_int32_t) :: device, precision_mode
   character(len=32) :: env
   integer :: ios
 
@@ -33,6 +33,11 @@ program md_initial_config_gpu
   device = 0
   call get_environment_variable('LJMD_DEVICE', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *, iostat=ios) device
+  precision_mode = LJMD_PRECISION_FP64
+  call get_environment_variable('LJMD_REPRODUCIBLE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) then
+    if (trim(env) /= '0') precision_mode = LJMD_PRECISION_FP64_REPRODUCIBLE
+  end if
 
   call build_fcc_lattice(params, state)
   seed = -12345_int_kind
@@ -40,7 +45,7 @@ program md_initial_config_gpu
   call remove_center_of_mass_velocity(params, state)
 
   ! ---- energies at t = 0, rescale to the target total energy ------------------------------------
-  call ljmd_check(ljmd_create(engine, params%n, params%box_length, params%dt, params%rc, LJMD_PRECISION_FP64, &
+  call ljmd_check(ljmd_create(engine, params%n, params%box_length, params%dt, params%rc, precision_mode, &
                               device, 0_c_int32_t, 1_c_int32_t), c_null_ptr, 'ljmd_create')
   call ljmd_check(ljmd_set_tail_corrections(engine, merge(1_c_int32_t, 0_c_int32_t, use_tail_corrections)), engine, &
                   'ljmd_set_tail_corrections')

@@ -15,7 +15,8 @@
 ! Environment: LJMD_DEVICE (default 0), LJMD_ASYNC_IO (default 1), LJMD_GPUS (default 1; > 1: this one process
 ! drives that many devices -- ljmd_create_multi, particles sharded by index range, RCCL all-gather of positions and
 ! reduce-scatter of forces per step inside the library -- e.g. BASELINE config 4 with LJMD_GPUS=8; LJMD_DEVICES, a
-! comma-separated device list of that length, overrides 0..LJMD_GPUS-1).
+! comma-separated device list of that length, overrides 0..LJMD_GPUS-1), LJMD_REPRODUCIBLE (default 0; 1: the
+! LJMD_PRECISION_FP64_REPRODUCIBLE mode -- every output file bitwise independent of LJMD_GPUS).
 !==============================================================================
 program md_simulation_gpu
   use, intrinsic :: iso_c_binding
@@ -38,6 +39,7 @@ program md_simulation_gpu
   integer(kind=int_kind) :: step, count, k, num_samples
   logical :: sample_now, async_io, sampled_steps
   integer :: iu_rva, iu_out, ios, device, n_gpus
+  integer(c_int32_t) :: precision_mode
   integer(c_int32_t), allocatable, target :: device_list(:)
   character(len=256) :: env_list
   integer(kind=8) :: c0, c1, crate
@@ -61,6 +63,11 @@ program md_simulation_gpu
   call get_environment_variable('LJMD_SAMPLED_STEPS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) sampled_steps = trim(env) /= '0'
 
+  precision_mode = LJMD_PRECISION_FP64
+  call get_environment_variable('LJMD_REPRODUCIBLE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) then
+    if (trim(env) /= '0') precision_mode = LJMD_PRECISION_FP64_REPRODUCIBLE
+  end if
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
@@ -70,11 +77,11 @@ program md_simulation_gpu
     call get_environment_variable('LJMD_DEVICES', env_list, status=ios)
     if (ios == 0 .and. len_trim(env_list) > 0) read(env_list, *) device_list
     call ljmd_check(ljmd_create_multi(engine, params%n, params%box_length, params%dt, params%rc, &
-                                      LJMD_PRECISION_FP64, int(n_gpus, c_int32_t), c_loc(device_list)), &
+                                      precision_mode, int(n_gpus, c_int32_t), c_loc(device_list)), &
                     c_null_ptr, 'ljmd_create_multi')
   else
     call ljmd_check(ljmd_create(engine, params%n, params%box_length, params%dt, params%rc, &
-                                LJMD_PRECISION_FP64, int(device, c_int32_t), 0_c_int32_t, 1_c_int32_t), &
+                                precision_mode, int(device, c_int32_t), 0_c_int32_t, 1_c_int32_t), &
                     c_null_ptr, 'ljmd_create')
   end if
   call ljmd_check(ljmd_set_tail_corrections(engine, merge(1_c_int32_t, 0_c_int32_t, use_tail_corrections)), engine, &

@@ -102,6 +102,7 @@ class Engine:
         self._lib = _lib.load()
         self.params = params
         self.rank, self.n_ranks = rank, n_ranks
+        self.precision_mode = precision_mode
         h = C.c_void_p()
         if devices is not None:
             devs = (C.c_int32 * len(devices))(*devices)
@@ -315,6 +316,24 @@ class Engine:
         p = np.ascontiguousarray(partials_by_rank, dtype=np.float64)
         outs = [C.c_double() for _ in range(4)]
         self._ck(self._lib.ljmd_combine_scalars(self._h, _ptr(p), p.shape[0], *[C.byref(o) for o in outs]))
+        return tuple(o.value for o in outs)
+
+    @property
+    def reproducible(self) -> bool:
+        return self.precision_mode == _lib.PRECISION_FP64_REPRODUCIBLE
+
+    def read_partials_exact(self, nsteps: int) -> np.ndarray:
+        """Reproducible mode: [nsteps, EXACT_PARTIAL_WORDS] int64 records (ljmd.h: LJMD_EXACT_PARTIAL_WORDS)."""
+        out = np.empty((nsteps, _lib.EXACT_PARTIAL_WORDS), dtype=np.int64)
+        self._ck(self._lib.ljmd_read_partials_exact(self._h, nsteps, out.ctypes.data_as(_lib.c_int64_p)))
+        return out
+
+    def combine_scalars_exact(self, words_by_rank: np.ndarray):
+        """words_by_rank: [n_ranks, EXACT_PARTIAL_WORDS] int64 of ONE step -> (epot, ekin, d_epot, dd_epot)"""
+        p = np.ascontiguousarray(words_by_rank, dtype=np.int64)
+        outs = [C.c_double() for _ in range(4)]
+        self._ck(self._lib.ljmd_combine_scalars_exact(self._h, p.ctypes.data_as(_lib.c_int64_p), p.shape[0],
+                                                      *[C.byref(o) for o in outs]))
         return tuple(o.value for o in outs)
 
     def set_tail_corrections(self, on: bool) -> None:
