@@ -402,6 +402,76 @@ int ljmd_profile_read_rank(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, do
 int ljmd_profile_read_stats(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, double *ms_min /* [6] */,
                             double *ms_median /* [6] */, int32_t *launches);
 
+/* ---- batch engine: many independent small systems on one device ------------------------------------------------
+ *
+ * One ljmd_batch_t holds B replicas of the same (n, L, dt, rc) on one device -- the ensemble runs of the reference's
+ * run-many framework (scripts/run_many_md_simuations/run_many_md.f90) -- and steps all of them with one kernel,
+ * one workgroup per replica, many steps per launch.  Each replica is exactly the physics of an ljmd_t.
+ *
+ * Layout: per-particle arrays are fp64 with B*n elements, replica-major (element (b, i) at b*n + i); per-replica
+ * scalars have B elements; the scalars of ljmd_batch_steps are [nsteps / sample_every][B], sample-major.
+ *
+ * Arithmetic, per replica, is the single engine's fast path (ljmd_kernels.hip):
+ *   drift + wrap + half-kick + unwrapped update: drift_kick_kernel's expressions in the same order, no contraction,
+ *     so with the same a(t) the positions after one step are bit-exact;
+ *   pair term: pair_fast in full-matrix gather form -- every ordered pair (i, j != i), minimum image
+ *     fma(-L, rint(d/L), d), r^2 = fma(dz, dz, fma(dy, dy, dx*dx)), strict r^2 < rc^2, 1/r^2 by v_rcp_f64 + one
+ *     Halley step -- the energy sums halved afterwards;
+ *   kick: a = 24 f, v += a dt/2, three separate sums of v^2; scalars combined on the host as for an ljmd_t
+ *     (tail constants included while ljmd_batch_set_tail_corrections is on, the default).
+ * Tolerances against the reference are those of the single engine.
+ *
+ * Determinism: every floating-point sum of a replica runs in an order fixed by n alone, with no floating-point
+ * atomics, so a replica's results are bitwise equal run to run and independent of B, of its slot in the batch and
+ * of what the other replicas hold.  The energy sums are evaluated only on sampled steps; r, ru, v, a are bitwise the
+ * same for every sample_every, and with no outputs at all.
+ *
+ * Limits: n <= LJMD_BATCH_MAX_N -- one replica's positions live in one CU's LDS for a whole launch, 24 n bytes
+ * <= 96 KiB; LJMD_PRECISION_FP64 only; rc <= (1 - 1e-9) L/2 and, at ljmd_batch_set_state, every replica's
+ * coordinates finite and spanning < 2.4 L per axis (the fast path's preconditions (b) and (a)): there is no
+ * generic-kernel fallback in this mode, so such input fails with LJMD_ERR_INVALID_ARG.  All guards run before the
+ * device probe; without a device ljmd_batch_create returns LJMD_ERR_NO_DEVICE.
+ *
+ * Sequence: ljmd_batch_steps before ljmd_batch_set_state, or before valid accelerations (ljmd_batch_compute_forces
+ * or ljmd_batch_set_accel), returns LJMD_ERR_STATE.  A launch that fails poisons the handle (LJMD_ERR_STATE) until
+ * ljmd_batch_set_state.  A handle is not thread-safe; one handle is one device.
+ */
+#define LJMD_BATCH_MAX_N 4096
+typedef struct ljmd_batch ljmd_batch_t;
+
+int ljmd_batch_create(ljmd_batch_t **out, int32_t n_replicas, int32_t n, double box_length, double dt, double rc,
+                      int32_t precision_mode, int32_t device);
+void ljmd_batch_destroy(ljmd_batch_t *h);
+/* Text of the most recent error on this handle (h == NULL: the thread's last failed ljmd_batch_create). */
+const char *ljmd_batch_last_error(const ljmd_batch_t *h);
+/* As ljmd_set_state for every replica: a = 0, ru = r.  All six arrays required. */
+int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, const double *rz,
+                         const double *vx, const double *vy, const double *vz);
+/* NULL = keep that component. */
+int ljmd_batch_set_accel(ljmd_batch_t *h, const double *ax, const double *ay, const double *az);
+int ljmd_batch_set_unwrapped(ljmd_batch_t *h, const double *ux, const double *uy, const double *uz);
+/* Any NULL = skipped. */
+int ljmd_batch_get_state(ljmd_batch_t *h, double *rx, double *ry, double *rz,
+                         double *ux, double *uy, double *uz,
+                         double *vx, double *vy, double *vz,
+                         double *ax, double *ay, double *az);
+/* Forces of every replica (overwrites a); epot, d_epot, dd_epot: [B] each or NULL. */
+int ljmd_batch_compute_forces(ljmd_batch_t *h, double *epot, double *d_epot, double *dd_epot);
+/* ekin[B]: 0.5 sum (vx^2 + vy^2 + vz^2), the fused sum of ljmd_kinetic_energy. */
+int ljmd_batch_kinetic_energy(ljmd_batch_t *h, double *ekin);
+/*
+ * nsteps x { verlet_step ; unwrapped update } on every replica, no host synchronisation inside; returns once the
+ * results are on the host.  The scalars of steps sample_every, 2 sample_every, ... go to [nsteps / sample_every][B]
+ * arrays (each NULL or such an array); nsteps % sample_every == 0 and nsteps / sample_every <=
+ * LJMD_MAX_PENDING_STEPS.  With all four arrays NULL no step is sampled and sample_every is not used.
+ */
+int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every,
+                     double *epot, double *ekin, double *d_epot, double *dd_epot);
+/* As ljmd_set_tail_corrections. */
+int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on);
+/* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL. */
+int ljmd_batch_profile_read(const ljmd_batch_t *h, double *kernel_ms, int32_t *launches);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,7 +108,23 @@ PROTOTYPES = {
     "ljmd_profile_read_ex": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int32_p]),
     "ljmd_profile_read_rank": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_int32_p]),
     "ljmd_profile_read_stats": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, c_double_p, c_double_p, c_int32_p]),
+    # batch engine: B independent replicas on one device (include/ljmd.h, ljmd_batch_*)
+    "ljmd_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                    C.c_int32, C.c_int32]),
+    "ljmd_batch_destroy": (None, [C.c_void_p]),
+    "ljmd_batch_last_error": (C.c_char_p, [C.c_void_p]),
+    "ljmd_batch_set_state": (C.c_int, [C.c_void_p] + [c_double_p] * 6),
+    "ljmd_batch_set_accel": (C.c_int, [C.c_void_p] + [c_double_p] * 3),
+    "ljmd_batch_set_unwrapped": (C.c_int, [C.c_void_p] + [c_double_p] * 3),
+    "ljmd_batch_get_state": (C.c_int, [C.c_void_p] + [c_double_p] * 12),
+    "ljmd_batch_compute_forces": (C.c_int, [C.c_void_p] + [c_double_p] * 3),
+    "ljmd_batch_kinetic_energy": (C.c_int, [C.c_void_p, c_double_p]),
+    "ljmd_batch_steps": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [c_double_p] * 4),
+    "ljmd_batch_set_tail_corrections": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ljmd_batch_profile_read": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
 }
+
+BATCH_MAX_N = 4096
 
 _lib = None
 
@@ -140,3 +156,13 @@ def last_error(handle=None) -> str:
 def check(status: int, handle=None) -> None:
     if status != LJMD_OK:
         raise LjmdError(status, last_error(handle) or last_error(None))
+
+
+def batch_last_error(handle=None) -> str:
+    msg = load().ljmd_batch_last_error(handle)
+    return msg.decode() if msg else ""
+
+
+def check_batch(status: int, handle=None) -> None:
+    if status != LJMD_OK:
+        raise LjmdError(status, batch_last_error(handle) or batch_last_error(None))

@@ -1,0 +1,272 @@
+// ljmd_batch.hip -- gfx950 kernel of the batch engine (include/ljmd.h: ljmd_batch_*): many independent small systems
+// of the same (n, L, dt, rc), one workgroup per replica, many MD steps per launch.
+//
+// Per replica the arithmetic is the single engine's fast path:
+//   drift + wrap + half-kick + unwrapped update  = drift_kick_kernel<0> (ljmd_kernels.hip), same expression order;
+//   pair term                                    = pair_fast<true> (ljmd_kernels.hip), full-matrix gather form: every
+//                                                  ordered pair (i, j != i), the energy sums scaled by 0.5 afterwards
+//                                                  as the gather kernels' FinalizeArgs::pair_scale does;
+//   second half-kick                             = kick_kernel<true>: a = 24 f, v += a dt/2, three separate sums of v^2.
+// Compiled with -ffp-contract=off (csrc/Makefile): FMAs only where the source says fma().
+//
+// Determinism: every floating-point sum of a replica runs in an order fixed by n alone -- j = 0 .. n-1 per particle,
+// the own particles of a thread in order, the lanes of a wave by the shuffle tree, the waves in order.  Nothing
+// depends on B, on the replica's slot or on the other replicas, and there are no floating-point atomics.
+//
+// Shape: the replica's positions stay in LDS (SoA, 3 NMAX doubles) for the whole launch; j is uniform across the
+// workgroup, so every position read is a broadcast.  A thread owns particles tid, tid + T, ... (K of them); their
+// ru, v, a stay in HBM (read and written by the owning thread only), their pair accumulators in registers.
+#include "ljmd_batch.h"
+
+namespace ljmdb {
+namespace {
+
+// ---- restated from ljmd_kernels.hip (which stays untouched): mic_fast, rcp_newton, pair_fast, wave_sum ------------
+// Fast-path preconditions, checked on the host (ljmd_batch.cpp): (a) every coordinate span < 2.4 L,
+// (b) rc <= (1 - 1e-9) L/2.  See the comment above mic_fast in ljmd_kernels.hip.
+__device__ __forceinline__ double mic_fast(double d, double L, double invL)
+{
+    return fma(-L, __builtin_rint(d * invL), d);
+}
+
+__device__ __forceinline__ double rcp_newton(double x)
+{
+    // v_rcp_f64 + one Halley step, within 1 ulp of the IEEE quotient (ljmd_kernels.hip: rcp_newton)
+    const double y0 = __builtin_amdgcn_rcp(x);
+    const double e = fma(-x, y0, 1.0);
+    const double t = fma(e, e, e);
+    return fma(y0, t, y0);
+}
+
+// = pair_fast<true>; ENERGY = false leaves out the two energy sums (forces-only steps; the forces are the same bits)
+template <bool ENERGY>
+__device__ __forceinline__ void pair_batch(double xi, double yi, double zi, double xj, double yj, double zj,
+                                           double L, double invL, double rc2, bool is_self,
+                                           double &ax, double &ay, double &az, double &s12, double &s6)
+{
+    const double dx = mic_fast(xi - xj, L, invL);
+    const double dy = mic_fast(yi - yj, L, invL);
+    const double dz = mic_fast(zi - zj, L, invL);
+    const double r2 = fma(dz, dz, fma(dy, dy, dx * dx));
+    const bool in = r2 < rc2 && !is_self;                // strict <; NaN (an unused own slot) never passes
+    if (in) {
+        const double u = rcp_newton(r2);
+        const double u3 = u * u * u;
+        const double u6 = u3 * u3;
+        if constexpr (ENERGY) {
+            s12 += u6;
+            s6 += u3;
+        }
+        const double g = fma(2.0, u6, -u3) * u;          // = -dU_r * inv_r2
+        ax = fma(g, dx, ax);
+        ay = fma(g, dy, ay);
+        az = fma(g, dz, az);
+    }
+}
+
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;  // valid in lane 0
+}
+
+// fixed-order workgroup sum for blockDim.x / 64 <= kBatchMaxWaves waves; the result is valid in thread 0
+template <int NVAL>
+__device__ __forceinline__ void block_sum_waves(double (&v)[NVAL], double *red /* [NVAL * kBatchMaxWaves] */)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NVAL; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane == 0) red[k * kBatchMaxWaves + wave] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < NVAL; ++k) {
+            double s = red[k * kBatchMaxWaves];
+            for (int w = 1; w < W; ++w) s += red[k * kBatchMaxWaves + w];
+            v[k] = s;
+        }
+    }
+}
+
+// gather over all n positions of the replica for the K own particles of this thread
+template <int NMAX, int K, bool ENERGY>
+__device__ __forceinline__ void gather(const double *pos, int n, const double (&xi)[K], const double (&yi)[K],
+                                       const double (&zi)[K], const int (&ii)[K], double L, double invL, double rc2,
+                                       double (&f)[3][K], double (&e)[2][K])
+{
+#pragma unroll
+    for (int k = 0; k < K; ++k) f[0][k] = f[1][k] = f[2][k] = e[0][k] = e[1][k] = 0.0;
+#pragma unroll K == 1 ? 2 : 1
+    for (int j = 0; j < n; ++j) {
+        const double xj = pos[j], yj = pos[NMAX + j], zj = pos[2 * NMAX + j];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+            pair_batch<ENERGY>(xi[k], yi[k], zi[k], xj, yj, zj, L, invL, rc2, j == ii[k],
+                               f[0][k], f[1][k], f[2][k], e[0][k], e[1][k]);
+    }
+}
+
+template <int NMAX, int K>
+__global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
+{
+    __shared__ double pos[3 * NMAX];
+    __shared__ double red[kBatchRecWords * kBatchMaxWaves];
+    const int n = a.n, T = blockDim.x, tid = threadIdx.x;
+    const size_t b = (size_t)a.b0 + blockIdx.x;
+    const size_t plane = a.B * (size_t)n, base = b * (size_t)n;
+    double *const R = a.state;
+    double *const RU = a.state + 3 * plane;
+    double *const V = a.state + 6 * plane;
+    double *const A = a.state + 9 * plane;
+
+    if (a.mode == kModeKinetic) {
+        double s[1] = {0.0};
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int i = tid + k * T;
+            if (i < n) {
+                const double vx = V[base + i], vy = V[plane + base + i], vz = V[2 * plane + base + i];
+                s[0] += vx * vx + vy * vy + vz * vz;
+            }
+        }
+        block_sum_waves<1>(s, red);
+        if (tid == 0) {
+            double *w = a.rec + b * kBatchRecWords;
+            w[0] = 0.0;
+            w[1] = 0.0;
+            w[2] = s[0];
+            w[3] = 0.0;
+            w[4] = 0.0;
+        }
+        return;
+    }
+
+    for (int i = tid; i < n; i += T) {
+        pos[i] = R[base + i];
+        pos[NMAX + i] = R[plane + base + i];
+        pos[2 * NMAX + i] = R[2 * plane + base + i];
+    }
+    __syncthreads();
+
+    const bool steps = a.mode == kModeSteps;
+    const int nsteps = steps ? a.nsteps : 1;
+    for (int s = 0; s < nsteps; ++s) {
+        const int gstep = a.step0 + s + 1;
+        const bool sampled = !steps || (a.sample_every > 0 && gstep % a.sample_every == 0);
+        if (steps) {
+            // drift_kick_kernel<0>: r(t+dt), wrap, ru update, first half-kick
+#pragma unroll 1
+            for (int k = 0; k < K; ++k) {
+                const int i = tid + k * T;
+                if (i < n) {
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        const size_t o = ax * plane + base + i;
+                        const double v0 = V[o], acc = A[o];
+                        const double r0 = pos[ax * NMAX + i];
+                        double r1 = (r0 + v0 * a.dt) + acc * a.dt_sq_half;
+                        r1 = r1 - a.L * __builtin_floor(r1 * a.invL);
+                        double d = r1 - r0;
+                        d = d - a.L * __builtin_round(d * a.invL);
+                        pos[ax * NMAX + i] = r1;
+                        RU[o] = RU[o] + d;
+                        V[o] = v0 + acc * a.dt_half;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        // at most two own particles per pass over j (KG): four interleaved pair chains need more than the 128 VGPRs a
+        // 1024-thread workgroup allows; a second pass costs only the LDS broadcasts.  The kick of a pass's particles
+        // follows its pass, so nothing of it stays live.  Sums over the own particles run in order k = 0 .. K-1.
+        constexpr int KG = K < 2 ? K : 2;
+        double e12 = 0.0, e6 = 0.0, kk[3] = {0.0, 0.0, 0.0};
+#pragma unroll 1
+        for (int g = 0; g < K; g += KG) {
+            double xs[KG], ys[KG], zs[KG], fs[3][KG], es[2][KG];
+            int is[KG];
+#pragma unroll
+            for (int k = 0; k < KG; ++k) {
+                const int i = tid + (g + k) * T;
+                is[k] = i;
+                xs[k] = i < n ? pos[i] : __builtin_nan("");
+                ys[k] = i < n ? pos[NMAX + i] : __builtin_nan("");
+                zs[k] = i < n ? pos[2 * NMAX + i] : __builtin_nan("");
+            }
+            if (sampled)
+                gather<NMAX, KG, true>(pos, n, xs, ys, zs, is, a.L, a.invL, a.rc2, fs, es);
+            else
+                gather<NMAX, KG, false>(pos, n, xs, ys, zs, is, a.L, a.invL, a.rc2, fs, es);
+            // kick_kernel<KICK = steps>: a = 24 f, second half-kick, sums of v^2 per axis
+#pragma unroll
+            for (int k = 0; k < KG; ++k) {
+                if (is[k] < n) {
+#pragma unroll
+                    for (int ax = 0; ax < 3; ++ax) {
+                        const size_t o = ax * plane + base + is[k];
+                        const double acc = 24.0 * fs[ax][k];
+                        A[o] = acc;
+                        if (steps) {
+                            const double v1 = V[o] + acc * a.dt_half;
+                            V[o] = v1;
+                            if (sampled) kk[ax] += v1 * v1;
+                        }
+                    }
+                }
+                e12 += es[0][k];
+                e6 += es[1][k];
+            }
+        }
+        if (sampled) {
+            double v[kBatchRecWords] = {e12, e6, kk[0], kk[1], kk[2]};
+            block_sum_waves<kBatchRecWords>(v, red);
+            if (tid == 0) {
+                const size_t rec = steps ? (size_t)(gstep / a.sample_every - 1) : 0;
+                double *w = a.rec + (rec * a.B + b) * kBatchRecWords;
+                w[0] = v[0] * 0.5;          // ordered -> unordered pairs; exact
+                w[1] = v[1] * 0.5;
+                w[2] = v[2];
+                w[3] = v[3];
+                w[4] = v[4];
+            }
+        }
+        __syncthreads();   // every read of pos[] by this step's gather precedes the next drift's writes
+    }
+    if (steps) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int i = tid + k * T;
+            if (i < n) {
+                R[base + i] = pos[i];
+                R[plane + base + i] = pos[NMAX + i];
+                R[2 * plane + base + i] = pos[2 * NMAX + i];
+            }
+        }
+    }
+}
+
+template <int NMAX, int K>
+hipError_t launch_class(const BatchArgs &a, int n_blocks, hipStream_t s)
+{
+    static_assert(64 * ((NMAX + 64 * K - 1) / (64 * K)) <= kBatchMaxThreads, "too many threads for the class");
+    hipLaunchKernelGGL((batch_md_kernel<NMAX, K>), dim3(n_blocks), dim3(batch_threads(a.n)), 0, s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_batch(const BatchArgs &a, int n_blocks, hipStream_t s)
+{
+    if (a.n <= 0 || a.n > 4096 || n_blocks <= 0) return hipErrorInvalidValue;
+    if (a.n <= 128) return launch_class<128, 1>(a, n_blocks, s);
+    if (a.n <= 512) return launch_class<512, 1>(a, n_blocks, s);
+    if (a.n <= 1024) return launch_class<1024, 1>(a, n_blocks, s);
+    if (a.n <= 2048) return launch_class<2048, 2>(a, n_blocks, s);
+    return launch_class<4096, 4>(a, n_blocks, s);
+}
+
+}  // namespace ljmdb

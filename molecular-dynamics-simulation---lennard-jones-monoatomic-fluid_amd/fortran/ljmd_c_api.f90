@@ -21,11 +21,17 @@ module ljmd_c_api
   public :: ljmd_last_error, ljmd_device_count, ljmd_profile_enable, ljmd_profile_read
   public :: ljmd_enqueue_steps, ljmd_enqueue_steps_sampled, ljmd_collect_steps, ljmd_snapshot_begin, ljmd_snapshot_end
   public :: ljmd_check, ljmd_error_text
+  ! batch engine: many independent replicas of one (n, L, dt, rc) on one device (ljmd.h, ljmd_batch_*)
+  public :: ljmd_batch_create, ljmd_batch_destroy, ljmd_batch_last_error, ljmd_batch_set_state, ljmd_batch_set_accel
+  public :: ljmd_batch_set_unwrapped, ljmd_batch_get_state, ljmd_batch_compute_forces, ljmd_batch_kinetic_energy
+  public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_profile_read
+  public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
   integer(c_int32_t), parameter, public :: LJMD_PRECISION_FP64 = 0
   integer(c_int32_t), parameter, public :: LJMD_PRECISION_FP64_REPRODUCIBLE = 2   ! exact fixed-point sums (ljmd.h)
   integer(c_int32_t), parameter, public :: LJMD_MAX_PENDING_STEPS = 4096
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_MAX_N = 4096
 
   interface
     function ljmd_compute_lj_potential_energy(n, box_length, rc, rx, ry, rz, ax, ay, az, &
@@ -202,6 +208,89 @@ module ljmd_c_api
       integer(c_int32_t), intent(out) :: launches
       integer(c_int) :: status
     end function
+    ! ---- batch engine: arrays of B*n doubles, replica-major; per-replica scalars [B]; ljmd_batch_steps' scalars
+    ! [nsteps/sample_every][B] (Fortran: dimension(B, nsteps/sample_every)); c_null_ptr = not wanted
+    function ljmd_batch_create(handle, n_replicas, n, box_length, dt, rc, precision_mode, device) &
+        bind(C, name="ljmd_batch_create") result(status)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), intent(out) :: handle
+      integer(c_int32_t), value :: n_replicas, n, precision_mode, device
+      real(c_double), value :: box_length, dt, rc
+      integer(c_int) :: status
+    end function
+
+    subroutine ljmd_batch_destroy(handle) bind(C, name="ljmd_batch_destroy")
+      import :: c_ptr
+      type(c_ptr), value :: handle
+    end subroutine
+
+    function ljmd_batch_last_error(handle) bind(C, name="ljmd_batch_last_error") result(text)
+      import :: c_ptr
+      type(c_ptr), value :: handle
+      type(c_ptr) :: text
+    end function
+
+    function ljmd_batch_set_state(handle, rx, ry, rz, vx, vy, vz) bind(C, name="ljmd_batch_set_state") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, rx, ry, rz, vx, vy, vz
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_set_accel(handle, ax, ay, az) bind(C, name="ljmd_batch_set_accel") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, ax, ay, az
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_set_unwrapped(handle, ux, uy, uz) bind(C, name="ljmd_batch_set_unwrapped") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, ux, uy, uz
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_get_state(handle, rx, ry, rz, ux, uy, uz, vx, vy, vz, ax, ay, az) &
+        bind(C, name="ljmd_batch_get_state") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, rx, ry, rz, ux, uy, uz, vx, vy, vz, ax, ay, az
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_compute_forces(handle, epot, d_epot, dd_epot) bind(C, name="ljmd_batch_compute_forces") &
+        result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, epot, d_epot, dd_epot
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_kinetic_energy(handle, ekin) bind(C, name="ljmd_batch_kinetic_energy") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, ekin
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_steps(handle, nsteps, sample_every, epot, ekin, d_epot, dd_epot) &
+        bind(C, name="ljmd_batch_steps") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle, epot, ekin, d_epot, dd_epot
+      integer(c_int32_t), value :: nsteps, sample_every
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_set_tail_corrections(handle, on) bind(C, name="ljmd_batch_set_tail_corrections") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: on
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_profile_read(handle, kernel_ms, launches) bind(C, name="ljmd_batch_profile_read") &
+        result(status)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      real(c_double), intent(out) :: kernel_ms
+      integer(c_int32_t), intent(out) :: launches
+      integer(c_int) :: status
+    end function
   end interface
 
 contains
@@ -227,6 +316,43 @@ contains
       text(k:k) = chars(k)
     end do
   end function ljmd_error_text
+
+  ! Text of the last error of a batch handle (handle = c_null_ptr: the last failed ljmd_batch_create of this thread).
+  function ljmd_batch_error_text(handle) result(text)
+    type(c_ptr), intent(in) :: handle
+    character(len=:), allocatable :: text
+    text = c_text(ljmd_batch_last_error(handle))
+  end function ljmd_batch_error_text
+
+  function c_text(p) result(text)
+    type(c_ptr), intent(in) :: p
+    character(len=:), allocatable :: text
+    character(kind=c_char), pointer :: chars(:)
+    integer :: k, n
+    text = ''
+    if (.not. c_associated(p)) return
+    call c_f_pointer(p, chars, [512])
+    n = 0
+    do k = 1, 512
+      if (chars(k) == c_null_char) exit
+      n = k
+    end do
+    allocate(character(len=n) :: text)
+    do k = 1, n
+      text(k:k) = chars(k)
+    end do
+  end function c_text
+
+  ! ljmd_check for a batch handle: the same `stop 'ljmd: ...'` convention
+  subroutine ljmd_batch_check(status, handle, where)
+    integer(c_int), intent(in) :: status
+    type(c_ptr), intent(in) :: handle
+    character(len=*), intent(in) :: where
+    if (status /= LJMD_OK) then
+      write(*, '(a)') 'ljmd: ' // where // ': ' // ljmd_batch_error_text(handle)
+      stop 'ljmd: GPU hot path failed'
+    end if
+  end subroutine ljmd_batch_check
 
   ! The reference's error convention is `stop 'routine(): message'` (e.g.
   ! lj_potential_energy.f90:77-82): a non-zero status ends the program the same way.

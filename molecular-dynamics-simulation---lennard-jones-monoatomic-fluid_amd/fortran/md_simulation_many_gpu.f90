@@ -1,0 +1,174 @@
+!==============================================================================
+! md_simulation_many_gpu -- the reference's run-many workflow (scripts/run_many_md_simuations/run_many_md.f90) on
+! ONE batch handle of the MI355X engine (include/ljmd.h: ljmd_batch_*): all runs step together, one workgroup per run.
+!
+!   in : inputs/input_simulation_parameters.txt (as md_simulation_gpu)
+!        outputs/run_NNNN/rv_init.dat when it exists, else the shared outputs/rv_init.dat -- with the shared file every
+!        run is the same trajectory, as in the reference (run_many_md.f90:13-15 warns about it); callers who want
+!        independent runs write one rv_init.dat per run
+!   out: outputs/run_NNNN/ instantaneous_energies.dat, rva.dat, corr_*.dat, corrmean_*.dat, md_final_results.txt --
+!        the files md_simulation_gpu writes into outputs/one_run/, same formats (module md_stats / md_run_outputs)
+!        outputs/several_runs.txt -- the reference's two header lines, then one directory per run (run_many_md.f90:
+!        30,48-49,74)
+! Each run is the physics of md_simulation_gpu (the batch engine's contract, ljmd.h); the runs differ from it only by
+! the summation order of the forces.
+! Environment: LJMD_RUNS (default 10, the reference's n_runs_default, run_many_md.f90:26), LJMD_DEVICE (default 0).
+! Batches are fp64 only and take n <= LJMD_BATCH_MAX_N.
+!==============================================================================
+program md_simulation_many_gpu
+  use, intrinsic :: iso_c_binding
+  use define_precision, only: dp_kind, int_kind
+  use md_types,         only: sim_params
+  use read_input_files, only: read_simulation_parameters
+  use ljmd_c_api
+  use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
+  use md_stats,         only: run_statistics, stats_begin, stats_push
+  use md_run_outputs,   only: write_run_statistics
+  implicit none
+
+  character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
+  type(sim_params) :: params
+  integer(kind=int_kind) :: total_steps, output_interval, warmup_steps, n_snapshots_expected
+  real(kind=dp_kind) :: rc_over_L, target_total_energy
+  real(kind=dp_kind), allocatable, target :: rx(:), ry(:), rz(:), ux(:), uy(:), uz(:)
+  real(kind=dp_kind), allocatable, target :: vx(:), vy(:), vz(:), ax(:), ay(:), az(:)
+  real(kind=dp_kind), allocatable, target :: s_epot(:), s_ekin(:), s_depot(:), s_ddepot(:)
+  type(run_statistics), allocatable :: stats(:)
+  integer, allocatable :: iu_rva(:), iu_out(:)
+  character(len=64), allocatable :: run_dir(:)
+  real(kind=dp_kind) :: time, etot, temp_inst, press_inst
+  integer(kind=int_kind) :: step, k, num_samples, n, rest
+  integer :: n_runs, i, ios, device, iu
+  integer(c_int32_t) :: n_runs_c
+  integer(kind=8) :: c0, c1, crate, o
+  type(c_ptr) :: batch
+  character(len=32) :: env
+
+  call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
+                                  output_interval, warmup_steps, rc_over_L, target_total_energy)
+  n = params%n
+  n_runs = 10
+  call get_environment_variable('LJMD_RUNS', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_runs
+  if (n_runs < 1) stop 'md_simulation_many: LJMD_RUNS must be >= 1.'
+  device = 0
+  call get_environment_variable('LJMD_DEVICE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) device
+
+  allocate(rx(n * n_runs), ry(n * n_runs), rz(n * n_runs), ux(n * n_runs), uy(n * n_runs), uz(n * n_runs), &
+           vx(n * n_runs), vy(n * n_runs), vz(n * n_runs), ax(n * n_runs), ay(n * n_runs), az(n * n_runs))
+  allocate(s_epot(n_runs), s_ekin(n_runs), s_depot(n_runs), s_ddepot(n_runs))
+  allocate(stats(n_runs), iu_rva(n_runs), iu_out(n_runs), run_dir(n_runs))
+
+  ! run directories (before the GPU is touched) and initial configurations, replica-major: run i at [(i-1) n + 1, i n]
+  do i = 1, n_runs
+    write(run_dir(i), '(a,i4.4)') 'outputs/run_', i
+    call execute_command_line('mkdir -p ' // trim(run_dir(i)), exitstat=ios)
+    if (ios /= 0) stop 'md_simulation_many: cannot create a run directory under outputs/.'
+    call read_rv_init(i)
+  end do
+
+  call ljmd_batch_check(ljmd_batch_create(batch, int(n_runs, c_int32_t), n, params%box_length, params%dt, params%rc, &
+                                          LJMD_PRECISION_FP64, int(device, c_int32_t)), c_null_ptr, 'ljmd_batch_create')
+  n_runs_c = int(n_runs, c_int32_t)
+  call ljmd_batch_check(ljmd_batch_set_tail_corrections(batch, merge(1_c_int32_t, 0_c_int32_t, use_tail_corrections)), &
+                        batch, 'ljmd_batch_set_tail_corrections')
+  ! H2D; the library sets ru <- r (md_simulation_program.f90:229-231)
+  call ljmd_batch_check(ljmd_batch_set_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(vx), c_loc(vy), &
+                                             c_loc(vz)), batch, 'ljmd_batch_set_state')
+  ! t = 0 forces and energies of every run (:236-243)
+  call ljmd_batch_check(ljmd_batch_compute_forces(batch, c_loc(s_epot), c_loc(s_depot), c_loc(s_ddepot)), batch, &
+                        'ljmd_batch_compute_forces')
+  call ljmd_batch_check(ljmd_batch_kinetic_energy(batch, c_loc(s_ekin)), batch, 'ljmd_batch_kinetic_energy')
+  time = 0.d0
+
+  n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
+  if (n_snapshots_expected < 0) n_snapshots_expected = 0
+  do i = 1, n_runs
+    open(newunit=iu_rva(i), file=trim(run_dir(i)) // '/rva.dat', form='unformatted', status='replace', &
+         action='write', iostat=ios)
+    if (ios /= 0) stop 'md_simulation_many: cannot open rva.dat of a run.'
+    write(iu_rva(i)) params%n, params%box_length, params%dt, output_interval, n_snapshots_expected
+    open(newunit=iu_out(i), file=trim(run_dir(i)) // '/instantaneous_energies.dat', status='replace', &
+         action='write', iostat=ios)
+    if (ios /= 0) stop 'md_simulation_many: cannot open instantaneous_energies.dat of a run.'
+    write(iu_out(i), '(a)') '# time   epot   ekin   etot   T   P'
+    call stats_begin(stats(i), params%n, params%volume, n_snapshots_expected)
+  end do
+
+  num_samples = 0
+  step = 0
+  call system_clock(c0, crate)
+  ! segments of output_interval steps, each sampled at its last step -- the sampling instants of :361
+  do while (step + output_interval <= total_steps)
+    call ljmd_batch_check(ljmd_batch_steps(batch, int(output_interval, c_int32_t), int(output_interval, c_int32_t), &
+                                           c_loc(s_epot), c_loc(s_ekin), c_loc(s_depot), c_loc(s_ddepot)), batch, &
+                          'ljmd_batch_steps')
+    do k = 1, output_interval
+      time = time + params%dt                       ! accumulated as at :356
+    end do
+    step = step + output_interval
+    if (step <= warmup_steps) cycle
+    num_samples = num_samples + 1
+    call ljmd_batch_check(ljmd_batch_get_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(ux), c_loc(uy), &
+                                               c_loc(uz), c_loc(vx), c_loc(vy), c_loc(vz), c_loc(ax), c_loc(ay), &
+                                               c_loc(az)), batch, 'ljmd_batch_get_state')
+    do i = 1, n_runs
+      call stats_push(stats(i), s_epot(i), s_ekin(i), s_depot(i), s_ddepot(i), temp_inst, press_inst)
+      etot = s_epot(i) + s_ekin(i)
+      write(iu_out(i), '(1pe13.6,5(2x,1pe13.6))') time, s_epot(i), s_ekin(i), etot, temp_inst, press_inst
+      o = int(i - 1, 8) * n
+      write(iu_rva(i)) rx(o + 1:o + n), ry(o + 1:o + n), rz(o + 1:o + n)
+      write(iu_rva(i)) ux(o + 1:o + n), uy(o + 1:o + n), uz(o + 1:o + n)
+      write(iu_rva(i)) vx(o + 1:o + n), vy(o + 1:o + n), vz(o + 1:o + n)
+      write(iu_rva(i)) ax(o + 1:o + n), ay(o + 1:o + n), az(o + 1:o + n)
+    end do
+  end do
+  rest = total_steps - step                         ! the steps after the last sampling instant: nothing is sampled
+  if (rest > 0) call ljmd_batch_check(ljmd_batch_steps(batch, int(rest, c_int32_t), 1_c_int32_t, c_null_ptr, &
+                                                       c_null_ptr, c_null_ptr, c_null_ptr), batch, 'ljmd_batch_steps')
+  call system_clock(c1)
+  call ljmd_batch_destroy(batch)
+  do i = 1, n_runs
+    close(iu_out(i))
+    close(iu_rva(i))
+  end do
+
+  if (num_samples <= 0) stop 'md_simulation: no samples were taken (check warmup_steps/output_interval).'
+  open(newunit=iu, file=runs_list, status='replace', action='write', iostat=ios)
+  if (ios /= 0) stop 'md_simulation_many: cannot open outputs/several_runs.txt for writing.'
+  write(iu, '(a)') '# List of MD run output directories (one per line)'
+  write(iu, '(a)') '# Generated by run_many_md.f90'
+  do i = 1, n_runs
+    call write_run_statistics(trim(run_dir(i)), params, total_steps, output_interval, warmup_steps, stats(i))
+    write(iu, '(a)') trim(run_dir(i))
+  end do
+  close(iu)
+  write(*, '(a,i0,a,i0,a,i0,a,f12.2,a)') 'md_simulation_many_gpu: N=', params%n, ' runs=', n_runs_c, ' steps=', &
+    total_steps, '  ', dble(n_runs) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' run-steps/s'
+
+contains
+
+  ! run i's rv_init.dat: record 1 = rx ry rz, record 2 = vx vy vz (md_initial_config_program.f90:285-286)
+  subroutine read_rv_init(irun)
+    integer, intent(in) :: irun
+    character(len=128) :: filename
+    logical :: own
+    integer :: iu_in, ierr
+    integer(kind=8) :: off
+    filename = trim(run_dir(irun)) // '/rv_init.dat'
+    inquire(file=trim(filename), exist=own)
+    if (.not. own) then
+      filename = 'outputs/rv_init.dat'
+      write(*, '(a,a,a)') 'md_simulation_many_gpu: ', trim(run_dir(irun)), &
+        ' starts from the shared outputs/rv_init.dat (identical to every other run that does)'
+    end if
+    open(newunit=iu_in, file=trim(filename), form='unformatted', status='old', action='read', iostat=ierr)
+    if (ierr /= 0) stop 'read_rv_init(): cannot open rv_init file.'
+    off = int(irun - 1, 8) * n
+    read(iu_in) rx(off + 1:off + n), ry(off + 1:off + n), rz(off + 1:off + n)
+    read(iu_in) vx(off + 1:off + n), vy(off + 1:off + n), vz(off + 1:off + n)
+    close(iu_in)
+  end subroutine read_rv_init
+
+end program md_simulation_many_gpu

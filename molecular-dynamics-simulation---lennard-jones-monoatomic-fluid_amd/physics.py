@@ -10,7 +10,8 @@ go through the *stateless* C entry points (ljmd_compute_lj_potential_energy /
 ljmd_verlet_step), i.e. exactly what the Fortran shim modules bind.
 
 `Engine` is the resident-state interface (ljmd_create ... ljmd_verlet_steps): state
-stays in HBM between calls and only the per-step scalars come back.
+stays in HBM between calls and only the per-step scalars come back.  `BatchEngine`
+(ljmd_batch_*) steps many independent small replicas of one system at once.
 """
 from __future__ import annotations
 
@@ -370,6 +371,120 @@ class Engine:
         out.update({k + "_median": med[i] for i, k in enumerate(names)})
         out["launches"] = c.value
         return out
+
+
+class BatchEngine:
+    """n_replicas independent systems of the same (n, L, dt, rc) on one GPU (ljmd_batch_*, include/ljmd.h): the ensemble
+    runs of the reference's run-many framework, one workgroup per replica.  Each replica is the physics of an Engine.
+    Per-particle arrays are (B, n) per component, per-replica scalars (B,); fp64 only, n <= 4096."""
+
+    def __init__(self, params: SimParams, n_replicas: int, device: int = 0):
+        self._lib = _lib.load()
+        self.params = params
+        self.n_replicas = int(n_replicas)
+        h = C.c_void_p()
+        _lib.check_batch(self._lib.ljmd_batch_create(C.byref(h), self.n_replicas, params.n, params.box_length,
+                                                     params.dt, params.rc, _lib.PRECISION_FP64, device))
+        self._h = h
+
+    # -- lifecycle ---------------------------------------------------------
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._lib.ljmd_batch_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _ck(self, status: int) -> None:
+        _lib.check_batch(status, self._h)
+
+    def _arrays(self, arrs, name: str):
+        shape = (self.n_replicas, self.params.n)
+        out = []
+        for a in arrs:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError(f"{name} must have shape {shape}, got {a.shape}")
+            out.append(a)
+        return out
+
+    # -- state transfer ----------------------------------------------------
+    def set_state(self, rx, ry, rz, vx, vy, vz) -> None:
+        arrs = self._arrays((rx, ry, rz, vx, vy, vz), "state array")
+        self._ck(self._lib.ljmd_batch_set_state(self._h, *[_ptr(a) for a in arrs]))
+
+    def set_accel(self, ax=None, ay=None, az=None) -> None:
+        """None = keep that component"""
+        ptrs, keep = [], []
+        for a in (ax, ay, az):
+            if a is None:
+                ptrs.append(None)
+            else:
+                (a,) = self._arrays((a,), "accel array")
+                keep.append(a)
+                ptrs.append(_ptr(a))
+        self._ck(self._lib.ljmd_batch_set_accel(self._h, *ptrs))
+
+    def set_unwrapped(self, ux, uy, uz) -> None:
+        arrs = self._arrays((ux, uy, uz), "unwrapped array")
+        self._ck(self._lib.ljmd_batch_set_unwrapped(self._h, *[_ptr(a) for a in arrs]))
+
+    def get_state(self, which=("r", "ru", "v", "a")) -> dict:
+        """-> {'r': (x, y, z), ...}, each component (B, n)"""
+        shape = (self.n_replicas, self.params.n)
+        out, ptrs = {}, []
+        for key in ("r", "ru", "v", "a"):
+            if key in which:
+                arrs = tuple(np.empty(shape, dtype=np.float64) for _ in range(3))
+                out[key] = arrs
+                ptrs += [_ptr(a) for a in arrs]
+            else:
+                ptrs += [None, None, None]
+        self._ck(self._lib.ljmd_batch_get_state(self._h, *ptrs))
+        return out
+
+    # -- hot path ----------------------------------------------------------
+    def compute_forces(self):
+        """-> (epot, d_epot, dd_epot), each (B,)"""
+        outs = [np.empty(self.n_replicas, dtype=np.float64) for _ in range(3)]
+        self._ck(self._lib.ljmd_batch_compute_forces(self._h, *[_ptr(o) for o in outs]))
+        return tuple(outs)
+
+    def kinetic_energy(self) -> np.ndarray:
+        out = np.empty(self.n_replicas, dtype=np.float64)
+        self._ck(self._lib.ljmd_batch_kinetic_energy(self._h, _ptr(out)))
+        return out
+
+    def steps(self, nsteps: int, sample_every: int = 1, observables: bool = True):
+        """nsteps Verlet steps of every replica -> (epot, ekin, d_epot, dd_epot), each (nsteps / sample_every, B): the
+        scalars of steps sample_every, 2 sample_every, ...; observables=False samples nothing and returns None"""
+        if not observables:
+            self._ck(self._lib.ljmd_batch_steps(self._h, nsteps, sample_every, None, None, None, None))
+            return None
+        if sample_every < 1 or nsteps % sample_every != 0:
+            raise ValueError("nsteps must be a multiple of sample_every >= 1")
+        outs = [np.empty((nsteps // sample_every, self.n_replicas), dtype=np.float64) for _ in range(4)]
+        self._ck(self._lib.ljmd_batch_steps(self._h, nsteps, sample_every, *[_ptr(o) for o in outs]))
+        return tuple(outs)
+
+    def set_tail_corrections(self, on: bool) -> None:
+        self._ck(self._lib.ljmd_batch_set_tail_corrections(self._h, 1 if on else 0))
+
+    def profile_read(self) -> dict:
+        """kernel time (ms, HIP events) and launches of the last steps() call"""
+        ms, c = C.c_double(), C.c_int32()
+        self._ck(self._lib.ljmd_batch_profile_read(self._h, C.byref(ms), C.byref(c)))
+        return {"kernel_ms": ms.value, "launches": c.value}
 
 
 def observables(params: SimParams, epot: float, ekin: float, d_epot: float):
