@@ -404,12 +404,16 @@ int ljmd_profile_read_stats(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, d
 
 /* ---- batch engine: many independent small systems on one device ------------------------------------------------
  *
- * One ljmd_batch_t holds B replicas of the same (n, L, dt, rc) on one device -- the ensemble runs of the reference's
- * run-many framework (scripts/run_many_md_simuations/run_many_md.f90) -- and steps all of them with one kernel,
- * one workgroup per replica, many steps per launch.  Each replica is exactly the physics of an ljmd_t.
+ * One ljmd_batch_t holds B replicas on one device -- the ensemble runs of the reference's run-many framework
+ * (scripts/run_many_md_simuations/run_many_md.f90), or a sweep over state points -- and steps all of them with one
+ * kernel, one workgroup per replica, many steps per launch.  ljmd_batch_create gives every replica the same
+ * (n, L, dt, rc); ljmd_batch_create_per_replica gives replica b its own (n_b, L_b, dt_b, rc_b).  Each replica is
+ * exactly the physics of an ljmd_t.
  *
- * Layout: per-particle arrays are fp64 with B*n elements, replica-major (element (b, i) at b*n + i); per-replica
- * scalars have B elements; the scalars of ljmd_batch_steps are [nsteps / sample_every][B], sample-major.
+ * Layout: per-particle arrays are fp64 with offsets[B] = sum n_b elements, the replicas concatenated in replica order
+ * (element (b, i) at offsets[b] + i; ljmd_batch_offsets; for ljmd_batch_create offsets[b] = b*n, replica-major);
+ * per-replica scalars have B elements; the scalars of ljmd_batch_steps are [nsteps / sample_every][B], sample-major.
+ * Every other ljmd_batch_* call works the same on both kinds of handle.
  *
  * Arithmetic, per replica, is the single engine's fast path (ljmd_kernels.hip):
  *   drift + wrap + half-kick + unwrapped update: drift_kick_kernel's expressions in the same order, no contraction,
@@ -421,14 +425,16 @@ int ljmd_profile_read_stats(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, d
  *     (tail constants included while ljmd_batch_set_tail_corrections is on, the default).
  * Tolerances against the reference are those of the single engine.
  *
- * Determinism: every floating-point sum of a replica runs in an order fixed by n alone, with no floating-point
+ * Determinism: every floating-point sum of a replica runs in an order fixed by its n alone, with no floating-point
  * atomics, so a replica's results are bitwise equal run to run and independent of B, of its slot in the batch and
- * of what the other replicas hold.  The energy sums are evaluated only on sampled steps; r, ru, v, a are bitwise the
+ * of what the other replicas hold: with its own (n, L, dt, rc) a replica gives the bits of a one-replica
+ * ljmd_batch_create handle of the same replica, whatever the other replicas' parameters, their order, the grouping
+ * into launches or the streams.  The energy sums are evaluated only on sampled steps; r, ru, v, a are bitwise the
  * same for every sample_every, and with no outputs at all.
  *
  * Limits: n <= LJMD_BATCH_MAX_N -- one replica's positions live in one CU's LDS for a whole launch, 24 n bytes
  * <= 96 KiB; LJMD_PRECISION_FP64 only; rc <= (1 - 1e-9) L/2 and, at ljmd_batch_set_state, every replica's
- * coordinates finite and spanning < 2.4 L per axis (the fast path's preconditions (b) and (a)): there is no
+ * coordinates finite and spanning < 2.4 L per axis (each replica against its own L) (the fast path's preconditions (b) and (a)): there is no
  * generic-kernel fallback in this mode, so such input fails with LJMD_ERR_INVALID_ARG.  All guards run before the
  * device probe; without a device ljmd_batch_create returns LJMD_ERR_NO_DEVICE.
  *
@@ -441,6 +447,14 @@ typedef struct ljmd_batch ljmd_batch_t;
 
 int ljmd_batch_create(ljmd_batch_t **out, int32_t n_replicas, int32_t n, double box_length, double dt, double rc,
                       int32_t precision_mode, int32_t device);
+/* B replicas, replica b with its own n[b], box_length[b], dt[b], rc[b] (arrays of n_replicas elements).  Every replica
+ * passes the guards of ljmd_batch_create; the sum of n must be < 2^31.  Failures before the device probe return
+ * LJMD_ERR_INVALID_ARG, the message starting "ljmd_batch_create_per_replica: replica <b>:" when one replica is at fault. */
+int ljmd_batch_create_per_replica(ljmd_batch_t **out, int32_t n_replicas, const int32_t *n,
+                                  const double *box_length, const double *dt, const double *rc,
+                                  int32_t precision_mode, int32_t device);
+/* offsets[B + 1]: replica b's particles are elements [offsets[b], offsets[b+1]) of every per-particle array. */
+int ljmd_batch_offsets(const ljmd_batch_t *h, int64_t *offsets);
 void ljmd_batch_destroy(ljmd_batch_t *h);
 /* Text of the most recent error on this handle (h == NULL: the thread's last failed ljmd_batch_create). */
 const char *ljmd_batch_last_error(const ljmd_batch_t *h);
@@ -469,7 +483,11 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every,
                      double *epot, double *ekin, double *d_epot, double *dd_epot);
 /* As ljmd_set_tail_corrections. */
 int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on);
-/* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL. */
+/* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL.
+ * Replicas of different kernel classes (n <= 128, 512, 1024, 2048, 4096) run as separate groups of launches, by
+ * default each on a stream of its own (LJMD_BATCH_GROUP_STREAMS=0: one after another on the handle's stream); the
+ * kernel time is then the span from the first group's first launch to the last group's end, not a sum over groups,
+ * and the launch count is the total over all groups. */
 int ljmd_batch_profile_read(const ljmd_batch_t *h, double *kernel_ms, int32_t *launches);
 
 #ifdef __cplusplus

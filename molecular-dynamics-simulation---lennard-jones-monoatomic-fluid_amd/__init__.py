@@ -9,5 +9,5 @@ Only what the hot path needs lives here:
 """
 from ._lib import LjmdError, load as load_library  # noqa: F401
 from .md_types import SimParams, SimState, init_params, init_state, compute_derived_params  # noqa: F401
-from .physics import (Engine, BatchEngine, compute_lj_potential_energy, verlet_step, minimum_image,  # noqa: F401
-                      observables)
+from .physics import (Engine, BatchEngine, PerReplicaBatchEngine, compute_lj_potential_energy,  # noqa: F401
+                      verlet_step, minimum_image, observables)

@@ -111,6 +111,9 @@ PROTOTYPES = {
     # batch engine: B independent replicas on one device (include/ljmd.h, ljmd_batch_*)
     "ljmd_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
                                     C.c_int32, C.c_int32]),
+    "ljmd_batch_create_per_replica": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, c_int32_p, c_double_p, c_double_p,
+                                                c_double_p, C.c_int32, C.c_int32]),
+    "ljmd_batch_offsets": (C.c_int, [C.c_void_p, c_int64_p]),
     "ljmd_batch_destroy": (None, [C.c_void_p]),
     "ljmd_batch_last_error": (C.c_char_p, [C.c_void_p]),
     "ljmd_batch_set_state": (C.c_int, [C.c_void_p] + [c_double_p] * 6),

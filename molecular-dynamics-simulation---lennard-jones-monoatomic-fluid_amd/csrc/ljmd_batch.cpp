@@ -1,23 +1,52 @@
-// ljmd_batch.cpp -- host side of the batch engine (include/ljmd.h: ljmd_batch_*): B independent replicas of the same
-// (n, L, dt, rc) on one device, stepped by one kernel (ljmd_batch.hip) with one workgroup per replica.  Handle
-// lifecycle, guards, device state, launch splitting and the combination of the per-replica step records.
+// ljmd_batch.cpp -- host side of the batch engine (include/ljmd.h: ljmd_batch_*): B independent replicas on one
+// device, each with its own (n, L, dt, rc) (ljmd_batch_create: all the same), stepped by one kernel (ljmd_batch.hip)
+// with one workgroup per replica.  Handle lifecycle, guards, device state, launch planning per kernel class and the
+// combination of the per-replica step records.
 #include "ljmd_batch.h"
 #include "ljmd_engine.h"
 
+#include <new>
+
 using namespace ljmdb;
 
-struct ljmd_batch {
+namespace {
+
+// one replica's parameters and derived constants (host side)
+struct BatchRep {
     int n = 0;
-    size_t B = 0;
-    int device = 0;
     double L = 0, invL = 0, rc = 0, rc2 = 0, dt = 0, dt_half = 0, dt_sq_half = 0, volume = 0;
     double tail_e = 0, tail_d = 0, tail_dd = 0;
+};
+
+// the replicas of one kernel class: entries [first, first + count) of the replica table, launched chunk replicas and
+// steps_per_launch steps at a time (launch_shape of n_max, the group's largest n)
+struct BatchGroup {
+    size_t first = 0, count = 0;
+    int n_max = 0;
+    size_t chunk = 0;
+    int steps_per_launch = 0;
+    hipStream_t stream = nullptr;     // own stream when the handle runs its groups concurrently, else the handle's
+    hipEvent_t done = nullptr;
+};
+
+}  // namespace
+
+struct ljmd_batch {
+    size_t B = 0;
+    size_t total = 0;                 // offsets[B]: elements of one plane
+    int device = 0;
+    std::vector<BatchRep> rep;        // [B], replica order
+    std::vector<int64_t> offsets;     // [B + 1]
+    std::vector<BatchGroup> groups;   // by kernel class, ascending
+    bool concurrent = false;          // groups on streams of their own, joined before the records are fetched
     bool tail_on = true;
     bool have_state = false, have_accel = false;
     bool poisoned = false;            // a launch failed half-way: LJMD_ERR_STATE until ljmd_batch_set_state
     hipStream_t stream = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};
-    double *d_state = nullptr;        // [12][B][n]
+    hipEvent_t fork = nullptr;
+    BatchReplica *d_table = nullptr;  // [B], the groups' entries one after another
+    double *d_state = nullptr;        // [12][offsets[B]]
     double *d_rec = nullptr;          // [rec_cap][B][kBatchRecWords]
     size_t rec_cap = 0;               // samples the record buffer holds (>= 1)
     std::vector<double> h_rec;
@@ -56,35 +85,56 @@ int bfail(const ljmd_batch *h, int code, const char *fmt, ...)
                          __LINE__);                                                                         \
     } while (0)
 
-double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->B * h->n; }
+double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
 
 BatchArgs base_args(ljmd_batch *h, int mode)
 {
     BatchArgs a{};
     a.state = h->d_state;
     a.rec = h->d_rec;
+    a.rep = h->d_table;
     a.B = h->B;
-    a.n = h->n;
+    a.plane = h->total;
     a.mode = mode;
-    a.L = h->L;
-    a.invL = h->invL;
-    a.rc2 = h->rc2;
-    a.dt = h->dt;
-    a.dt_half = h->dt_half;
-    a.dt_sq_half = h->dt_sq_half;
     return a;
 }
 
-// replicas per launch and steps per launch, from the n^2 * steps * max(replicas, CUs) estimate
-void launch_shape(const ljmd_batch *h, size_t *chunk, int *steps_per_launch)
+// replicas per launch and steps per launch of `count` replicas of at most n particles, from the
+// n^2 * steps * max(replicas, CUs) estimate
+void launch_shape(int n, size_t count, size_t *chunk, int *steps_per_launch)
 {
-    const double n2 = (double)h->n * h->n;
+    const double n2 = (double)n * n;
     const double c = std::max(kMinParallel, std::floor(kLaunchPairs / n2));
-    *chunk = std::min(h->B, (size_t)std::min(c, 2147483647.0));
+    *chunk = std::min(count, (size_t)std::min(c, 2147483647.0));
     const double s = std::floor(kLaunchPairs / (n2 * std::max(kMinParallel, (double)*chunk)));
-    const int passes = (batch_k(h->n) + 1) / 2;                 // passes over j per step (ljmd_batch.hip: KG)
-    const double s_latency = std::floor(kLaunchIterations / ((double)h->n * passes));
+    const int passes = (batch_k(n) + 1) / 2;                 // passes over j per step (ljmd_batch.hip: KG)
+    const double s_latency = std::floor(kLaunchIterations / ((double)n * passes));
     *steps_per_launch = (int)std::max(1.0, std::min({s, s_latency, (double)LJMD_MAX_PENDING_STEPS}));
+}
+
+// a replica's derived constants: compute_derived_params (md_types.f90:137-159), the expressions of ljmd_create
+BatchRep derive(int n, double box_length, double dt, double rc)
+{
+    BatchRep r;
+    r.n = n;
+    r.L = box_length;
+    r.invL = 1.0 / box_length;
+    r.volume = box_length * box_length * box_length;
+    r.rc = rc;
+    r.rc2 = rc * rc;
+    r.dt = dt;
+    r.dt_half = 0.5 * dt;
+    r.dt_sq_half = r.dt_half * dt;
+    {   // tail corrections, lj_potential_energy.f90:205-223
+        const double npd = (double)n;
+        const double rc3 = (rc * rc) * rc;
+        const double rc6 = ((rc * rc) * (rc * rc)) * (rc * rc);
+        const double tf = 8.0 * ljmdh::kPi * (npd * npd) / (r.volume * rc3);
+        r.tail_e = tf * ((1.0 / (3.0 * rc6)) - 1.0) / 3.0;
+        r.tail_d = 2.0 * tf * (-2.0 / (3.0 * rc6) + 1.0);
+        r.tail_dd = 2.0 * tf * (26.0 / (3.0 * rc6) - 7.0);
+    }
+    return r;
 }
 
 int ensure_records(ljmd_batch *h, size_t samples)
@@ -118,11 +168,12 @@ int fetch_records(ljmd_batch *h, size_t samples)
     return LJMD_OK;
 }
 
-// as combine_one (ljmd_capi.cpp) for one replica's record: the kernel already halved the ordered-pair sums
-void combine(const ljmd_batch *h, const double *r, double *epot, double *ekin, double *d_epot, double *dd_epot)
+// as combine_one (ljmd_capi.cpp) for replica b's record: the kernel already halved the ordered-pair sums
+void combine(const ljmd_batch *h, size_t b, const double *r, double *epot, double *ekin, double *d_epot, double *dd_epot)
 {
     const double s12 = r[0], s6 = r[1], kx = r[2], ky = r[3], kz = r[4];
-    const double te = h->tail_on ? h->tail_e : 0.0, td = h->tail_on ? h->tail_d : 0.0, tdd = h->tail_on ? h->tail_dd : 0.0;
+    const BatchRep &p = h->rep[b];
+    const double te = h->tail_on ? p.tail_e : 0.0, td = h->tail_on ? p.tail_d : 0.0, tdd = h->tail_on ? p.tail_dd : 0.0;
     if (epot) *epot = 4.0 * (s12 - s6) + te;
     if (d_epot) *d_epot = 24.0 * (-2.0 * s12 + s6) + td;
     if (dd_epot) *dd_epot = 24.0 * (26.0 * s12 - 7.0 * s6) + tdd;
@@ -131,8 +182,150 @@ void combine(const ljmd_batch *h, const double *r, double *epot, double *ekin, d
 
 int upload(ljmd_batch *h, int which, int axis, const double *src)
 {
-    BATCH_HIP(h, hipMemcpyAsync(plane(h, which, axis), src, h->B * h->n * sizeof(double), hipMemcpyHostToDevice,
+    BATCH_HIP(h, hipMemcpyAsync(plane(h, which, axis), src, h->total * sizeof(double), hipMemcpyHostToDevice,
                                 h->stream));
+    return LJMD_OK;
+}
+
+// one pass of the kernel over every replica in `mode`: nsteps steps (kModeSteps) or one evaluation.  Group by group,
+// launches of at most chunk replicas and steps_per_launch steps, in the order steps-outer, replicas-inner.  With
+// concurrent groups every group runs on its own stream between a fork from and a join into the handle's stream, so
+// what the handle's stream does next (the record copy) follows all of them.  A failed launch poisons the handle.
+int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const char *who)
+{
+    if (h->concurrent) {
+        BATCH_HIP(h, hipEventRecord(h->fork, h->stream));
+        for (const BatchGroup &g : h->groups) BATCH_HIP(h, hipStreamWaitEvent(g.stream, h->fork, 0));
+    }
+    const bool steps = a.mode == kModeSteps;
+    int32_t count = 0;
+    for (const BatchGroup &g : h->groups) {
+        hipStream_t s = h->concurrent ? g.stream : h->stream;
+        const int spl = steps ? g.steps_per_launch : 1;
+        for (int s0 = 0; s0 < (steps ? nsteps : 1); s0 += spl) {
+            a.step0 = s0;
+            a.nsteps = steps ? std::min(spl, nsteps - s0) : 0;
+            for (size_t c0 = 0; c0 < g.count; c0 += g.chunk) {
+                a.g0 = (int)(g.first + c0);
+                const hipError_t e = launch_batch(a, g.n_max, (int)std::min(g.chunk, g.count - c0), s);
+                ++count;
+                if (e != hipSuccess) {
+                    h->poisoned = true;
+                    if (steps)
+                        return bfail(h, LJMD_ERR_HIP, "%s: launch at step %d failed: %s; the handle is poisoned until "
+                                                      "ljmd_batch_set_state", who, s0, hipGetErrorString(e));
+                    return bfail(h, LJMD_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+                }
+            }
+        }
+        if (h->concurrent) {
+            BATCH_HIP(h, hipEventRecord(g.done, s));
+            BATCH_HIP(h, hipStreamWaitEvent(h->stream, g.done, 0));
+        }
+    }
+    if (launches) *launches = count;
+    return LJMD_OK;
+}
+
+// the device probe, after the caller's guards
+int probe(int32_t device, const char *who)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return bfail(nullptr, LJMD_ERR_NO_DEVICE, "%s: no HIP device available (this library has no CPU path)", who);
+    if (device < 0 || device >= ndev)
+        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: device %d out of range (0..%d)", who, device, ndev - 1);
+    return LJMD_OK;
+}
+
+// the handle from its replicas' parameters, after the guards and the probe: groups, stream(s), device memory
+int create_handle(ljmd_batch_t **out, std::vector<BatchRep> &&reps, int32_t device, const char *who)
+{
+    ljmd_batch *h = new (std::nothrow) ljmd_batch;
+    if (!h) return bfail(nullptr, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+    auto undo = [&](int code) {
+        const std::string msg = h->err;
+        ljmd_batch_destroy(h);
+        ljmdh::g_last_error = msg;
+        return code;
+    };
+    h->B = reps.size();
+    h->device = device;
+    std::vector<BatchReplica> table;
+    try {
+        h->rep = std::move(reps);
+        h->offsets.resize(h->B + 1);
+        table.reserve(h->B);
+    } catch (const std::bad_alloc &) {
+        bfail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+        return undo(LJMD_ERR_ALLOC);
+    }
+    h->offsets[0] = 0;
+    for (size_t b = 0; b < h->B; ++b) h->offsets[b + 1] = h->offsets[b] + h->rep[b].n;
+    h->total = (size_t)h->offsets[h->B];
+    // the replica table, grouped by kernel class; replica order inside a group
+    for (int c = 0; c < kBatchClasses; ++c) {
+        BatchGroup g;
+        g.first = table.size();
+        for (size_t b = 0; b < h->B; ++b) {
+            const BatchRep &p = h->rep[b];
+            if (batch_class(p.n) != c) continue;
+            BatchReplica e{};
+            e.off = (size_t)h->offsets[b];
+            e.b = (int)b;
+            e.n = p.n;
+            e.threads = batch_threads(p.n);
+            e.L = p.L;
+            e.invL = p.invL;
+            e.rc2 = p.rc2;
+            e.dt = p.dt;
+            e.dt_half = p.dt_half;
+            e.dt_sq_half = p.dt_sq_half;
+            table.push_back(e);
+            g.n_max = std::max(g.n_max, p.n);
+        }
+        g.count = table.size() - g.first;
+        if (g.count == 0) continue;
+        launch_shape(g.n_max, g.count, &g.chunk, &g.steps_per_launch);
+        h->groups.push_back(g);
+    }
+    // several groups run concurrently unless LJMD_BATCH_GROUP_STREAMS=0 (one after another on the handle's stream)
+    const char *env = std::getenv("LJMD_BATCH_GROUP_STREAMS");
+    h->concurrent = h->groups.size() > 1 && !(env && std::strcmp(env, "0") == 0);
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreate(&h->ev[0]) != hipSuccess || hipEventCreate(&h->ev[1]) != hipSuccess) {
+        bfail(h, LJMD_ERR_HIP, "%s: cannot create the stream on device %d", who, device);
+        return undo(LJMD_ERR_HIP);
+    }
+    if (h->concurrent) {
+        bool ok = hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) == hipSuccess;
+        for (BatchGroup &g : h->groups)
+            ok = ok && hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking) == hipSuccess &&
+                 hipEventCreateWithFlags(&g.done, hipEventDisableTiming) == hipSuccess;
+        if (!ok) {
+            bfail(h, LJMD_ERR_HIP, "%s: cannot create the group streams on device %d", who, device);
+            return undo(LJMD_ERR_HIP);
+        }
+    }
+    const size_t bytes = 12 * h->total * sizeof(double);
+    if (hipMalloc(&h->d_state, bytes) != hipSuccess) {
+        h->d_state = nullptr;
+        bfail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of replica state", who, bytes);
+        return undo(LJMD_ERR_ALLOC);
+    }
+    const size_t tbytes = h->B * sizeof(BatchReplica);
+    if (hipMalloc(&h->d_table, tbytes) != hipSuccess) {
+        h->d_table = nullptr;
+        bfail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of the replica table", who, tbytes);
+        return undo(LJMD_ERR_ALLOC);
+    }
+    if (hipMemcpyAsync(h->d_table, table.data(), tbytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+        bfail(h, LJMD_ERR_HIP, "%s: cannot upload the replica table", who);
+        return undo(LJMD_ERR_HIP);
+    }
+    if (ensure_records(h, 1) != LJMD_OK) return undo(LJMD_ERR_ALLOC);
+    *out = h;
     return LJMD_OK;
 }
 
@@ -164,54 +357,63 @@ int ljmd_batch_create(ljmd_batch_t **out, int32_t n_replicas, int32_t n, double 
     if (!(rc <= (1.0 - 1e-9) * 0.5 * box_length))
         return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: rc must be <= (1 - 1e-9) L/2 (fast-path "
                                                     "precondition; batches have no generic kernel)");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return bfail(nullptr, LJMD_ERR_NO_DEVICE, "ljmd_batch_create: no HIP device available (this library has no CPU path)");
-    if (device < 0 || device >= ndev)
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: device %d out of range (0..%d)", device, ndev - 1);
+    const int rc_ = probe(device, "ljmd_batch_create");
+    if (rc_ != LJMD_OK) return rc_;
+    std::vector<BatchRep> reps;
+    try {
+        reps.assign((size_t)n_replicas, derive(n, box_length, dt, rc));
+    } catch (const std::bad_alloc &) {
+        return bfail(nullptr, LJMD_ERR_ALLOC, "ljmd_batch_create: out of host memory");
+    }
+    return create_handle(out, std::move(reps), device, "ljmd_batch_create");
+}
 
-    ljmd_batch *h = new (std::nothrow) ljmd_batch;
-    if (!h) return bfail(nullptr, LJMD_ERR_ALLOC, "ljmd_batch_create: out of host memory");
-    h->n = n;
-    h->B = (size_t)n_replicas;
-    h->device = device;
-    // compute_derived_params, md_types.f90:137-159, the expressions of ljmd_create
-    h->L = box_length;
-    h->invL = 1.0 / box_length;
-    h->volume = box_length * box_length * box_length;
-    h->rc = rc;
-    h->rc2 = rc * rc;
-    h->dt = dt;
-    h->dt_half = 0.5 * dt;
-    h->dt_sq_half = h->dt_half * dt;
-    {   // tail corrections, lj_potential_energy.f90:205-223
-        const double npd = (double)n;
-        const double rc3 = (rc * rc) * rc;
-        const double rc6 = ((rc * rc) * (rc * rc)) * (rc * rc);
-        const double tf = 8.0 * ljmdh::kPi * (npd * npd) / (h->volume * rc3);
-        h->tail_e = tf * ((1.0 / (3.0 * rc6)) - 1.0) / 3.0;
-        h->tail_d = 2.0 * tf * (-2.0 / (3.0 * rc6) + 1.0);
-        h->tail_dd = 2.0 * tf * (26.0 / (3.0 * rc6) - 7.0);
+int ljmd_batch_create_per_replica(ljmd_batch_t **out, int32_t n_replicas, const int32_t *n, const double *box_length,
+                                  const double *dt, const double *rc, int32_t precision_mode, int32_t device)
+{
+    static const char *who = "ljmd_batch_create_per_replica";
+    if (!out) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: out is NULL", who);
+    *out = nullptr;
+    if (n_replicas < 1) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: n_replicas must be >= 1", who);
+    if (!n || !box_length || !dt || !rc)
+        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: n, box_length, dt and rc must not be NULL", who);
+    if (precision_mode != LJMD_PRECISION_FP64)
+        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: precision_mode %d not available for batches "
+                                                    "(LJMD_PRECISION_FP64 only)", who, precision_mode);
+    // every replica passes the guards of ljmd_batch_create
+    int64_t total = 0;
+    for (int32_t b = 0; b < n_replicas; ++b) {
+        const double L = box_length[b];
+        if (n[b] <= 0 || n[b] > LJMD_BATCH_MAX_N)
+            return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: n = %d outside 1..LJMD_BATCH_MAX_N (%d)", who,
+                         b, n[b], LJMD_BATCH_MAX_N);
+        if (!(L > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: box_length must be > 0", who, b);
+        if (!(dt[b] > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: dt must be > 0", who, b);
+        if (!(rc[b] > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: rc must be > 0", who, b);
+        if (!(rc[b] <= (1.0 - 1e-9) * 0.5 * L))
+            return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: rc must be <= (1 - 1e-9) L/2 (fast-path "
+                                                        "precondition; batches have no generic kernel)", who, b);
+        total += n[b];
     }
-    auto undo = [&](int code) {
-        const std::string msg = h->err;
-        ljmd_batch_destroy(h);
-        ljmdh::g_last_error = msg;
-        return code;
-    };
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&h->ev[0]) != hipSuccess || hipEventCreate(&h->ev[1]) != hipSuccess) {
-        bfail(h, LJMD_ERR_HIP, "ljmd_batch_create: cannot create the stream on device %d", device);
-        return undo(LJMD_ERR_HIP);
+    if (total >= ((int64_t)1 << 31))
+        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: %lld particles in all; the sum of n must be < 2^31", who,
+                     (long long)total);
+    const int rc_ = probe(device, who);
+    if (rc_ != LJMD_OK) return rc_;
+    std::vector<BatchRep> reps;
+    try {
+        reps.reserve((size_t)n_replicas);
+        for (int32_t b = 0; b < n_replicas; ++b) reps.push_back(derive(n[b], box_length[b], dt[b], rc[b]));
+    } catch (const std::bad_alloc &) {
+        return bfail(nullptr, LJMD_ERR_ALLOC, "%s: out of host memory", who);
     }
-    const size_t bytes = 12 * h->B * (size_t)n * sizeof(double);
-    if (hipMalloc(&h->d_state, bytes) != hipSuccess) {
-        h->d_state = nullptr;
-        bfail(h, LJMD_ERR_ALLOC, "ljmd_batch_create: cannot allocate %zu bytes of replica state", bytes);
-        return undo(LJMD_ERR_ALLOC);
-    }
-    if (ensure_records(h, 1) != LJMD_OK) return undo(LJMD_ERR_ALLOC);
-    *out = h;
+    return create_handle(out, std::move(reps), device, who);
+}
+
+int ljmd_batch_offsets(const ljmd_batch_t *h, int64_t *offsets)
+{
+    if (!h || !offsets) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_offsets: NULL argument");
+    std::copy(h->offsets.begin(), h->offsets.end(), offsets);
     return LJMD_OK;
 }
 
@@ -221,9 +423,17 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->d_state) (void)hipFree(h->d_state);
+    for (const BatchGroup &g : h->groups)
+        if (g.stream) (void)hipStreamSynchronize(g.stream);
     if (h->d_rec) (void)hipFree(h->d_rec);
+    if (h->d_table) (void)hipFree(h->d_table);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
+    if (h->fork) (void)hipEventDestroy(h->fork);
+    for (const BatchGroup &g : h->groups) {
+        if (g.done) (void)hipEventDestroy(g.done);
+        if (g.stream) (void)hipStreamDestroy(g.stream);
+    }
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -233,25 +443,27 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
 {
     if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: NULL handle");
     if (!rx || !ry || !rz || !vx || !vy || !vz) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: NULL array");
-    // fast-path precondition (a), ljmd_kernels.hip: per replica and axis, finite coordinates spanning < 2.4 L
+    // fast-path precondition (a), ljmd_kernels.hip: per replica and axis, finite coordinates spanning < 2.4 L_b
     const double *src[3] = {rx, ry, rz};
     for (size_t b = 0; b < h->B; ++b)
         for (int ax = 0; ax < 3; ++ax) {
-            const double *p = src[ax] + b * h->n;
+            const double *p = src[ax] + h->offsets[b];
             double lo = INFINITY, hi = -INFINITY;
-            for (int i = 0; i < h->n; ++i) {
+            for (int i = 0; i < h->rep[b].n; ++i) {
                 lo = std::min(lo, p[i]);
                 hi = std::max(hi, p[i]);
                 if (!std::isfinite(p[i]))
                     return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: replica %zu has a non-finite position", b);
             }
-            if (!(hi - lo < 2.4 * h->L))
+            if (!(hi - lo < 2.4 * h->rep[b].L))
                 return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: replica %zu spans >= 2.4 L along axis %d "
                                                       "(wrap the positions first)", b, ax);
         }
     BATCH_HIP(h, hipSetDevice(h->device));
     if (h->poisoned) {
         (void)hipStreamSynchronize(h->stream);   // drain what a failed call left behind
+        for (const BatchGroup &g : h->groups)
+            if (g.stream) (void)hipStreamSynchronize(g.stream);
         (void)hipGetLastError();
         h->poisoned = false;
     }
@@ -262,7 +474,7 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
         if (rc_ == LJMD_OK) rc_ = upload(h, LJMD_V, ax, vs[ax]);
         if (rc_ != LJMD_OK) return rc_;
     }
-    BATCH_HIP(h, hipMemsetAsync(plane(h, LJMD_A, 0), 0, 3 * h->B * h->n * sizeof(double), h->stream));
+    BATCH_HIP(h, hipMemsetAsync(plane(h, LJMD_A, 0), 0, 3 * h->total * sizeof(double), h->stream));
     BATCH_HIP(h, hipStreamSynchronize(h->stream));
     h->have_state = true;
     h->have_accel = false;
@@ -314,7 +526,7 @@ int ljmd_batch_get_state(ljmd_batch_t *h, double *rx, double *ry, double *rz, do
     double *const dst[12] = {rx, ry, rz, ux, uy, uz, vx, vy, vz, ax, ay, az};
     for (int k = 0; k < 12; ++k)
         if (dst[k])
-            BATCH_HIP(h, hipMemcpyAsync(dst[k], plane(h, k / 3, k % 3), h->B * h->n * sizeof(double),
+            BATCH_HIP(h, hipMemcpyAsync(dst[k], plane(h, k / 3, k % 3), h->total * sizeof(double),
                                         hipMemcpyDeviceToHost, h->stream));
     BATCH_HIP(h, hipStreamSynchronize(h->stream));
     return LJMD_OK;
@@ -328,23 +540,13 @@ int ljmd_batch_compute_forces(ljmd_batch_t *h, double *epot, double *d_epot, dou
         return bfail(h, LJMD_ERR_STATE, "ljmd_batch_compute_forces: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
     BATCH_HIP(h, hipSetDevice(h->device));
-    size_t chunk;
-    int spl;
-    launch_shape(h, &chunk, &spl);
-    BatchArgs a = base_args(h, kModeForces);
-    for (size_t b0 = 0; b0 < h->B; b0 += chunk) {
-        a.b0 = (int)b0;
-        const hipError_t e = launch_batch(a, (int)std::min(chunk, h->B - b0), h->stream);
-        if (e != hipSuccess) {
-            h->poisoned = true;
-            return bfail(h, LJMD_ERR_HIP, "ljmd_batch_compute_forces: launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    const int rc_ = fetch_records(h, 1);
+    int rc_ = run_groups(h, base_args(h, kModeForces), 0, nullptr, "ljmd_batch_compute_forces");
+    if (rc_ != LJMD_OK) return rc_;
+    rc_ = fetch_records(h, 1);
     if (rc_ != LJMD_OK) return rc_;
     h->have_accel = true;
     for (size_t b = 0; b < h->B; ++b)
-        combine(h, h->h_rec.data() + b * kBatchRecWords, epot ? epot + b : nullptr, nullptr,
+        combine(h, b, h->h_rec.data() + b * kBatchRecWords, epot ? epot + b : nullptr, nullptr,
                 d_epot ? d_epot + b : nullptr, dd_epot ? dd_epot + b : nullptr);
     return LJMD_OK;
 }
@@ -357,19 +559,9 @@ int ljmd_batch_kinetic_energy(ljmd_batch_t *h, double *ekin)
         return bfail(h, LJMD_ERR_STATE, "ljmd_batch_kinetic_energy: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
     BATCH_HIP(h, hipSetDevice(h->device));
-    size_t chunk;
-    int spl;
-    launch_shape(h, &chunk, &spl);
-    BatchArgs a = base_args(h, kModeKinetic);
-    for (size_t b0 = 0; b0 < h->B; b0 += chunk) {
-        a.b0 = (int)b0;
-        const hipError_t e = launch_batch(a, (int)std::min(chunk, h->B - b0), h->stream);
-        if (e != hipSuccess) {
-            h->poisoned = true;
-            return bfail(h, LJMD_ERR_HIP, "ljmd_batch_kinetic_energy: launch failed: %s", hipGetErrorString(e));
-        }
-    }
-    const int rc_ = fetch_records(h, 1);
+    int rc_ = run_groups(h, base_args(h, kModeKinetic), 0, nullptr, "ljmd_batch_kinetic_energy");
+    if (rc_ != LJMD_OK) return rc_;
+    rc_ = fetch_records(h, 1);
     if (rc_ != LJMD_OK) return rc_;
     for (size_t b = 0; b < h->B; ++b) ekin[b] = 0.5 * h->h_rec[b * kBatchRecWords + 2];   // md_simulation_program.f90:238-240
     return LJMD_OK;
@@ -402,27 +594,12 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     const size_t samples = sampling ? (size_t)(nsteps / sample_every) : 0;
     int rc_ = ensure_records(h, samples);
     if (rc_ != LJMD_OK) return rc_;
-    size_t chunk;
-    int spl;
-    launch_shape(h, &chunk, &spl);
     BatchArgs a = base_args(h, kModeSteps);
     a.sample_every = sampling ? sample_every : 0;
     int32_t launches = 0;
     BATCH_HIP(h, hipEventRecord(h->ev[0], h->stream));
-    for (int s0 = 0; s0 < nsteps; s0 += spl) {
-        a.step0 = s0;
-        a.nsteps = std::min(spl, nsteps - s0);
-        for (size_t b0 = 0; b0 < h->B; b0 += chunk) {
-            a.b0 = (int)b0;
-            const hipError_t e = launch_batch(a, (int)std::min(chunk, h->B - b0), h->stream);
-            ++launches;
-            if (e != hipSuccess) {
-                h->poisoned = true;
-                return bfail(h, LJMD_ERR_HIP, "ljmd_batch_steps: launch at step %d failed: %s; the handle is poisoned "
-                                              "until ljmd_batch_set_state", s0, hipGetErrorString(e));
-            }
-        }
-    }
+    rc_ = run_groups(h, a, nsteps, &launches, "ljmd_batch_steps");
+    if (rc_ != LJMD_OK) return rc_;
     BATCH_HIP(h, hipEventRecord(h->ev[1], h->stream));
     rc_ = fetch_records(h, samples);
     if (rc_ != LJMD_OK) return rc_;
@@ -433,7 +610,7 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     for (size_t s = 0; s < samples; ++s)
         for (size_t b = 0; b < h->B; ++b) {
             const size_t o = s * h->B + b;
-            combine(h, h->h_rec.data() + o * kBatchRecWords, epot ? epot + o : nullptr, ekin ? ekin + o : nullptr,
+            combine(h, b, h->h_rec.data() + o * kBatchRecWords, epot ? epot + o : nullptr, ekin ? ekin + o : nullptr,
                     d_epot ? d_epot + o : nullptr, dd_epot ? dd_epot + o : nullptr);
         }
     return LJMD_OK;

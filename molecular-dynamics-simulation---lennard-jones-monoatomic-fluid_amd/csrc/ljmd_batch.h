@@ -1,7 +1,8 @@
 // ljmd_batch.h -- argument block of the batch kernel (ljmd_batch.hip), shared with its host side ljmd_batch.cpp.
 //
-// Device layout of a batch of B replicas of n particles: twelve planes of B*n doubles, replica-major inside a plane
-// (element (b, i) at b*n + i), in the order rx ry rz | ux uy uz | vx vy vz | ax ay az.  Step records: per sample and
+// Device layout of a batch of B replicas, replica b holding n_b particles: twelve planes of offsets[B] = sum n_b
+// doubles, the replicas concatenated in replica order inside a plane (element (b, i) at offsets[b] + i; for B replicas
+// of one n, offsets[b] = b*n), in the order rx ry rz | ux uy uz | vx vy vz | ax ay az.  Step records: per sample and
 // replica kBatchRecWords doubles {0.5 sum u^6, 0.5 sum u^3 over the replica's ordered pairs, sum vx^2, sum vy^2,
 // sum vz^2}, sample-major: record (s, b) at (s*B + b) * kBatchRecWords.
 #ifndef LJMD_BATCH_KERNEL_H
@@ -23,19 +24,29 @@ enum BatchMode : int {
     kModeKinetic = 2,   // record 0 word 2 = sum (vx*vx + vy*vy + vz*vz), the fused form of ljmd_kinetic_energy
 };
 
-struct BatchArgs {
-    double *state;          // [12][B][n]
-    double *rec;            // [n_samples][B][kBatchRecWords]
-    size_t B;               // replicas of the handle (plane stride = B * n)
+// one replica of a launch: its own n and constants.  The host keeps these entries grouped by kernel class
+// (batch_class); a launch covers a contiguous range of them, blockIdx.x + BatchArgs::g0.
+struct BatchReplica {
+    size_t off;             // offsets[b]: the replica's first element in every plane
+    int b;                  // replica index: its record slot
     int n;
-    int b0;                 // first replica of this launch (blockIdx.x + b0)
+    int threads;            // batch_threads(n): the replica's own thread count, <= blockDim.x
+    int pad_;
+    double L, invL, rc2, dt, dt_half, dt_sq_half;
+};
+
+struct BatchArgs {
+    double *state;          // [12][plane]
+    double *rec;            // [n_samples][B][kBatchRecWords]
+    const BatchReplica *rep;  // the handle's replica table (device), launch order
+    size_t B;               // replicas of the handle (record stride)
+    size_t plane;           // elements of one plane = offsets[B]
+    int g0;                 // first table entry of this launch (blockIdx.x + g0)
     int mode;
     int nsteps;             // steps of this launch (kModeSteps)
     int step0;              // steps of the same ljmd_batch_steps call before this launch
     int sample_every;       // step s (1-based within the call) is sampled when s % sample_every == 0; 0 = none
-    double L, invL, rc2, dt, dt_half, dt_sq_half;
 };
-
 
 // own particles per thread: 1 up to n = 1024, then 2, then 4 (<= 1024 threads per workgroup)
 inline int batch_k(int n) { return n <= 1024 ? 1 : n <= 2048 ? 2 : 4; }
@@ -45,7 +56,13 @@ inline int batch_threads(int n)
     return 64 * ((n + 64 * k - 1) / (64 * k));
 }
 
-hipError_t launch_batch(const BatchArgs &a, int n_blocks, hipStream_t s);
+// kernel class (NMAX, K) of a replica of n particles: 0 <= 128 < 1 <= 512 < 2 <= 1024 < 3 <= 2048 < 4 <= 4096
+constexpr int kBatchClasses = 5;
+inline int batch_class(int n) { return n <= 128 ? 0 : n <= 512 ? 1 : n <= 1024 ? 2 : n <= 2048 ? 3 : 4; }
+
+// one launch of n_blocks table entries, all of batch_class(n_max), each at most n_max particles; the workgroup has
+// batch_threads(n_max) threads, of which an entry of fewer particles uses its own batch_threads(n)
+hipError_t launch_batch(const BatchArgs &a, int n_max, int n_blocks, hipStream_t s);
 
 }  // namespace ljmdb
 

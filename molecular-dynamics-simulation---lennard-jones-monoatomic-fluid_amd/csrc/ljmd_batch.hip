@@ -1,5 +1,5 @@
-// ljmd_batch.hip -- gfx950 kernel of the batch engine (include/ljmd.h: ljmd_batch_*): many independent small systems
-// of the same (n, L, dt, rc), one workgroup per replica, many MD steps per launch.
+// ljmd_batch.hip -- gfx950 kernel of the batch engine (include/ljmd.h: ljmd_batch_*): many independent small systems,
+// each with its own (n, L, dt, rc), one workgroup per replica, many MD steps per launch.
 //
 // Per replica the arithmetic is the single engine's fast path:
 //   drift + wrap + half-kick + unwrapped update  = drift_kick_kernel<0> (ljmd_kernels.hip), same expression order;
@@ -9,12 +9,15 @@
 //   second half-kick                             = kick_kernel<true>: a = 24 f, v += a dt/2, three separate sums of v^2.
 // Compiled with -ffp-contract=off (csrc/Makefile): FMAs only where the source says fma().
 //
-// Determinism: every floating-point sum of a replica runs in an order fixed by n alone -- j = 0 .. n-1 per particle,
+// Determinism: every floating-point sum of a replica runs in an order fixed by its n alone -- j = 0 .. n-1 per particle,
 // the own particles of a thread in order, the lanes of a wave by the shuffle tree, the waves in order.  Nothing
-// depends on B, on the replica's slot or on the other replicas, and there are no floating-point atomics.
+// depends on B, on the replica's slot or on the other replicas, and there are no floating-point atomics.  A replica
+// reads its n and constants from the replica table (BatchReplica) and always uses its own thread count
+// T = batch_threads(n) and mapping, whatever the launch's block size: a launch sized for a larger replica of the same
+// class leaves the waves from T on idle, and they only take part in the barriers.
 //
 // Shape: the replica's positions stay in LDS (SoA, 3 NMAX doubles) for the whole launch; j is uniform across the
-// workgroup, so every position read is a broadcast.  A thread owns particles tid, tid + T, ... (K of them); their
+// workgroup, so every position read is a broadcast.  A thread tid < T owns particles tid, tid + T, ... (K of them); their
 // ru, v, a stay in HBM (read and written by the owning thread only), their pair accumulators in registers.
 #include "ljmd_batch.h"
 
@@ -71,11 +74,12 @@ __device__ __forceinline__ double wave_sum(double v)
     return v;  // valid in lane 0
 }
 
-// fixed-order workgroup sum for blockDim.x / 64 <= kBatchMaxWaves waves; the result is valid in thread 0
+// fixed-order sum over the first W <= kBatchMaxWaves waves of the workgroup (the replica's own); every thread of the
+// workgroup calls it (it holds a barrier), the waves from W on contribute nothing.  The result is valid in thread 0
 template <int NVAL>
-__device__ __forceinline__ void block_sum_waves(double (&v)[NVAL], double *red /* [NVAL * kBatchMaxWaves] */)
+__device__ __forceinline__ void block_sum_waves(double (&v)[NVAL], double *red /* [NVAL * kBatchMaxWaves] */, int W)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, W = blockDim.x >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < NVAL; ++k) {
         const double s = wave_sum(v[k]);
@@ -115,9 +119,14 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
 {
     __shared__ double pos[3 * NMAX];
     __shared__ double red[kBatchRecWords * kBatchMaxWaves];
-    const int n = a.n, T = blockDim.x, tid = threadIdx.x;
-    const size_t b = (size_t)a.b0 + blockIdx.x;
-    const size_t plane = a.B * (size_t)n, base = b * (size_t)n;
+    const BatchReplica &rp = a.rep[a.g0 + blockIdx.x];
+    const int n = rp.n, T = rp.threads, tid = threadIdx.x;
+    const double L = rp.L, invL = rp.invL, rc2 = rp.rc2, dt = rp.dt, dt_half = rp.dt_half, dt_sq_half = rp.dt_sq_half;
+    const size_t b = (size_t)rp.b;
+    const size_t plane = a.plane, base = rp.off;
+    // own particles: i = tid + k T < n_own; an idle thread (tid >= T, whole waves) owns none
+    const bool own = tid < T;
+    const int n_own = own ? n : 0;
     double *const R = a.state;
     double *const RU = a.state + 3 * plane;
     double *const V = a.state + 6 * plane;
@@ -128,12 +137,12 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int i = tid + k * T;
-            if (i < n) {
+            if (i < n_own) {
                 const double vx = V[base + i], vy = V[plane + base + i], vz = V[2 * plane + base + i];
                 s[0] += vx * vx + vy * vy + vz * vz;
             }
         }
-        block_sum_waves<1>(s, red);
+        block_sum_waves<1>(s, red, T >> 6);
         if (tid == 0) {
             double *w = a.rec + b * kBatchRecWords;
             w[0] = 0.0;
@@ -142,10 +151,10 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
             w[3] = 0.0;
             w[4] = 0.0;
         }
-        return;
+        return;    // the mode is uniform across the launch: no thread of the workgroup reaches another barrier
     }
 
-    for (int i = tid; i < n; i += T) {
+    for (int i = tid; i < n; i += blockDim.x) {
         pos[i] = R[base + i];
         pos[NMAX + i] = R[plane + base + i];
         pos[2 * NMAX + i] = R[2 * plane + base + i];
@@ -162,19 +171,19 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
 #pragma unroll 1
             for (int k = 0; k < K; ++k) {
                 const int i = tid + k * T;
-                if (i < n) {
+                if (i < n_own) {
 #pragma unroll
                     for (int ax = 0; ax < 3; ++ax) {
                         const size_t o = ax * plane + base + i;
                         const double v0 = V[o], acc = A[o];
                         const double r0 = pos[ax * NMAX + i];
-                        double r1 = (r0 + v0 * a.dt) + acc * a.dt_sq_half;
-                        r1 = r1 - a.L * __builtin_floor(r1 * a.invL);
+                        double r1 = (r0 + v0 * dt) + acc * dt_sq_half;
+                        r1 = r1 - L * __builtin_floor(r1 * invL);
                         double d = r1 - r0;
-                        d = d - a.L * __builtin_round(d * a.invL);
+                        d = d - L * __builtin_round(d * invL);
                         pos[ax * NMAX + i] = r1;
                         RU[o] = RU[o] + d;
-                        V[o] = v0 + acc * a.dt_half;
+                        V[o] = v0 + acc * dt_half;
                     }
                 }
             }
@@ -185,45 +194,47 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
         // follows its pass, so nothing of it stays live.  Sums over the own particles run in order k = 0 .. K-1.
         constexpr int KG = K < 2 ? K : 2;
         double e12 = 0.0, e6 = 0.0, kk[3] = {0.0, 0.0, 0.0};
+        if (own) {     // wave-uniform (T is a multiple of 64); no barrier inside
 #pragma unroll 1
-        for (int g = 0; g < K; g += KG) {
-            double xs[KG], ys[KG], zs[KG], fs[3][KG], es[2][KG];
-            int is[KG];
+            for (int g = 0; g < K; g += KG) {
+                double xs[KG], ys[KG], zs[KG], fs[3][KG], es[2][KG];
+                int is[KG];
 #pragma unroll
-            for (int k = 0; k < KG; ++k) {
-                const int i = tid + (g + k) * T;
-                is[k] = i;
-                xs[k] = i < n ? pos[i] : __builtin_nan("");
-                ys[k] = i < n ? pos[NMAX + i] : __builtin_nan("");
-                zs[k] = i < n ? pos[2 * NMAX + i] : __builtin_nan("");
-            }
-            if (sampled)
-                gather<NMAX, KG, true>(pos, n, xs, ys, zs, is, a.L, a.invL, a.rc2, fs, es);
-            else
-                gather<NMAX, KG, false>(pos, n, xs, ys, zs, is, a.L, a.invL, a.rc2, fs, es);
-            // kick_kernel<KICK = steps>: a = 24 f, second half-kick, sums of v^2 per axis
+                for (int k = 0; k < KG; ++k) {
+                    const int i = tid + (g + k) * T;
+                    is[k] = i;
+                    xs[k] = i < n ? pos[i] : __builtin_nan("");
+                    ys[k] = i < n ? pos[NMAX + i] : __builtin_nan("");
+                    zs[k] = i < n ? pos[2 * NMAX + i] : __builtin_nan("");
+                }
+                if (sampled)
+                    gather<NMAX, KG, true>(pos, n, xs, ys, zs, is, L, invL, rc2, fs, es);
+                else
+                    gather<NMAX, KG, false>(pos, n, xs, ys, zs, is, L, invL, rc2, fs, es);
+                // kick_kernel<KICK = steps>: a = 24 f, second half-kick, sums of v^2 per axis
 #pragma unroll
-            for (int k = 0; k < KG; ++k) {
-                if (is[k] < n) {
+                for (int k = 0; k < KG; ++k) {
+                    if (is[k] < n) {
 #pragma unroll
-                    for (int ax = 0; ax < 3; ++ax) {
-                        const size_t o = ax * plane + base + is[k];
-                        const double acc = 24.0 * fs[ax][k];
-                        A[o] = acc;
-                        if (steps) {
-                            const double v1 = V[o] + acc * a.dt_half;
-                            V[o] = v1;
-                            if (sampled) kk[ax] += v1 * v1;
+                        for (int ax = 0; ax < 3; ++ax) {
+                            const size_t o = ax * plane + base + is[k];
+                            const double acc = 24.0 * fs[ax][k];
+                            A[o] = acc;
+                            if (steps) {
+                                const double v1 = V[o] + acc * dt_half;
+                                V[o] = v1;
+                                if (sampled) kk[ax] += v1 * v1;
+                            }
                         }
                     }
+                    e12 += es[0][k];
+                    e6 += es[1][k];
                 }
-                e12 += es[0][k];
-                e6 += es[1][k];
             }
         }
         if (sampled) {
             double v[kBatchRecWords] = {e12, e6, kk[0], kk[1], kk[2]};
-            block_sum_waves<kBatchRecWords>(v, red);
+            block_sum_waves<kBatchRecWords>(v, red, T >> 6);
             if (tid == 0) {
                 const size_t rec = steps ? (size_t)(gstep / a.sample_every - 1) : 0;
                 double *w = a.rec + (rec * a.B + b) * kBatchRecWords;
@@ -240,7 +251,7 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             const int i = tid + k * T;
-            if (i < n) {
+            if (i < n_own) {
                 R[base + i] = pos[i];
                 R[plane + base + i] = pos[NMAX + i];
                 R[2 * plane + base + i] = pos[2 * NMAX + i];
@@ -250,23 +261,25 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
 }
 
 template <int NMAX, int K>
-hipError_t launch_class(const BatchArgs &a, int n_blocks, hipStream_t s)
+hipError_t launch_class(const BatchArgs &a, int n_max, int n_blocks, hipStream_t s)
 {
     static_assert(64 * ((NMAX + 64 * K - 1) / (64 * K)) <= kBatchMaxThreads, "too many threads for the class");
-    hipLaunchKernelGGL((batch_md_kernel<NMAX, K>), dim3(n_blocks), dim3(batch_threads(a.n)), 0, s, a);
+    hipLaunchKernelGGL((batch_md_kernel<NMAX, K>), dim3(n_blocks), dim3(batch_threads(n_max)), 0, s, a);
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t launch_batch(const BatchArgs &a, int n_blocks, hipStream_t s)
+hipError_t launch_batch(const BatchArgs &a, int n_max, int n_blocks, hipStream_t s)
 {
-    if (a.n <= 0 || a.n > 4096 || n_blocks <= 0) return hipErrorInvalidValue;
-    if (a.n <= 128) return launch_class<128, 1>(a, n_blocks, s);
-    if (a.n <= 512) return launch_class<512, 1>(a, n_blocks, s);
-    if (a.n <= 1024) return launch_class<1024, 1>(a, n_blocks, s);
-    if (a.n <= 2048) return launch_class<2048, 2>(a, n_blocks, s);
-    return launch_class<4096, 4>(a, n_blocks, s);
+    if (n_max <= 0 || n_max > 4096 || n_blocks <= 0) return hipErrorInvalidValue;
+    switch (batch_class(n_max)) {
+    case 0: return launch_class<128, 1>(a, n_max, n_blocks, s);
+    case 1: return launch_class<512, 1>(a, n_max, n_blocks, s);
+    case 2: return launch_class<1024, 1>(a, n_max, n_blocks, s);
+    case 3: return launch_class<2048, 2>(a, n_max, n_blocks, s);
+    default: return launch_class<4096, 4>(a, n_max, n_blocks, s);
+    }
 }
 
 }  // namespace ljmdb

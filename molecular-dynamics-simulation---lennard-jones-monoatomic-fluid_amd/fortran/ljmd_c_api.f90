@@ -21,8 +21,9 @@ module ljmd_c_api
   public :: ljmd_last_error, ljmd_device_count, ljmd_profile_enable, ljmd_profile_read
   public :: ljmd_enqueue_steps, ljmd_enqueue_steps_sampled, ljmd_collect_steps, ljmd_snapshot_begin, ljmd_snapshot_end
   public :: ljmd_check, ljmd_error_text
-  ! batch engine: many independent replicas of one (n, L, dt, rc) on one device (ljmd.h, ljmd_batch_*)
-  public :: ljmd_batch_create, ljmd_batch_destroy, ljmd_batch_last_error, ljmd_batch_set_state, ljmd_batch_set_accel
+  ! batch engine: many independent replicas on one device, of one (n, L, dt, rc) or each with its own (ljmd.h,
+  ! ljmd_batch_*)
+  public :: ljmd_batch_create, ljmd_batch_create_per_replica, ljmd_batch_offsets, ljmd_batch_destroy, ljmd_batch_last_error, ljmd_batch_set_state, ljmd_batch_set_accel
   public :: ljmd_batch_set_unwrapped, ljmd_batch_get_state, ljmd_batch_compute_forces, ljmd_batch_kinetic_energy
   public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_profile_read
   public :: ljmd_batch_check, ljmd_batch_error_text
@@ -216,6 +217,25 @@ module ljmd_c_api
       type(c_ptr), intent(out) :: handle
       integer(c_int32_t), value :: n_replicas, n, precision_mode, device
       real(c_double), value :: box_length, dt, rc
+      integer(c_int) :: status
+    end function
+
+    ! replica b with its own n(b), box_length(b), dt(b), rc(b); per-particle arrays hold the replicas one after another
+    function ljmd_batch_create_per_replica(handle, n_replicas, n, box_length, dt, rc, precision_mode, device) &
+        bind(C, name="ljmd_batch_create_per_replica") result(status)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), intent(out) :: handle
+      integer(c_int32_t), value :: n_replicas, precision_mode, device
+      integer(c_int32_t), intent(in) :: n(*)
+      real(c_double), intent(in) :: box_length(*), dt(*), rc(*)
+      integer(c_int) :: status
+    end function
+
+    ! offsets(b + 1) .. offsets(b + 2) - 1 (0-based elements): replica b's particles in every per-particle array
+    function ljmd_batch_offsets(handle, offsets) bind(C, name="ljmd_batch_offsets") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: offsets(*)
       integer(c_int) :: status
     end function
 

@@ -3,15 +3,19 @@
 ! ONE batch handle of the MI355X engine (include/ljmd.h: ljmd_batch_*): all runs step together, one workgroup per run.
 !
 !   in : inputs/input_simulation_parameters.txt (as md_simulation_gpu)
+!        outputs/run_NNNN/input_simulation_parameters.txt when it exists: that run takes k, dt, L and rc_over_L from
+!        it (a state-point or size sweep in one batch handle, ljmd_batch_create_per_replica); its total_steps,
+!        output_interval and warmup_steps must equal the shared file's, since all runs step in lockstep
 !        outputs/run_NNNN/rv_init.dat when it exists, else the shared outputs/rv_init.dat -- with the shared file every
 !        run is the same trajectory, as in the reference (run_many_md.f90:13-15 warns about it); callers who want
-!        independent runs write one rv_init.dat per run
+!        independent runs write one rv_init.dat per run (a run with its own N needs its own)
 !   out: outputs/run_NNNN/ instantaneous_energies.dat, rva.dat, corr_*.dat, corrmean_*.dat, md_final_results.txt --
 !        the files md_simulation_gpu writes into outputs/one_run/, same formats (module md_stats / md_run_outputs)
 !        outputs/several_runs.txt -- the reference's two header lines, then one directory per run (run_many_md.f90:
 !        30,48-49,74)
 ! Each run is the physics of md_simulation_gpu (the batch engine's contract, ljmd.h); the runs differ from it only by
-! the summation order of the forces.
+! the summation order of the forces.  Every file of a run is byte-identical to what this program writes with
+! LJMD_RUNS=1 and that run's parameters as the shared input.
 ! Environment: LJMD_RUNS (default 10, the reference's n_runs_default, run_many_md.f90:26), LJMD_DEVICE (default 0).
 ! Batches are fp64 only and take n <= LJMD_BATCH_MAX_N.
 !==============================================================================
@@ -28,6 +32,12 @@ program md_simulation_many_gpu
 
   character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
   type(sim_params) :: params
+  type(sim_params), allocatable :: rparams(:)       ! each run's parameters: its own file's or the shared ones
+  logical, allocatable :: own_params(:)
+  integer(kind=8), allocatable :: off(:)            ! run i's particles: elements off(i) + 1 .. off(i + 1)
+  integer(c_int32_t), allocatable :: n_c(:)
+  real(c_double), allocatable :: box_c(:), dt_c(:), rc_c(:), time_run(:)
+  logical :: any_own
   integer(kind=int_kind) :: total_steps, output_interval, warmup_steps, n_snapshots_expected
   real(kind=dp_kind) :: rc_over_L, target_total_energy
   real(kind=dp_kind), allocatable, target :: rx(:), ry(:), rz(:), ux(:), uy(:), uz(:)
@@ -37,10 +47,10 @@ program md_simulation_many_gpu
   integer, allocatable :: iu_rva(:), iu_out(:)
   character(len=64), allocatable :: run_dir(:)
   real(kind=dp_kind) :: time, etot, temp_inst, press_inst
-  integer(kind=int_kind) :: step, k, num_samples, n, rest
+  integer(kind=int_kind) :: step, k, num_samples, n, ni, rest
   integer :: n_runs, i, ios, device, iu
   integer(c_int32_t) :: n_runs_c
-  integer(kind=8) :: c0, c1, crate, o
+  integer(kind=8) :: c0, c1, crate, o, total
   type(c_ptr) :: batch
   character(len=32) :: env
 
@@ -55,21 +65,42 @@ program md_simulation_many_gpu
   call get_environment_variable('LJMD_DEVICE', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) device
 
-  allocate(rx(n * n_runs), ry(n * n_runs), rz(n * n_runs), ux(n * n_runs), uy(n * n_runs), uz(n * n_runs), &
-           vx(n * n_runs), vy(n * n_runs), vz(n * n_runs), ax(n * n_runs), ay(n * n_runs), az(n * n_runs))
+  allocate(rparams(n_runs), own_params(n_runs), off(n_runs + 1), time_run(n_runs))
   allocate(s_epot(n_runs), s_ekin(n_runs), s_depot(n_runs), s_ddepot(n_runs))
   allocate(stats(n_runs), iu_rva(n_runs), iu_out(n_runs), run_dir(n_runs))
 
-  ! run directories (before the GPU is touched) and initial configurations, replica-major: run i at [(i-1) n + 1, i n]
+  ! run directories and parameters (before the GPU is touched); the runs' particles one after another
+  off(1) = 0
   do i = 1, n_runs
     write(run_dir(i), '(a,i4.4)') 'outputs/run_', i
     call execute_command_line('mkdir -p ' // trim(run_dir(i)), exitstat=ios)
     if (ios /= 0) stop 'md_simulation_many: cannot create a run directory under outputs/.'
+    call read_run_parameters(i)
+    off(i + 1) = off(i) + rparams(i)%n
+  end do
+  any_own = any(own_params)
+  total = off(n_runs + 1)
+  allocate(rx(total), ry(total), rz(total), ux(total), uy(total), uz(total), &
+           vx(total), vy(total), vz(total), ax(total), ay(total), az(total))
+  do i = 1, n_runs
     call read_rv_init(i)
   end do
 
-  call ljmd_batch_check(ljmd_batch_create(batch, int(n_runs, c_int32_t), n, params%box_length, params%dt, params%rc, &
-                                          LJMD_PRECISION_FP64, int(device, c_int32_t)), c_null_ptr, 'ljmd_batch_create')
+  if (any_own) then
+    allocate(n_c(n_runs), box_c(n_runs), dt_c(n_runs), rc_c(n_runs))
+    do i = 1, n_runs
+      n_c(i) = int(rparams(i)%n, c_int32_t)
+      box_c(i) = rparams(i)%box_length
+      dt_c(i) = rparams(i)%dt
+      rc_c(i) = rparams(i)%rc
+    end do
+    call ljmd_batch_check(ljmd_batch_create_per_replica(batch, int(n_runs, c_int32_t), n_c, box_c, dt_c, rc_c, &
+                                                        LJMD_PRECISION_FP64, int(device, c_int32_t)), c_null_ptr, &
+                          'ljmd_batch_create_per_replica')
+  else
+    call ljmd_batch_check(ljmd_batch_create(batch, int(n_runs, c_int32_t), n, params%box_length, params%dt, params%rc, &
+                                            LJMD_PRECISION_FP64, int(device, c_int32_t)), c_null_ptr, 'ljmd_batch_create')
+  end if
   n_runs_c = int(n_runs, c_int32_t)
   call ljmd_batch_check(ljmd_batch_set_tail_corrections(batch, merge(1_c_int32_t, 0_c_int32_t, use_tail_corrections)), &
                         batch, 'ljmd_batch_set_tail_corrections')
@@ -80,7 +111,7 @@ program md_simulation_many_gpu
   call ljmd_batch_check(ljmd_batch_compute_forces(batch, c_loc(s_epot), c_loc(s_depot), c_loc(s_ddepot)), batch, &
                         'ljmd_batch_compute_forces')
   call ljmd_batch_check(ljmd_batch_kinetic_energy(batch, c_loc(s_ekin)), batch, 'ljmd_batch_kinetic_energy')
-  time = 0.d0
+  time_run = 0.d0
 
   n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
   if (n_snapshots_expected < 0) n_snapshots_expected = 0
@@ -88,12 +119,12 @@ program md_simulation_many_gpu
     open(newunit=iu_rva(i), file=trim(run_dir(i)) // '/rva.dat', form='unformatted', status='replace', &
          action='write', iostat=ios)
     if (ios /= 0) stop 'md_simulation_many: cannot open rva.dat of a run.'
-    write(iu_rva(i)) params%n, params%box_length, params%dt, output_interval, n_snapshots_expected
+    write(iu_rva(i)) rparams(i)%n, rparams(i)%box_length, rparams(i)%dt, output_interval, n_snapshots_expected
     open(newunit=iu_out(i), file=trim(run_dir(i)) // '/instantaneous_energies.dat', status='replace', &
          action='write', iostat=ios)
     if (ios /= 0) stop 'md_simulation_many: cannot open instantaneous_energies.dat of a run.'
     write(iu_out(i), '(a)') '# time   epot   ekin   etot   T   P'
-    call stats_begin(stats(i), params%n, params%volume, n_snapshots_expected)
+    call stats_begin(stats(i), rparams(i)%n, rparams(i)%volume, n_snapshots_expected)
   end do
 
   num_samples = 0
@@ -104,8 +135,10 @@ program md_simulation_many_gpu
     call ljmd_batch_check(ljmd_batch_steps(batch, int(output_interval, c_int32_t), int(output_interval, c_int32_t), &
                                            c_loc(s_epot), c_loc(s_ekin), c_loc(s_depot), c_loc(s_ddepot)), batch, &
                           'ljmd_batch_steps')
-    do k = 1, output_interval
-      time = time + params%dt                       ! accumulated as at :356
+    do i = 1, n_runs
+      do k = 1, output_interval
+        time_run(i) = time_run(i) + rparams(i)%dt   ! accumulated as at :356, with the run's own dt
+      end do
     end do
     step = step + output_interval
     if (step <= warmup_steps) cycle
@@ -116,12 +149,14 @@ program md_simulation_many_gpu
     do i = 1, n_runs
       call stats_push(stats(i), s_epot(i), s_ekin(i), s_depot(i), s_ddepot(i), temp_inst, press_inst)
       etot = s_epot(i) + s_ekin(i)
+      time = time_run(i)
       write(iu_out(i), '(1pe13.6,5(2x,1pe13.6))') time, s_epot(i), s_ekin(i), etot, temp_inst, press_inst
-      o = int(i - 1, 8) * n
-      write(iu_rva(i)) rx(o + 1:o + n), ry(o + 1:o + n), rz(o + 1:o + n)
-      write(iu_rva(i)) ux(o + 1:o + n), uy(o + 1:o + n), uz(o + 1:o + n)
-      write(iu_rva(i)) vx(o + 1:o + n), vy(o + 1:o + n), vz(o + 1:o + n)
-      write(iu_rva(i)) ax(o + 1:o + n), ay(o + 1:o + n), az(o + 1:o + n)
+      o = off(i)
+      ni = rparams(i)%n
+      write(iu_rva(i)) rx(o + 1:o + ni), ry(o + 1:o + ni), rz(o + 1:o + ni)
+      write(iu_rva(i)) ux(o + 1:o + ni), uy(o + 1:o + ni), uz(o + 1:o + ni)
+      write(iu_rva(i)) vx(o + 1:o + ni), vy(o + 1:o + ni), vz(o + 1:o + ni)
+      write(iu_rva(i)) ax(o + 1:o + ni), ay(o + 1:o + ni), az(o + 1:o + ni)
     end do
   end do
   rest = total_steps - step                         ! the steps after the last sampling instant: nothing is sampled
@@ -140,14 +175,49 @@ program md_simulation_many_gpu
   write(iu, '(a)') '# List of MD run output directories (one per line)'
   write(iu, '(a)') '# Generated by run_many_md.f90'
   do i = 1, n_runs
-    call write_run_statistics(trim(run_dir(i)), params, total_steps, output_interval, warmup_steps, stats(i))
+    call write_run_statistics(trim(run_dir(i)), rparams(i), total_steps, output_interval, warmup_steps, stats(i))
     write(iu, '(a)') trim(run_dir(i))
   end do
   close(iu)
-  write(*, '(a,i0,a,i0,a,i0,a,f12.2,a)') 'md_simulation_many_gpu: N=', params%n, ' runs=', n_runs_c, ' steps=', &
-    total_steps, '  ', dble(n_runs) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' run-steps/s'
+  if (any_own) then
+    write(*, '(a,i0,a,i0,a,i0,a,f12.2,a)') 'md_simulation_many_gpu: particles=', total, ' runs=', n_runs_c, &
+      ' steps=', total_steps, '  ', dble(n_runs) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), &
+      ' run-steps/s'
+  else
+    write(*, '(a,i0,a,i0,a,i0,a,f12.2,a)') 'md_simulation_many_gpu: N=', params%n, ' runs=', n_runs_c, ' steps=', &
+      total_steps, '  ', dble(n_runs) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' run-steps/s'
+  end if
 
 contains
+
+  ! run i's own outputs/run_NNNN/input_simulation_parameters.txt, if any: k, dt, L, rc_over_L of the run; its block 1
+  ! must repeat the shared total_steps, output_interval and warmup_steps
+  subroutine read_run_parameters(irun)
+    integer, intent(in) :: irun
+    character(len=128) :: filename
+    integer(kind=int_kind) :: ts, oi, ws
+    real(kind=dp_kind) :: rcl, tte
+    filename = trim(run_dir(irun)) // '/input_simulation_parameters.txt'
+    inquire(file=trim(filename), exist=own_params(irun))
+    if (.not. own_params(irun)) then
+      rparams(irun) = params
+      return
+    end if
+    call read_simulation_parameters(trim(filename), rparams(irun), ts, oi, ws, rcl, tte)
+    if (ts /= total_steps .or. oi /= output_interval .or. ws /= warmup_steps) then
+      write(*, '(a,a,a)') 'md_simulation_many_gpu: ', trim(filename), ': total_steps, output_interval and '// &
+        'warmup_steps must equal those of inputs/input_simulation_parameters.txt (all runs step together)'
+      stop 'md_simulation_many: a run''s steps block differs from the shared input.'
+    end if
+    if (rparams(irun)%n > LJMD_BATCH_MAX_N) then
+      write(*, '(a,a,a,i0,a,i0,a)') 'md_simulation_many_gpu: ', trim(filename), ': N = ', rparams(irun)%n, &
+        ' exceeds LJMD_BATCH_MAX_N (', LJMD_BATCH_MAX_N, ')'
+      stop 'md_simulation_many: a run''s N is too large for a batch.'
+    end if
+    write(*, '(a,a,a,i0,a,1pe13.6,a,1pe13.6,a,1pe13.6)') 'md_simulation_many_gpu: ', trim(run_dir(irun)), &
+      ' uses its own input_simulation_parameters.txt: N=', rparams(irun)%n, ' L=', rparams(irun)%box_length, &
+      ' dt=', rparams(irun)%dt, ' rc=', rparams(irun)%rc
+  end subroutine read_run_parameters
 
   ! run i's rv_init.dat: record 1 = rx ry rz, record 2 = vx vy vz (md_initial_config_program.f90:285-286)
   subroutine read_rv_init(irun)
@@ -155,19 +225,26 @@ contains
     character(len=128) :: filename
     logical :: own
     integer :: iu_in, ierr
-    integer(kind=8) :: off
+    integer(kind=8) :: o0
+    integer(kind=int_kind) :: ni0
     filename = trim(run_dir(irun)) // '/rv_init.dat'
     inquire(file=trim(filename), exist=own)
     if (.not. own) then
+      if (rparams(irun)%n /= n) then
+        write(*, '(a,a,a)') 'md_simulation_many_gpu: ', trim(run_dir(irun)), &
+          ' has its own N but no rv_init.dat of its own'
+        stop 'read_rv_init(): a run with its own N needs its own rv_init.dat.'
+      end if
       filename = 'outputs/rv_init.dat'
       write(*, '(a,a,a)') 'md_simulation_many_gpu: ', trim(run_dir(irun)), &
         ' starts from the shared outputs/rv_init.dat (identical to every other run that does)'
     end if
     open(newunit=iu_in, file=trim(filename), form='unformatted', status='old', action='read', iostat=ierr)
     if (ierr /= 0) stop 'read_rv_init(): cannot open rv_init file.'
-    off = int(irun - 1, 8) * n
-    read(iu_in) rx(off + 1:off + n), ry(off + 1:off + n), rz(off + 1:off + n)
-    read(iu_in) vx(off + 1:off + n), vy(off + 1:off + n), vz(off + 1:off + n)
+    o0 = off(irun)
+    ni0 = rparams(irun)%n
+    read(iu_in) rx(o0 + 1:o0 + ni0), ry(o0 + 1:o0 + ni0), rz(o0 + 1:o0 + ni0)
+    read(iu_in) vx(o0 + 1:o0 + ni0), vy(o0 + 1:o0 + ni0), vz(o0 + 1:o0 + ni0)
     close(iu_in)
   end subroutine read_rv_init
 

@@ -486,6 +486,74 @@ class BatchEngine:
         self._ck(self._lib.ljmd_batch_profile_read(self._h, C.byref(ms), C.byref(c)))
         return {"kernel_ms": ms.value, "launches": c.value}
 
+    @staticmethod
+    def per_replica(params_list, device: int = 0) -> "PerReplicaBatchEngine":
+        """one handle of len(params_list) replicas, replica b with its own (n, L, dt, rc) = params_list[b]"""
+        return PerReplicaBatchEngine(params_list, device)
+
+
+class PerReplicaBatchEngine(BatchEngine):
+    """BatchEngine whose replicas each have their own SimParams (ljmd_batch_create_per_replica): a sweep over state
+    points or sizes in one handle.  Replica b's results equal those of a one-replica BatchEngine of params_list[b].
+    Per-particle arguments and results are lists of B arrays of shape (n_b,); per-replica scalars stay (B,) and the
+    scalars of steps() (samples, B).  offsets[b] .. offsets[b + 1] is replica b's range in the library's planes."""
+
+    def __init__(self, params_list, device: int = 0):
+        self._lib = _lib.load()
+        self.params_list = list(params_list)
+        self.n_replicas = len(self.params_list)
+        if self.n_replicas < 1:
+            raise ValueError("params_list must hold at least one SimParams")
+        n = np.array([p.n for p in self.params_list], dtype=np.int32)
+        box = np.array([p.box_length for p in self.params_list], dtype=np.float64)
+        dt = np.array([p.dt for p in self.params_list], dtype=np.float64)
+        rc = np.array([p.rc for p in self.params_list], dtype=np.float64)
+        h = C.c_void_p()
+        _lib.check_batch(self._lib.ljmd_batch_create_per_replica(
+            C.byref(h), self.n_replicas, n.ctypes.data_as(_lib.c_int32_p), _ptr(box), _ptr(dt), _ptr(rc),
+            _lib.PRECISION_FP64, device))
+        self._h = h
+        off = np.empty(self.n_replicas + 1, dtype=np.int64)
+        self._ck(self._lib.ljmd_batch_offsets(self._h, off.ctypes.data_as(_lib.c_int64_p)))
+        self.offsets = off
+
+    @property
+    def params(self):
+        return self.params_list
+
+    def _arrays(self, arrs, name: str):
+        """each of arrs: B arrays, replica b's of shape (n_b,) -> one concatenated array per component"""
+        out = []
+        for a in arrs:
+            if isinstance(a, np.ndarray) or len(a) != self.n_replicas:
+                raise ValueError(f"{name} must be a list of {self.n_replicas} arrays (one per replica)")
+            parts = []
+            for b, x in enumerate(a):
+                x = np.ascontiguousarray(x, dtype=np.float64)
+                nb = int(self.offsets[b + 1] - self.offsets[b])
+                if x.shape != (nb,):
+                    raise ValueError(f"{name} of replica {b} must have shape ({nb},), got {x.shape}")
+                parts.append(x)
+            out.append(np.concatenate(parts))
+        return out
+
+    def _split(self, flat: np.ndarray):
+        return [flat[self.offsets[b]:self.offsets[b + 1]] for b in range(self.n_replicas)]
+
+    def get_state(self, which=("r", "ru", "v", "a")) -> dict:
+        """-> {'r': (x, y, z), ...}, each component a list of B arrays (n_b,)"""
+        total = int(self.offsets[-1])
+        out, ptrs = {}, []
+        for key in ("r", "ru", "v", "a"):
+            if key in which:
+                arrs = tuple(np.empty(total, dtype=np.float64) for _ in range(3))
+                out[key] = tuple(self._split(a) for a in arrs)
+                ptrs += [_ptr(a) for a in arrs]
+            else:
+                ptrs += [None, None, None]
+        self._ck(self._lib.ljmd_batch_get_state(self._h, *ptrs))
+        return out
+
 
 def observables(params: SimParams, epot: float, ekin: float, d_epot: float):
     """etot, T, P of one sample: md_simulation_program.f90:355,366 + md_means.f90:215-228.
