@@ -3,19 +3,22 @@
 // with one workgroup per replica.  Handle lifecycle, guards, device state, launch planning per kernel class and the
 // combination of the per-replica step records.
 #include "ljmd_batch.h"
-#include "ljmd_engine.h"
+#include "ljmd_common.h"
 
+#include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <new>
+#include <vector>
 
 using namespace ljmdb;
+using ljmdh::fail;
 
 namespace {
 
 // one replica's parameters and derived constants (host side)
-struct BatchRep {
+struct BatchRep : ljmdh::SimParams {
     int n = 0;
-    double L = 0, invL = 0, rc = 0, rc2 = 0, dt = 0, dt_half = 0, dt_sq_half = 0, volume = 0;
-    double tail_e = 0, tail_d = 0, tail_dd = 0;
 };
 
 // the replicas of one kernel class: entries [first, first + count) of the replica table, launched chunk replicas and
@@ -65,26 +68,6 @@ constexpr double kMinParallel = 256;  // below one replica per CU a launch does 
 // wave over j costs ~30 dependent fp64 instructions, at most ~100 ns; 2e5 iterations of it per launch = <= 20 ms
 constexpr double kLaunchIterations = 2e5;
 
-int bfail(const ljmd_batch *h, int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    ljmdh::fail(nullptr, code, "%s", buf);          // the thread's last error, as the single engine
-    if (h) const_cast<ljmd_batch *>(h)->err = buf;
-    return code;
-}
-
-#define BATCH_HIP(h, call)                                                                                  \
-    do {                                                                                                    \
-        hipError_t e_ = (call);                                                                             \
-        if (e_ != hipSuccess)                                                                               \
-            return bfail((h), LJMD_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, \
-                         __LINE__);                                                                         \
-    } while (0)
-
 double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
 
 BatchArgs base_args(ljmd_batch *h, int mode)
@@ -112,28 +95,11 @@ void launch_shape(int n, size_t count, size_t *chunk, int *steps_per_launch)
     *steps_per_launch = (int)std::max(1.0, std::min({s, s_latency, (double)LJMD_MAX_PENDING_STEPS}));
 }
 
-// a replica's derived constants: compute_derived_params (md_types.f90:137-159), the expressions of ljmd_create
 BatchRep derive(int n, double box_length, double dt, double rc)
 {
     BatchRep r;
+    static_cast<ljmdh::SimParams &>(r) = ljmdh::derive_params(n, box_length, dt, rc);
     r.n = n;
-    r.L = box_length;
-    r.invL = 1.0 / box_length;
-    r.volume = box_length * box_length * box_length;
-    r.rc = rc;
-    r.rc2 = rc * rc;
-    r.dt = dt;
-    r.dt_half = 0.5 * dt;
-    r.dt_sq_half = r.dt_half * dt;
-    {   // tail corrections, lj_potential_energy.f90:205-223
-        const double npd = (double)n;
-        const double rc3 = (rc * rc) * rc;
-        const double rc6 = ((rc * rc) * (rc * rc)) * (rc * rc);
-        const double tf = 8.0 * ljmdh::kPi * (npd * npd) / (r.volume * rc3);
-        r.tail_e = tf * ((1.0 / (3.0 * rc6)) - 1.0) / 3.0;
-        r.tail_d = 2.0 * tf * (-2.0 / (3.0 * rc6) + 1.0);
-        r.tail_dd = 2.0 * tf * (26.0 / (3.0 * rc6) - 7.0);
-    }
     return r;
 }
 
@@ -147,7 +113,7 @@ int ensure_records(ljmd_batch *h, size_t samples)
     const size_t bytes = samples * h->B * kBatchRecWords * sizeof(double);
     if (hipMalloc(&h->d_rec, bytes) != hipSuccess) {
         h->d_rec = nullptr;
-        return bfail(h, LJMD_ERR_ALLOC, "ljmd_batch: cannot allocate %zu bytes of step records", bytes);
+        return fail(h, LJMD_ERR_ALLOC, "ljmd_batch: cannot allocate %zu bytes of step records", bytes);
     }
     h->rec_cap = samples;
     return LJMD_OK;
@@ -162,27 +128,23 @@ int fetch_records(ljmd_batch *h, size_t samples)
     const hipError_t s = e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
     if (s != hipSuccess) {
         h->poisoned = true;
-        return bfail(h, LJMD_ERR_HIP, "ljmd_batch: kernel or copy failed: %s; the handle is poisoned until "
+        return fail(h, LJMD_ERR_HIP, "ljmd_batch: kernel or copy failed: %s; the handle is poisoned until "
                                       "ljmd_batch_set_state", hipGetErrorString(s));
     }
     return LJMD_OK;
 }
 
-// as combine_one (ljmd_capi.cpp) for replica b's record: the kernel already halved the ordered-pair sums
+// as combine_one (ljmd_records.cpp) for replica b's record: the kernel already halved the ordered-pair sums
 void combine(const ljmd_batch *h, size_t b, const double *r, double *epot, double *ekin, double *d_epot, double *dd_epot)
 {
-    const double s12 = r[0], s6 = r[1], kx = r[2], ky = r[3], kz = r[4];
     const BatchRep &p = h->rep[b];
     const double te = h->tail_on ? p.tail_e : 0.0, td = h->tail_on ? p.tail_d : 0.0, tdd = h->tail_on ? p.tail_dd : 0.0;
-    if (epot) *epot = 4.0 * (s12 - s6) + te;
-    if (d_epot) *d_epot = 24.0 * (-2.0 * s12 + s6) + td;
-    if (dd_epot) *dd_epot = 24.0 * (26.0 * s12 - 7.0 * s6) + tdd;
-    if (ekin) *ekin = 0.5 * (kx + ky + kz);
+    ljmdh::scalars_from_sums(r[0], r[1], r[2], r[3], r[4], te, td, tdd, epot, ekin, d_epot, dd_epot);
 }
 
 int upload(ljmd_batch *h, int which, int axis, const double *src)
 {
-    BATCH_HIP(h, hipMemcpyAsync(plane(h, which, axis), src, h->total * sizeof(double), hipMemcpyHostToDevice,
+    LJMD_HIP(h, hipMemcpyAsync(plane(h, which, axis), src, h->total * sizeof(double), hipMemcpyHostToDevice,
                                 h->stream));
     return LJMD_OK;
 }
@@ -194,8 +156,8 @@ int upload(ljmd_batch *h, int which, int axis, const double *src)
 int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const char *who)
 {
     if (h->concurrent) {
-        BATCH_HIP(h, hipEventRecord(h->fork, h->stream));
-        for (const BatchGroup &g : h->groups) BATCH_HIP(h, hipStreamWaitEvent(g.stream, h->fork, 0));
+        LJMD_HIP(h, hipEventRecord(h->fork, h->stream));
+        for (const BatchGroup &g : h->groups) LJMD_HIP(h, hipStreamWaitEvent(g.stream, h->fork, 0));
     }
     const bool steps = a.mode == kModeSteps;
     int32_t count = 0;
@@ -212,29 +174,18 @@ int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const 
                 if (e != hipSuccess) {
                     h->poisoned = true;
                     if (steps)
-                        return bfail(h, LJMD_ERR_HIP, "%s: launch at step %d failed: %s; the handle is poisoned until "
+                        return fail(h, LJMD_ERR_HIP, "%s: launch at step %d failed: %s; the handle is poisoned until "
                                                       "ljmd_batch_set_state", who, s0, hipGetErrorString(e));
-                    return bfail(h, LJMD_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+                    return fail(h, LJMD_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
                 }
             }
         }
         if (h->concurrent) {
-            BATCH_HIP(h, hipEventRecord(g.done, s));
-            BATCH_HIP(h, hipStreamWaitEvent(h->stream, g.done, 0));
+            LJMD_HIP(h, hipEventRecord(g.done, s));
+            LJMD_HIP(h, hipStreamWaitEvent(h->stream, g.done, 0));
         }
     }
     if (launches) *launches = count;
-    return LJMD_OK;
-}
-
-// the device probe, after the caller's guards
-int probe(int32_t device, const char *who)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return bfail(nullptr, LJMD_ERR_NO_DEVICE, "%s: no HIP device available (this library has no CPU path)", who);
-    if (device < 0 || device >= ndev)
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: device %d out of range (0..%d)", who, device, ndev - 1);
     return LJMD_OK;
 }
 
@@ -242,89 +193,81 @@ int probe(int32_t device, const char *who)
 int create_handle(ljmd_batch_t **out, std::vector<BatchRep> &&reps, int32_t device, const char *who)
 {
     ljmd_batch *h = new (std::nothrow) ljmd_batch;
-    if (!h) return bfail(nullptr, LJMD_ERR_ALLOC, "%s: out of host memory", who);
-    auto undo = [&](int code) {
+    if (!h) return fail(nullptr, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+    auto body = [&]() -> int {
+        h->B = reps.size();
+        h->device = device;
+        std::vector<BatchReplica> table;
+        try {
+            h->rep = std::move(reps);
+            h->offsets.resize(h->B + 1);
+            table.reserve(h->B);
+        } catch (const std::bad_alloc &) {
+            return fail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+        }
+        h->offsets[0] = 0;
+        for (size_t b = 0; b < h->B; ++b) h->offsets[b + 1] = h->offsets[b] + h->rep[b].n;
+        h->total = (size_t)h->offsets[h->B];
+        // the replica table, grouped by kernel class; replica order inside a group
+        for (int c = 0; c < kBatchClasses; ++c) {
+            BatchGroup g;
+            g.first = table.size();
+            for (size_t b = 0; b < h->B; ++b) {
+                const BatchRep &p = h->rep[b];
+                if (batch_class(p.n) != c) continue;
+                BatchReplica e{};
+                e.off = (size_t)h->offsets[b];
+                e.b = (int)b;
+                e.n = p.n;
+                e.threads = batch_threads(p.n);
+                e.L = p.L;
+                e.invL = p.invL;
+                e.rc2 = p.rc2;
+                e.dt = p.dt;
+                e.dt_half = p.dt_half;
+                e.dt_sq_half = p.dt_sq_half;
+                table.push_back(e);
+                g.n_max = std::max(g.n_max, p.n);
+            }
+            g.count = table.size() - g.first;
+            if (g.count == 0) continue;
+            launch_shape(g.n_max, g.count, &g.chunk, &g.steps_per_launch);
+            h->groups.push_back(g);
+        }
+        // several groups run concurrently unless LJMD_BATCH_GROUP_STREAMS=0 (one after another on the handle's stream)
+        h->concurrent = h->groups.size() > 1 && ljmdh::read_knobs().batch_group_streams;
+        if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreate(&h->ev[0]) != hipSuccess || hipEventCreate(&h->ev[1]) != hipSuccess)
+            return fail(h, LJMD_ERR_HIP, "%s: cannot create the stream on device %d", who, device);
+        if (h->concurrent) {
+            bool ok = hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) == hipSuccess;
+            for (BatchGroup &g : h->groups)
+                ok = ok && hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking) == hipSuccess &&
+                     hipEventCreateWithFlags(&g.done, hipEventDisableTiming) == hipSuccess;
+            if (!ok) return fail(h, LJMD_ERR_HIP, "%s: cannot create the group streams on device %d", who, device);
+        }
+        const size_t bytes = 12 * h->total * sizeof(double);
+        if (hipMalloc(&h->d_state, bytes) != hipSuccess) {
+            h->d_state = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of replica state", who, bytes);
+        }
+        const size_t tbytes = h->B * sizeof(BatchReplica);
+        if (hipMalloc(&h->d_table, tbytes) != hipSuccess) {
+            h->d_table = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of the replica table", who, tbytes);
+        }
+        if (hipMemcpyAsync(h->d_table, table.data(), tbytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess)
+            return fail(h, LJMD_ERR_HIP, "%s: cannot upload the replica table", who);
+        return ensure_records(h, 1);
+    };
+    const int rc_ = body();
+    if (rc_ != LJMD_OK) {                  // one release on failure; the message outlives the handle
         const std::string msg = h->err;
         ljmd_batch_destroy(h);
         ljmdh::g_last_error = msg;
-        return code;
-    };
-    h->B = reps.size();
-    h->device = device;
-    std::vector<BatchReplica> table;
-    try {
-        h->rep = std::move(reps);
-        h->offsets.resize(h->B + 1);
-        table.reserve(h->B);
-    } catch (const std::bad_alloc &) {
-        bfail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
-        return undo(LJMD_ERR_ALLOC);
+        return rc_;
     }
-    h->offsets[0] = 0;
-    for (size_t b = 0; b < h->B; ++b) h->offsets[b + 1] = h->offsets[b] + h->rep[b].n;
-    h->total = (size_t)h->offsets[h->B];
-    // the replica table, grouped by kernel class; replica order inside a group
-    for (int c = 0; c < kBatchClasses; ++c) {
-        BatchGroup g;
-        g.first = table.size();
-        for (size_t b = 0; b < h->B; ++b) {
-            const BatchRep &p = h->rep[b];
-            if (batch_class(p.n) != c) continue;
-            BatchReplica e{};
-            e.off = (size_t)h->offsets[b];
-            e.b = (int)b;
-            e.n = p.n;
-            e.threads = batch_threads(p.n);
-            e.L = p.L;
-            e.invL = p.invL;
-            e.rc2 = p.rc2;
-            e.dt = p.dt;
-            e.dt_half = p.dt_half;
-            e.dt_sq_half = p.dt_sq_half;
-            table.push_back(e);
-            g.n_max = std::max(g.n_max, p.n);
-        }
-        g.count = table.size() - g.first;
-        if (g.count == 0) continue;
-        launch_shape(g.n_max, g.count, &g.chunk, &g.steps_per_launch);
-        h->groups.push_back(g);
-    }
-    // several groups run concurrently unless LJMD_BATCH_GROUP_STREAMS=0 (one after another on the handle's stream)
-    const char *env = std::getenv("LJMD_BATCH_GROUP_STREAMS");
-    h->concurrent = h->groups.size() > 1 && !(env && std::strcmp(env, "0") == 0);
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&h->ev[0]) != hipSuccess || hipEventCreate(&h->ev[1]) != hipSuccess) {
-        bfail(h, LJMD_ERR_HIP, "%s: cannot create the stream on device %d", who, device);
-        return undo(LJMD_ERR_HIP);
-    }
-    if (h->concurrent) {
-        bool ok = hipEventCreateWithFlags(&h->fork, hipEventDisableTiming) == hipSuccess;
-        for (BatchGroup &g : h->groups)
-            ok = ok && hipStreamCreateWithFlags(&g.stream, hipStreamNonBlocking) == hipSuccess &&
-                 hipEventCreateWithFlags(&g.done, hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            bfail(h, LJMD_ERR_HIP, "%s: cannot create the group streams on device %d", who, device);
-            return undo(LJMD_ERR_HIP);
-        }
-    }
-    const size_t bytes = 12 * h->total * sizeof(double);
-    if (hipMalloc(&h->d_state, bytes) != hipSuccess) {
-        h->d_state = nullptr;
-        bfail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of replica state", who, bytes);
-        return undo(LJMD_ERR_ALLOC);
-    }
-    const size_t tbytes = h->B * sizeof(BatchReplica);
-    if (hipMalloc(&h->d_table, tbytes) != hipSuccess) {
-        h->d_table = nullptr;
-        bfail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of the replica table", who, tbytes);
-        return undo(LJMD_ERR_ALLOC);
-    }
-    if (hipMemcpyAsync(h->d_table, table.data(), tbytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess) {
-        bfail(h, LJMD_ERR_HIP, "%s: cannot upload the replica table", who);
-        return undo(LJMD_ERR_HIP);
-    }
-    if (ensure_records(h, 1) != LJMD_OK) return undo(LJMD_ERR_ALLOC);
     *out = h;
     return LJMD_OK;
 }
@@ -338,32 +281,27 @@ const char *ljmd_batch_last_error(const ljmd_batch_t *h) { return h ? h->err.c_s
 int ljmd_batch_create(ljmd_batch_t **out, int32_t n_replicas, int32_t n, double box_length, double dt, double rc,
                       int32_t precision_mode, int32_t device)
 {
-    if (!out) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: out is NULL");
+    if (!out) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: out is NULL");
     *out = nullptr;
     // the guards of ljmd_create (md_types.f90:143-161), then the batch engine's own
-    if (n <= 0) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: n must be > 0");
-    if (!(box_length > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: box_length must be > 0");
-    if (!(rc > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: rc must be > 0");
-    if (rc >= 0.5 * box_length)
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: rc must be < L/2 (minimum image convention)");
-    if (!(dt > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: dt must be > 0");
-    if (n_replicas < 1) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: n_replicas must be >= 1");
+    LJMD_TRY(ljmdh::check_sim_params("ljmd_batch_create", n, box_length, dt, rc));
+    if (n_replicas < 1) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: n_replicas must be >= 1");
     if (n > LJMD_BATCH_MAX_N)
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: n must be <= LJMD_BATCH_MAX_N (%d)",
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: n must be <= LJMD_BATCH_MAX_N (%d)",
                      LJMD_BATCH_MAX_N);
     if (precision_mode != LJMD_PRECISION_FP64)
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: precision_mode %d not available for batches "
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: precision_mode %d not available for batches "
                                                     "(LJMD_PRECISION_FP64 only)", precision_mode);
     if (!(rc <= (1.0 - 1e-9) * 0.5 * box_length))
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: rc must be <= (1 - 1e-9) L/2 (fast-path "
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_create: rc must be <= (1 - 1e-9) L/2 (fast-path "
                                                     "precondition; batches have no generic kernel)");
-    const int rc_ = probe(device, "ljmd_batch_create");
+    const int rc_ = ljmdh::probe_device(device, "ljmd_batch_create");
     if (rc_ != LJMD_OK) return rc_;
     std::vector<BatchRep> reps;
     try {
         reps.assign((size_t)n_replicas, derive(n, box_length, dt, rc));
     } catch (const std::bad_alloc &) {
-        return bfail(nullptr, LJMD_ERR_ALLOC, "ljmd_batch_create: out of host memory");
+        return fail(nullptr, LJMD_ERR_ALLOC, "ljmd_batch_create: out of host memory");
     }
     return create_handle(out, std::move(reps), device, "ljmd_batch_create");
 }
@@ -372,47 +310,47 @@ int ljmd_batch_create_per_replica(ljmd_batch_t **out, int32_t n_replicas, const 
                                   const double *dt, const double *rc, int32_t precision_mode, int32_t device)
 {
     static const char *who = "ljmd_batch_create_per_replica";
-    if (!out) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: out is NULL", who);
+    if (!out) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: out is NULL", who);
     *out = nullptr;
-    if (n_replicas < 1) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: n_replicas must be >= 1", who);
+    if (n_replicas < 1) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: n_replicas must be >= 1", who);
     if (!n || !box_length || !dt || !rc)
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: n, box_length, dt and rc must not be NULL", who);
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: n, box_length, dt and rc must not be NULL", who);
     if (precision_mode != LJMD_PRECISION_FP64)
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: precision_mode %d not available for batches "
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: precision_mode %d not available for batches "
                                                     "(LJMD_PRECISION_FP64 only)", who, precision_mode);
     // every replica passes the guards of ljmd_batch_create
     int64_t total = 0;
     for (int32_t b = 0; b < n_replicas; ++b) {
         const double L = box_length[b];
         if (n[b] <= 0 || n[b] > LJMD_BATCH_MAX_N)
-            return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: n = %d outside 1..LJMD_BATCH_MAX_N (%d)", who,
+            return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: n = %d outside 1..LJMD_BATCH_MAX_N (%d)", who,
                          b, n[b], LJMD_BATCH_MAX_N);
-        if (!(L > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: box_length must be > 0", who, b);
-        if (!(dt[b] > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: dt must be > 0", who, b);
-        if (!(rc[b] > 0.0)) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: rc must be > 0", who, b);
+        if (!(L > 0.0)) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: box_length must be > 0", who, b);
+        if (!(dt[b] > 0.0)) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: dt must be > 0", who, b);
+        if (!(rc[b] > 0.0)) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: rc must be > 0", who, b);
         if (!(rc[b] <= (1.0 - 1e-9) * 0.5 * L))
-            return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: rc must be <= (1 - 1e-9) L/2 (fast-path "
+            return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: replica %d: rc must be <= (1 - 1e-9) L/2 (fast-path "
                                                         "precondition; batches have no generic kernel)", who, b);
         total += n[b];
     }
     if (total >= ((int64_t)1 << 31))
-        return bfail(nullptr, LJMD_ERR_INVALID_ARG, "%s: %lld particles in all; the sum of n must be < 2^31", who,
+        return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: %lld particles in all; the sum of n must be < 2^31", who,
                      (long long)total);
-    const int rc_ = probe(device, who);
+    const int rc_ = ljmdh::probe_device(device, who);
     if (rc_ != LJMD_OK) return rc_;
     std::vector<BatchRep> reps;
     try {
         reps.reserve((size_t)n_replicas);
         for (int32_t b = 0; b < n_replicas; ++b) reps.push_back(derive(n[b], box_length[b], dt[b], rc[b]));
     } catch (const std::bad_alloc &) {
-        return bfail(nullptr, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+        return fail(nullptr, LJMD_ERR_ALLOC, "%s: out of host memory", who);
     }
     return create_handle(out, std::move(reps), device, who);
 }
 
 int ljmd_batch_offsets(const ljmd_batch_t *h, int64_t *offsets)
 {
-    if (!h || !offsets) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_offsets: NULL argument");
+    if (!h || !offsets) return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_offsets: NULL argument");
     std::copy(h->offsets.begin(), h->offsets.end(), offsets);
     return LJMD_OK;
 }
@@ -441,8 +379,8 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
 int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, const double *rz, const double *vx,
                          const double *vy, const double *vz)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: NULL handle");
-    if (!rx || !ry || !rz || !vx || !vy || !vz) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: NULL array");
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: NULL handle");
+    if (!rx || !ry || !rz || !vx || !vy || !vz) return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: NULL array");
     // fast-path precondition (a), ljmd_kernels.hip: per replica and axis, finite coordinates spanning < 2.4 L_b
     const double *src[3] = {rx, ry, rz};
     for (size_t b = 0; b < h->B; ++b)
@@ -453,13 +391,13 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
                 lo = std::min(lo, p[i]);
                 hi = std::max(hi, p[i]);
                 if (!std::isfinite(p[i]))
-                    return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: replica %zu has a non-finite position", b);
+                    return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: replica %zu has a non-finite position", b);
             }
             if (!(hi - lo < 2.4 * h->rep[b].L))
-                return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: replica %zu spans >= 2.4 L along axis %d "
+                return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_state: replica %zu spans >= 2.4 L along axis %d "
                                                       "(wrap the positions first)", b, ax);
         }
-    BATCH_HIP(h, hipSetDevice(h->device));
+    LJMD_HIP(h, hipSetDevice(h->device));
     if (h->poisoned) {
         (void)hipStreamSynchronize(h->stream);   // drain what a failed call left behind
         for (const BatchGroup &g : h->groups)
@@ -474,8 +412,8 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
         if (rc_ == LJMD_OK) rc_ = upload(h, LJMD_V, ax, vs[ax]);
         if (rc_ != LJMD_OK) return rc_;
     }
-    BATCH_HIP(h, hipMemsetAsync(plane(h, LJMD_A, 0), 0, 3 * h->total * sizeof(double), h->stream));
-    BATCH_HIP(h, hipStreamSynchronize(h->stream));
+    LJMD_HIP(h, hipMemsetAsync(plane(h, LJMD_A, 0), 0, 3 * h->total * sizeof(double), h->stream));
+    LJMD_HIP(h, hipStreamSynchronize(h->stream));
     h->have_state = true;
     h->have_accel = false;
     return LJMD_OK;
@@ -483,63 +421,63 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
 
 int ljmd_batch_set_accel(ljmd_batch_t *h, const double *ax, const double *ay, const double *az)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_accel: NULL handle");
-    if (!h->have_state) return bfail(h, LJMD_ERR_STATE, "ljmd_batch_set_accel: call ljmd_batch_set_state first");
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_accel: NULL handle");
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "ljmd_batch_set_accel: call ljmd_batch_set_state first");
     // NULL keeps a component, which is only valid accelerations once there are some: right after set_state every
     // component must be given
     if (!h->have_accel && !(ax && ay && az))
-        return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_accel: no valid accelerations to keep; pass all three "
+        return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_accel: no valid accelerations to keep; pass all three "
                                               "components (or call ljmd_batch_compute_forces)");
-    BATCH_HIP(h, hipSetDevice(h->device));
+    LJMD_HIP(h, hipSetDevice(h->device));
     const double *src[3] = {ax, ay, az};
     for (int k = 0; k < 3; ++k)
         if (src[k]) {
             const int rc_ = upload(h, LJMD_A, k, src[k]);
             if (rc_ != LJMD_OK) return rc_;
         }
-    BATCH_HIP(h, hipStreamSynchronize(h->stream));
+    LJMD_HIP(h, hipStreamSynchronize(h->stream));
     h->have_accel = true;
     return LJMD_OK;
 }
 
 int ljmd_batch_set_unwrapped(ljmd_batch_t *h, const double *ux, const double *uy, const double *uz)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_unwrapped: NULL handle");
-    if (!ux || !uy || !uz) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_unwrapped: NULL array");
-    if (!h->have_state) return bfail(h, LJMD_ERR_STATE, "ljmd_batch_set_unwrapped: call ljmd_batch_set_state first");
-    BATCH_HIP(h, hipSetDevice(h->device));
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_unwrapped: NULL handle");
+    if (!ux || !uy || !uz) return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_unwrapped: NULL array");
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "ljmd_batch_set_unwrapped: call ljmd_batch_set_state first");
+    LJMD_HIP(h, hipSetDevice(h->device));
     const double *src[3] = {ux, uy, uz};
     for (int k = 0; k < 3; ++k) {
         const int rc_ = upload(h, LJMD_RU, k, src[k]);
         if (rc_ != LJMD_OK) return rc_;
     }
-    BATCH_HIP(h, hipStreamSynchronize(h->stream));
+    LJMD_HIP(h, hipStreamSynchronize(h->stream));
     return LJMD_OK;
 }
 
 int ljmd_batch_get_state(ljmd_batch_t *h, double *rx, double *ry, double *rz, double *ux, double *uy, double *uz,
                          double *vx, double *vy, double *vz, double *ax, double *ay, double *az)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_get_state: NULL handle");
-    if (!h->have_state) return bfail(h, LJMD_ERR_STATE, "ljmd_batch_get_state: no state has been set");
-    BATCH_HIP(h, hipSetDevice(h->device));
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_get_state: NULL handle");
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "ljmd_batch_get_state: no state has been set");
+    LJMD_HIP(h, hipSetDevice(h->device));
     double *const dst[12] = {rx, ry, rz, ux, uy, uz, vx, vy, vz, ax, ay, az};
     for (int k = 0; k < 12; ++k)
         if (dst[k])
-            BATCH_HIP(h, hipMemcpyAsync(dst[k], plane(h, k / 3, k % 3), h->total * sizeof(double),
+            LJMD_HIP(h, hipMemcpyAsync(dst[k], plane(h, k / 3, k % 3), h->total * sizeof(double),
                                         hipMemcpyDeviceToHost, h->stream));
-    BATCH_HIP(h, hipStreamSynchronize(h->stream));
+    LJMD_HIP(h, hipStreamSynchronize(h->stream));
     return LJMD_OK;
 }
 
 int ljmd_batch_compute_forces(ljmd_batch_t *h, double *epot, double *d_epot, double *dd_epot)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_compute_forces: NULL handle");
-    if (!h->have_state) return bfail(h, LJMD_ERR_STATE, "ljmd_batch_compute_forces: no state has been set");
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_compute_forces: NULL handle");
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "ljmd_batch_compute_forces: no state has been set");
     if (h->poisoned)
-        return bfail(h, LJMD_ERR_STATE, "ljmd_batch_compute_forces: handle poisoned by an earlier failure; call "
+        return fail(h, LJMD_ERR_STATE, "ljmd_batch_compute_forces: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
-    BATCH_HIP(h, hipSetDevice(h->device));
+    LJMD_HIP(h, hipSetDevice(h->device));
     int rc_ = run_groups(h, base_args(h, kModeForces), 0, nullptr, "ljmd_batch_compute_forces");
     if (rc_ != LJMD_OK) return rc_;
     rc_ = fetch_records(h, 1);
@@ -553,12 +491,12 @@ int ljmd_batch_compute_forces(ljmd_batch_t *h, double *epot, double *d_epot, dou
 
 int ljmd_batch_kinetic_energy(ljmd_batch_t *h, double *ekin)
 {
-    if (!h || !ekin) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_kinetic_energy: NULL argument");
-    if (!h->have_state) return bfail(h, LJMD_ERR_STATE, "ljmd_batch_kinetic_energy: no state has been set");
+    if (!h || !ekin) return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_kinetic_energy: NULL argument");
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "ljmd_batch_kinetic_energy: no state has been set");
     if (h->poisoned)
-        return bfail(h, LJMD_ERR_STATE, "ljmd_batch_kinetic_energy: handle poisoned by an earlier failure; call "
+        return fail(h, LJMD_ERR_STATE, "ljmd_batch_kinetic_energy: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
-    BATCH_HIP(h, hipSetDevice(h->device));
+    LJMD_HIP(h, hipSetDevice(h->device));
     int rc_ = run_groups(h, base_args(h, kModeKinetic), 0, nullptr, "ljmd_batch_kinetic_energy");
     if (rc_ != LJMD_OK) return rc_;
     rc_ = fetch_records(h, 1);
@@ -570,41 +508,41 @@ int ljmd_batch_kinetic_energy(ljmd_batch_t *h, double *ekin)
 int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, double *epot, double *ekin,
                      double *d_epot, double *dd_epot)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: NULL handle");
-    if (nsteps < 0) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: nsteps < 0");
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: NULL handle");
+    if (nsteps < 0) return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: nsteps < 0");
     const bool sampling = epot || ekin || d_epot || dd_epot;
     if (sampling) {
-        if (sample_every < 1) return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: sample_every must be >= 1");
+        if (sample_every < 1) return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: sample_every must be >= 1");
         if (nsteps % sample_every != 0)
-            return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: nsteps %d is not a multiple of sample_every %d",
+            return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: nsteps %d is not a multiple of sample_every %d",
                          nsteps, sample_every);
         if (nsteps / sample_every > LJMD_MAX_PENDING_STEPS)
-            return bfail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: %d samples exceed LJMD_MAX_PENDING_STEPS",
+            return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: %d samples exceed LJMD_MAX_PENDING_STEPS",
                          nsteps / sample_every);
     }
-    if (!h->have_state) return bfail(h, LJMD_ERR_STATE, "ljmd_batch_steps: no state has been set");
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "ljmd_batch_steps: no state has been set");
     if (!h->have_accel)
-        return bfail(h, LJMD_ERR_STATE, "ljmd_batch_steps: no valid accelerations; call ljmd_batch_compute_forces or "
+        return fail(h, LJMD_ERR_STATE, "ljmd_batch_steps: no valid accelerations; call ljmd_batch_compute_forces or "
                                         "ljmd_batch_set_accel first");
     if (h->poisoned)
-        return bfail(h, LJMD_ERR_STATE, "ljmd_batch_steps: handle poisoned by an earlier failure; call "
+        return fail(h, LJMD_ERR_STATE, "ljmd_batch_steps: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
     if (nsteps == 0) return LJMD_OK;
-    BATCH_HIP(h, hipSetDevice(h->device));
+    LJMD_HIP(h, hipSetDevice(h->device));
     const size_t samples = sampling ? (size_t)(nsteps / sample_every) : 0;
     int rc_ = ensure_records(h, samples);
     if (rc_ != LJMD_OK) return rc_;
     BatchArgs a = base_args(h, kModeSteps);
     a.sample_every = sampling ? sample_every : 0;
     int32_t launches = 0;
-    BATCH_HIP(h, hipEventRecord(h->ev[0], h->stream));
+    LJMD_HIP(h, hipEventRecord(h->ev[0], h->stream));
     rc_ = run_groups(h, a, nsteps, &launches, "ljmd_batch_steps");
     if (rc_ != LJMD_OK) return rc_;
-    BATCH_HIP(h, hipEventRecord(h->ev[1], h->stream));
+    LJMD_HIP(h, hipEventRecord(h->ev[1], h->stream));
     rc_ = fetch_records(h, samples);
     if (rc_ != LJMD_OK) return rc_;
     float ms = 0.0f;
-    BATCH_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    LJMD_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
     h->last_ms = ms;
     h->last_launches = launches;
     for (size_t s = 0; s < samples; ++s)
@@ -618,14 +556,14 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
 
 int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_tail_corrections: NULL handle");
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_tail_corrections: NULL handle");
     h->tail_on = on != 0;
     return LJMD_OK;
 }
 
 int ljmd_batch_profile_read(const ljmd_batch_t *h, double *kernel_ms, int32_t *launches)
 {
-    if (!h) return bfail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_profile_read: NULL handle");
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_profile_read: NULL handle");
     if (kernel_ms) *kernel_ms = h->last_ms;
     if (launches) *launches = h->last_launches;
     return LJMD_OK;

@@ -296,7 +296,7 @@ hipError_t launch_iota(int *idx, int P, hipStream_t s);
 hipError_t kd_level(void *temp, size_t temp_bytes, const double *coord_axis, double L, unsigned long long *keys,
                     unsigned long long *keys_out, int *idx, int *idx_out, int S, int nseg, const int *seg_offsets,
                     hipStream_t s);
-// ownership migration of a multi-GPU run (ljmd_sort.hip; ljmd_capi.cpp: migrate_pack / migrate_deal)
+// ownership migration of a multi-GPU run (ljmd_sort.hip; ljmd_migrate.cpp: migrate_pack / migrate_deal)
 constexpr int kMigrateRows = 10;            // doubles per slot in the migration buffer: ru, v, a (3 each) + the particle id
 hipError_t launch_iota_blocked(int *idx, int n, int S, int P, hipStream_t s);
 hipError_t launch_iota_offset(int *idx, int count, int P, int offset, hipStream_t s);

@@ -72,7 +72,7 @@ __device__ __forceinline__ void block_sum(double (&v)[NVAL], double *lds /* [NVA
 // except that it accumulates the linear sums s12 = sum u^6, s6 = sum u^3 instead of
 // epot / d_epot / dd_epot separately.  Full matrix (each ordered pair), one thread per
 // row, j broadcast through scalar loads.  Used when the fast path's preconditions do
-// not hold (ljmd_capi.cpp: fast_path_ok).
+// not hold (ljmd_engine.cpp: fast_path_ok).
 // ===========================================================================
 __global__ __launch_bounds__(kBlock) void pair_rows_generic_kernel(PairArgs a)
 {

@@ -16,7 +16,7 @@
 //   owner, host -> device by every reader) -- needs neither RCCL nor peer access: the last rung of bench.py's ladder.
 // Every exchange runs on a per-rank COMMUNICATION stream, fenced against the rank's engine stream by events, so that the
 // position exchange overlaps the velocity half-kick of K1 (verlet.f90:72-74 reads a(t) and v only; the positions are final
-// at :58-63) exactly as in the one-process-per-GPU form (ljmd_capi.cpp: enqueue_drift); LJMD_OVERLAP_EXCHANGE=0 puts
+// at :58-63) exactly as in the one-process-per-GPU form (ljmd_engine.cpp: enqueue_drift); LJMD_OVERLAP_EXCHANGE=0 puts
 // everything back on the engine streams.
 // The per-step scalar records stay on the devices; they are read back once per batch and combined on the host
 // in rank order (combine_one), exactly as the multi-process path does.
@@ -75,12 +75,6 @@ namespace ljmdm {
 
 namespace {
 
-#define LJMD_TRY(expr)                      \
-    do {                                    \
-        const int rc__ = (expr);            \
-        if (rc__ != LJMD_OK) return rc__;   \
-    } while (0)
-
 // a child's error text becomes the parent's
 int child_failed(ljmd_t *h, const ljmd_t *c, int code)
 {
@@ -107,7 +101,7 @@ int nccl_failed(ljmd_t *h, const char *what, ncclResult_t r)
     return fail(h, LJMD_ERR_HIP, "multi-device %s failed: %s", what, ncclGetErrorString(r));
 }
 
-bool exchanges(const ljmd_multi *m) { return m->G > 1 || m->eng[0]->force_collectives; }
+bool exchanges(const ljmd_multi *m) { return m->G > 1 || m->eng[0]->knobs.force_collectives; }
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The two exchanges, rank by rank.  Every function below is called with rank g's device current and reports errors on
@@ -129,7 +123,7 @@ int pos_prepare(ljmd_multi *m, int g, EventSet *q)
     LJMD_HIP(e, hipStreamWaitEvent(m->xs[g], m->ev_pos[g], 0));
     if (q) LJMD_HIP(e, hipEventRecord(q->e[5], m->xs[g]));
     if (m->xmode == kHost) {
-        LJMD_HIP(e, hipMemcpyAsync(m->h_xpos[g], own_block(e), 3 * (size_t)e->P * sizeof(double), hipMemcpyDeviceToHost,
+        LJMD_HIP(e, hipMemcpyAsync(m->h_xpos[g], own_block(e), 3 * (size_t)e->plan.P * sizeof(double), hipMemcpyDeviceToHost,
                                    m->xs[g]));
         LJMD_HIP(e, hipEventRecord(m->ev_hpos[g], m->xs[g]));
     }
@@ -140,7 +134,7 @@ int pos_prepare(ljmd_multi *m, int g, EventSet *q)
 int pos_collect(ljmd_multi *m, int d)
 {
     ljmd_t *dst = m->eng[d];
-    const size_t blk = 3 * (size_t)dst->P;
+    const size_t blk = 3 * (size_t)dst->plan.P;
     if (m->xmode == kRccl) {
         const ncclResult_t r = ncclAllGather(own_block(dst), dst->d_pos, blk, ncclDouble, m->comm[d], m->xs[d]);
         if (r != ncclSuccess) return fail(dst, LJMD_ERR_HIP, "all-gather failed: %s", ncclGetErrorString(r));
@@ -187,7 +181,7 @@ int force_prepare(ljmd_multi *m, int g, EventSet *q)
     LJMD_HIP(e, hipStreamWaitEvent(m->xs[g], m->ev_force[g], 0));
     if (q) LJMD_HIP(e, hipEventRecord(q->e[7], m->xs[g]));
     if (m->xmode == kHost) {
-        LJMD_HIP(e, hipMemcpyAsync(m->h_xforce[g], e->d_fpart, (size_t)m->G * 3 * e->P * sizeof(double), hipMemcpyDeviceToHost,
+        LJMD_HIP(e, hipMemcpyAsync(m->h_xforce[g], e->d_fpart, (size_t)m->G * 3 * e->plan.P * sizeof(double), hipMemcpyDeviceToHost,
                                    m->xs[g]));
         LJMD_HIP(e, hipEventRecord(m->ev_hforce[g], m->xs[g]));
     }
@@ -197,7 +191,7 @@ int force_prepare(ljmd_multi *m, int g, EventSet *q)
 int force_collect(ljmd_multi *m, int d)
 {
     ljmd_t *dst = m->eng[d];
-    const size_t blk = 3 * (size_t)dst->P;
+    const size_t blk = 3 * (size_t)dst->plan.P;
     if (m->xmode == kRccl) {
         const ncclResult_t r = ncclReduceScatter(dst->d_fpart, dst->d_frecv, blk, ncclDouble, ncclSum, m->comm[d], m->xs[d]);
         if (r != ncclSuccess) return fail(dst, LJMD_ERR_HIP, "reduce-scatter failed: %s", ncclGetErrorString(r));
@@ -500,8 +494,8 @@ int create(ljmd_t **out, int32_t n, double box_length, double dt, double rc, int
         for (int k : m->dev) distinct = distinct && k != d;
         m->dev.push_back(d);
     }
-    const char *xm = std::getenv("LJMD_MULTI_EXCHANGE");
-    const std::string want = xm ? xm : "";
+    const Knobs knobs = read_knobs();
+    const std::string &want = knobs.multi_exchange;
     if (!want.empty() && want != "rccl" && want != "copy" && want != "host") {
         destroy(h);
         return fail(nullptr, LJMD_ERR_INVALID_ARG, "LJMD_MULTI_EXCHANGE=%s: expected rccl, copy or host", want.c_str());
@@ -512,7 +506,7 @@ int create(ljmd_t **out, int32_t n, double box_length, double dt, double rc, int
                     "LJMD_MULTI_EXCHANGE=rccl needs %d distinct devices (RCCL refuses two ranks on one device)", n_gpus);
     }
     m->xmode = want == "host" ? kHost : (want == "copy" || !distinct) ? kCopy : kRccl;
-    m->overlap = env_int("LJMD_OVERLAP_EXCHANGE", 1) != 0;
+    m->overlap = knobs.overlap_exchange;
     for (int g = 0; g < n_gpus; ++g) {
         ljmd_t *e = nullptr;
         const int rc_ = ljmd_create(&e, n, box_length, dt, rc, precision_mode, m->dev[g], g, n_gpus);
@@ -526,19 +520,14 @@ int create(ljmd_t **out, int32_t n, double box_length, double dt, double rc, int
     }
     // the parent carries the parameters the scalar combination needs (tail constants) and what callers query
     const ljmd_t *e0 = m->eng[0];
-    h->n = n; h->G = n_gpus; h->S = e0->S; h->P = e0->P; h->mode = precision_mode; h->rec_stride = e0->rec_stride;
+    h->n = n; h->G = n_gpus; h->plan.S = e0->plan.S; h->plan.P = e0->plan.P; h->mode = precision_mode; h->rec_stride = e0->rec_stride;
     m->owner.resize(n);
     for (int k = 0; k < n; ++k) m->owner[k] = k;
     // LJMD_MULTI_MIGRATE_EVERY: steps between two ownership migrations (0 = never).  Default 2000: at n = 65536 and 8
     // ranks the step rate falls by 1 % per 1000 steps without it (tools/shard_mixing_probe.py) and one migration costs
     // about as much as 50 steps there
-    {
-        const char *me = std::getenv("LJMD_MULTI_MIGRATE_EVERY");
-        m->migrate_every = me && *me ? std::max(0, std::atoi(me)) : 2000;
-    }
-    h->L = e0->L; h->invL = e0->invL; h->volume = e0->volume; h->rc = e0->rc; h->rc2 = e0->rc2;
-    h->dt = e0->dt; h->dt_half = e0->dt_half; h->dt_sq_half = e0->dt_sq_half;
-    h->tail_e = e0->tail_e; h->tail_d = e0->tail_d; h->tail_dd = e0->tail_dd;
+    m->migrate_every = knobs.multi_migrate_every;
+    static_cast<SimParams &>(*h) = *e0;
     auto body = [&]() -> int {
         std::vector<hipEvent_t> *evs[] = {&m->ev_pos, &m->ev_got, &m->ev_force, &m->ev_fgot, &m->ev_hpos, &m->ev_hforce};
         for (auto *v : evs) v->assign(n_gpus, nullptr);
@@ -566,7 +555,7 @@ int create(ljmd_t **out, int32_t n, double box_length, double dt, double rc, int
                                         hipGetErrorString(pe));
                         (void)hipGetLastError();
                     }
-            const size_t blk = 3 * (size_t)e->P * sizeof(double);
+            const size_t blk = 3 * (size_t)e->plan.P * sizeof(double);
             if (m->xmode != kRccl && needs_force_exchange(e) && !e->d_fall) LJMD_HIP(h, hipMalloc(&e->d_fall, blk * n_gpus));
             if (m->xmode == kHost) {
                 // portable: every device's copy engine reads the staging of every rank
@@ -582,7 +571,7 @@ int create(ljmd_t **out, int32_t n, double box_length, double dt, double rc, int
                 return fail(h, LJMD_ERR_HIP, "ncclCommInitAll over %d devices failed: %s", n_gpus, ncclGetErrorString(r));
             }
         }
-        if (n_gpus > 1 && env_int("LJMD_MULTI_THREADS", 1) != 0) {
+        if (n_gpus > 1 && knobs.multi_threads) {
             m->team.reset(new StepTeam);
             m->team->rc.assign(n_gpus, LJMD_OK);
             for (int g = 0; g < n_gpus; ++g) m->team->threads.emplace_back(team_worker, m, g);
@@ -697,7 +686,7 @@ int gather_by_owner(ljmd_t *h, const std::vector<int32_t> &owner, double *const 
         if (p[k]) m->stage[k].resize(h->n);
     for (ljmd_t *e : m->eng) {
         double *q[12];
-        for (int k = 0; k < 12; ++k) q[k] = p[k] ? m->stage[k].data() + (size_t)e->rank * e->S : nullptr;
+        for (int k = 0; k < 12; ++k) q[k] = p[k] ? m->stage[k].data() + (size_t)e->rank * e->plan.S : nullptr;
         LJMD_CHILD(h, e, fetch(e, q));
     }
     for (int k = 0; k < 12; ++k)
@@ -754,7 +743,7 @@ int migrate(ljmd_t *h)
         LJMD_HIP(h, hipStreamSynchronize(m->eng[g]->stream));
         LJMD_HIP(h, hipStreamSynchronize(m->xs[g]));
     }
-    const size_t blk = (size_t)kMigrateRows * m->eng[0]->P;
+    const size_t blk = (size_t)kMigrateRows * m->eng[0]->plan.P;
     if (m->xmode == kRccl) {
         ncclResult_t r = ncclGroupStart();
         for (int g = 0; g < G && r == ncclSuccess; ++g) {
@@ -806,10 +795,10 @@ int migrate(ljmd_t *h)
         ljmd_t *e = m->eng[g];
         LJMD_HIP(h, hipSetDevice(m->dev[g]));
         LJMD_CHILD(h, e, migrate_deal(e));                   // synchronises the rank's stream; e->h_gid0 is valid
-        for (int j = 0; j < e->S; ++j) {
+        for (int j = 0; j < e->plan.S; ++j) {
             const int id = e->h_gid0[j];
             if (id < 0 || id >= n) return fail(h, LJMD_ERR_STATE, "ownership migration: rank %d reports particle id %d", g, id);
-            owner[(size_t)g * e->S + j] = m->owner[id];
+            owner[(size_t)g * e->plan.S + j] = m->owner[id];
         }
         LJMD_CHILD(h, e, migrate_rebase(e));
     }
