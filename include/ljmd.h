@@ -432,11 +432,26 @@ int ljmd_profile_read_stats(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, d
  * into launches or the streams.  The energy sums are evaluated only on sampled steps; r, ru, v, a are bitwise the
  * same for every sample_every, and with no outputs at all.
  *
+ * Reproducible batches (ljmd_batch_set_precision with LJMD_PRECISION_FP64_REPRODUCIBLE): per replica, exactly the
+ * definition of LJMD_PRECISION_FP64_REPRODUCIBLE above -- the pair terms of that definition over every ordered pair,
+ * each entering a 128-bit integer sum as Q(t); a = 24 R(sum) with one rounding; S12, S6, Kx, Ky, Kz as exact 192-bit
+ * integers per replica (the ordered-pair sums halved as integers), ONE rounding per scalar, then the tail constants;
+ * ljmd_batch_kinetic_energy = 0.5 ((Kx + Ky) + Kz) of that definition; the integrator is the fp64 mode's.  A
+ * replica's results are then a function of its particle set alone: bitwise equal to tests/reproducible_model.py and to
+ * an ljmd_t of the same mode, and on top of the invariances above independent of the order of its particles (permuted
+ * input gives the permuted state and the same scalars).  Range: every term of every step, sampled or not, must be
+ * finite with |t| < 2^40; otherwise the term enters as 0, the replica's sticky flag is set, and the call
+ * (ljmd_batch_steps, ljmd_batch_compute_forces or ljmd_batch_kinetic_energy) fails with LJMD_ERR_RANGE, its message
+ * naming the lowest such replica ("replica <b>"); the handle is poisoned until ljmd_batch_set_state, which also clears
+ * the flags.  Launches hold fewer steps than in the fp64 mode (a pair costs several times as much).
+ *
  * Limits: n <= LJMD_BATCH_MAX_N -- one replica's positions live in one CU's LDS for a whole launch, 24 n bytes
- * <= 96 KiB; LJMD_PRECISION_FP64 only; rc <= (1 - 1e-9) L/2 and, at ljmd_batch_set_state, every replica's
- * coordinates finite and spanning < 2.4 L per axis (each replica against its own L) (the fast path's preconditions (b) and (a)): there is no
- * generic-kernel fallback in this mode, so such input fails with LJMD_ERR_INVALID_ARG.  All guards run before the
- * device probe; without a device ljmd_batch_create returns LJMD_ERR_NO_DEVICE.
+ * <= 96 KiB; the creators take LJMD_PRECISION_FP64 only (the mode of a new handle; the reproducible mode is selected
+ * afterwards with ljmd_batch_set_precision, no other mode exists for batches); rc <= (1 - 1e-9) L/2 and, at
+ * ljmd_batch_set_state, every replica's coordinates finite and spanning < 2.4 L per axis (each replica against its
+ * own L) (the fast path's preconditions (b) and (a)): there is no generic-kernel fallback in this mode, so such input
+ * fails with LJMD_ERR_INVALID_ARG.  All guards run before the device probe; without a device ljmd_batch_create
+ * returns LJMD_ERR_NO_DEVICE.
  *
  * Sequence: ljmd_batch_steps before ljmd_batch_set_state, or before valid accelerations (ljmd_batch_compute_forces
  * or ljmd_batch_set_accel), returns LJMD_ERR_STATE.  A launch that fails poisons the handle (LJMD_ERR_STATE) until
@@ -483,6 +498,11 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every,
                      double *epot, double *ekin, double *d_epot, double *dd_epot);
 /* As ljmd_set_tail_corrections. */
 int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on);
+/* LJMD_PRECISION_FP64 (the default of a new handle) or LJMD_PRECISION_FP64_REPRODUCIBLE; anything else:
+ * LJMD_ERR_INVALID_ARG and the handle keeps its mode.  The resident accelerations belong to the old mode:
+ * the handle then needs ljmd_batch_set_state again (LJMD_ERR_STATE from steps / compute_forces until then).
+ * Setting the mode the handle already has changes nothing.  Works on both kinds of handle. */
+int ljmd_batch_set_precision(ljmd_batch_t *h, int32_t precision_mode);
 /* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL.
  * Replicas of different kernel classes (n <= 128, 512, 1024, 2048, 4096) run as separate groups of launches, by
  * default each on a stream of its own (LJMD_BATCH_GROUP_STREAMS=0: one after another on the handle's stream); the

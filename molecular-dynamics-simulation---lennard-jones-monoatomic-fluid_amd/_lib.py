@@ -124,6 +124,7 @@ PROTOTYPES = {
     "ljmd_batch_kinetic_energy": (C.c_int, [C.c_void_p, c_double_p]),
     "ljmd_batch_steps": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [c_double_p] * 4),
     "ljmd_batch_set_tail_corrections": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ljmd_batch_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "ljmd_batch_profile_read": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
 }
 

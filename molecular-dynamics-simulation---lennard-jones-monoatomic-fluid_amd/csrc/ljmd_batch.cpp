@@ -1,9 +1,11 @@
 // ljmd_batch.cpp -- host side of the batch engine (include/ljmd.h: ljmd_batch_*): B independent replicas on one
 // device, each with its own (n, L, dt, rc) (ljmd_batch_create: all the same), stepped by one kernel (ljmd_batch.hip)
 // with one workgroup per replica.  Handle lifecycle, guards, device state, launch planning per kernel class and the
-// combination of the per-replica step records.
+// combination of the per-replica step records, in the fp64 mode and in the reproducible mode (ljmd_batch_fixed.hip:
+// exact integer records, a sticky range flag per replica).
 #include "ljmd_batch.h"
 #include "ljmd_common.h"
+#include "ljmd_internal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -42,6 +44,7 @@ struct ljmd_batch {
     std::vector<int64_t> offsets;     // [B + 1]
     std::vector<BatchGroup> groups;   // by kernel class, ascending
     bool concurrent = false;          // groups on streams of their own, joined before the records are fetched
+    int mode = LJMD_PRECISION_FP64;   // or LJMD_PRECISION_FP64_REPRODUCIBLE (ljmd_batch_set_precision)
     bool tail_on = true;
     bool have_state = false, have_accel = false;
     bool poisoned = false;            // a launch failed half-way: LJMD_ERR_STATE until ljmd_batch_set_state
@@ -50,9 +53,11 @@ struct ljmd_batch {
     hipEvent_t fork = nullptr;
     BatchReplica *d_table = nullptr;  // [B], the groups' entries one after another
     double *d_state = nullptr;        // [12][offsets[B]]
-    double *d_rec = nullptr;          // [rec_cap][B][kBatchRecWords]
-    size_t rec_cap = 0;               // samples the record buffer holds (>= 1)
+    double *d_rec = nullptr;          // [samples][B][rec_words]: doubles, or int64 words in the reproducible mode
+    size_t rec_cap = 0;               // 8-byte words the record buffer holds (>= B * kExactWords)
     std::vector<double> h_rec;
+    int32_t *d_range = nullptr;       // [B] reproducible mode: sticky range flags, cleared by ljmd_batch_set_state
+    std::vector<int32_t> h_range;
     double last_ms = 0.0;             // kernel time of the last ljmd_batch_steps call
     int32_t last_launches = 0;
     std::string err;
@@ -67,6 +72,26 @@ constexpr double kMinParallel = 256;  // below one replica per CU a launch does 
 // ... and a bound for a workgroup that runs alone on its CU, where latency, not throughput, sets the pace: one pass of a
 // wave over j costs ~30 dependent fp64 instructions, at most ~100 ns; 2e5 iterations of it per launch = <= 20 ms
 constexpr double kLaunchIterations = 2e5;
+// The reproducible mode (ljmd_batch_fixed.hip): ~230 VALU instructions per pair against ~34 gave the
+// starting values 3e9 / 3e4, whose launches measured 12.6-18.9 ms on one MI355X; raised by 1.2 to bring every class
+// into the 16-22 ms of the fp64 launches.  Measured full launches of these values (tools/batch_reproducible_rate.py,
+// profiles/batch_reproducible_rate.txt), n (B): steps per launch, kernel time:
+//   108 (4096): 75, 20.9 ms    500 (1024): 14, 16.9 ms    4000 (256): 1, 18.6 ms
+//   108 (1):   333, 16.7 ms    500 (1):    56, 19.2 ms    4000 (1):   1, 18.8 ms
+// = 1.7-2.2e11 ordered pairs/s and 0.47-1.17 us per pass over j.  From n = 3424 on one step of 256 replicas is already
+// more than kFixedLaunchPairs; a launch cannot hold less than one step, and fewer replicas than CUs do not shorten it.
+constexpr double kFixedLaunchPairs = 3.6e9;
+constexpr double kFixedLaunchIterations = 3.6e4;
+
+// the exact record's layout and flag bits are the kernels' (ljmd_internal.h); the range flag that counts is the sticky
+// word, not the record's
+using ljmdk::kExactWords;
+using ljmdk::kFlagNoEnergy;
+using ljmdk::kFlagNoKinetic;
+static_assert(kExactWords == LJMD_EXACT_PARTIAL_WORDS, "exact record layout out of sync with include/ljmd.h");
+
+bool reproducible(const ljmd_batch *h) { return h->mode == LJMD_PRECISION_FP64_REPRODUCIBLE; }
+size_t rec_words(const ljmd_batch *h) { return reproducible(h) ? kExactWords : kBatchRecWords; }
 
 double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
 
@@ -84,14 +109,17 @@ BatchArgs base_args(ljmd_batch *h, int mode)
 
 // replicas per launch and steps per launch of `count` replicas of at most n particles, from the
 // n^2 * steps * max(replicas, CUs) estimate
-void launch_shape(int n, size_t count, size_t *chunk, int *steps_per_launch)
+void launch_shape(int n, size_t count, bool fixed, size_t *chunk, int *steps_per_launch)
 {
+    const double pairs = fixed ? kFixedLaunchPairs : kLaunchPairs;
+    const double iterations = fixed ? kFixedLaunchIterations : kLaunchIterations;
     const double n2 = (double)n * n;
-    const double c = std::max(kMinParallel, std::floor(kLaunchPairs / n2));
+    const double c = std::max(kMinParallel, std::floor(pairs / n2));
     *chunk = std::min(count, (size_t)std::min(c, 2147483647.0));
-    const double s = std::floor(kLaunchPairs / (n2 * std::max(kMinParallel, (double)*chunk)));
-    const int passes = (batch_k(n) + 1) / 2;                 // passes over j per step (ljmd_batch.hip: KG)
-    const double s_latency = std::floor(kLaunchIterations / ((double)n * passes));
+    const double s = std::floor(pairs / (n2 * std::max(kMinParallel, (double)*chunk)));
+    // passes over j per step: ljmd_batch.hip works two own particles per pass (KG), ljmd_batch_fixed.hip one
+    const int passes = fixed ? batch_k(n) : (batch_k(n) + 1) / 2;
+    const double s_latency = std::floor(iterations / ((double)n * passes));
     *steps_per_launch = (int)std::max(1.0, std::min({s, s_latency, (double)LJMD_MAX_PENDING_STEPS}));
 }
 
@@ -103,43 +131,66 @@ BatchRep derive(int n, double box_length, double dt, double rc)
     return r;
 }
 
+// room for `samples` records of the handle's mode (at least one of either mode)
 int ensure_records(ljmd_batch *h, size_t samples)
 {
-    samples = std::max<size_t>(samples, 1);
-    if (samples <= h->rec_cap) return LJMD_OK;
+    const size_t words = std::max(samples * h->B * rec_words(h), h->B * (size_t)kExactWords);
+    if (words <= h->rec_cap) return LJMD_OK;
     if (h->d_rec) (void)hipFree(h->d_rec);
     h->d_rec = nullptr;
     h->rec_cap = 0;
-    const size_t bytes = samples * h->B * kBatchRecWords * sizeof(double);
+    const size_t bytes = words * sizeof(double);
     if (hipMalloc(&h->d_rec, bytes) != hipSuccess) {
         h->d_rec = nullptr;
         return fail(h, LJMD_ERR_ALLOC, "ljmd_batch: cannot allocate %zu bytes of step records", bytes);
     }
-    h->rec_cap = samples;
+    h->rec_cap = words;
     return LJMD_OK;
 }
 
-// copies `samples` records to the host; the handle is poisoned when the kernels behind them failed
-int fetch_records(ljmd_batch *h, size_t samples)
+// copies `samples` records to the host; the handle is poisoned when the kernels behind them failed.  Reproducible
+// mode: the range flags come along, and a set flag -- of a sampled or an unsampled step -- fails the call with
+// LJMD_ERR_RANGE, names the lowest such replica and poisons the handle
+int fetch_records(ljmd_batch *h, size_t samples, const char *who)
 {
-    h->h_rec.resize(samples * h->B * kBatchRecWords);
-    const hipError_t e = hipMemcpyAsync(h->h_rec.data(), h->d_rec, h->h_rec.size() * sizeof(double),
-                                        hipMemcpyDeviceToHost, h->stream);
+    h->h_rec.resize(samples * h->B * rec_words(h));
+    hipError_t e = hipMemcpyAsync(h->h_rec.data(), h->d_rec, h->h_rec.size() * sizeof(double), hipMemcpyDeviceToHost,
+                                  h->stream);
+    if (e == hipSuccess && reproducible(h))
+        e = hipMemcpyAsync(h->h_range.data(), h->d_range, h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
     const hipError_t s = e == hipSuccess ? hipStreamSynchronize(h->stream) : e;
     if (s != hipSuccess) {
         h->poisoned = true;
         return fail(h, LJMD_ERR_HIP, "ljmd_batch: kernel or copy failed: %s; the handle is poisoned until "
                                       "ljmd_batch_set_state", hipGetErrorString(s));
     }
+    if (reproducible(h))
+        for (size_t b = 0; b < h->B; ++b)
+            if (h->h_range[b] != 0) {
+                h->poisoned = true;
+                return fail(h, LJMD_ERR_RANGE, "%s: reproducible mode: replica %zu: a pair or velocity term was not "
+                                               "finite or |term| >= 2^40 (particles closer than about 0.12 sigma?); "
+                                               "the handle is poisoned until ljmd_batch_set_state", who, b);
+            }
     return LJMD_OK;
 }
 
-// as combine_one (ljmd_records.cpp) for replica b's record: the kernel already halved the ordered-pair sums
+// as combine_one (ljmd_records.cpp) for replica b's record: the kernel already halved the ordered-pair sums.
+// Reproducible mode: as combine_exact for the replica's one exact record (the words of r are int64)
 void combine(const ljmd_batch *h, size_t b, const double *r, double *epot, double *ekin, double *d_epot, double *dd_epot)
 {
     const BatchRep &p = h->rep[b];
     const double te = h->tail_on ? p.tail_e : 0.0, td = h->tail_on ? p.tail_d : 0.0, tdd = h->tail_on ? p.tail_dd : 0.0;
-    ljmdh::scalars_from_sums(r[0], r[1], r[2], r[3], r[4], te, td, tdd, epot, ekin, d_epot, dd_epot);
+    if (!reproducible(h)) {
+        ljmdh::scalars_from_sums(r[0], r[1], r[2], r[3], r[4], te, td, tdd, epot, ekin, d_epot, dd_epot);
+        return;
+    }
+    uint64_t sum[5][3];
+    int64_t flags;
+    std::memcpy(sum, r, sizeof sum);
+    std::memcpy(&flags, r + 15, sizeof flags);
+    ljmdh::scalars_from_exact_sums(sum, te, td, tdd, !(flags & kFlagNoEnergy), !(flags & kFlagNoKinetic), epot, ekin,
+                                   d_epot, dd_epot);
 }
 
 int upload(ljmd_batch *h, int which, int axis, const double *src)
@@ -169,7 +220,11 @@ int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const 
             a.nsteps = steps ? std::min(spl, nsteps - s0) : 0;
             for (size_t c0 = 0; c0 < g.count; c0 += g.chunk) {
                 a.g0 = (int)(g.first + c0);
-                const hipError_t e = launch_batch(a, g.n_max, (int)std::min(g.chunk, g.count - c0), s);
+                const int blocks = (int)std::min(g.chunk, g.count - c0);
+                const hipError_t e = reproducible(h)
+                    ? launch_batch_fixed(BatchFixedArgs{a, reinterpret_cast<int64_t *>(h->d_rec), h->d_range}, g.n_max,
+                                         blocks, s)
+                    : launch_batch(a, g.n_max, blocks, s);
                 ++count;
                 if (e != hipSuccess) {
                     h->poisoned = true;
@@ -231,7 +286,7 @@ int create_handle(ljmd_batch_t **out, std::vector<BatchRep> &&reps, int32_t devi
             }
             g.count = table.size() - g.first;
             if (g.count == 0) continue;
-            launch_shape(g.n_max, g.count, &g.chunk, &g.steps_per_launch);
+            launch_shape(g.n_max, g.count, reproducible(h), &g.chunk, &g.steps_per_launch);
             h->groups.push_back(g);
         }
         // several groups run concurrently unless LJMD_BATCH_GROUP_STREAMS=0 (one after another on the handle's stream)
@@ -259,6 +314,18 @@ int create_handle(ljmd_batch_t **out, std::vector<BatchRep> &&reps, int32_t devi
         if (hipMemcpyAsync(h->d_table, table.data(), tbytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
             hipStreamSynchronize(h->stream) != hipSuccess)
             return fail(h, LJMD_ERR_HIP, "%s: cannot upload the replica table", who);
+        try {
+            h->h_range.assign(h->B, 0);
+        } catch (const std::bad_alloc &) {
+            return fail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+        }
+        if (hipMalloc(&h->d_range, h->B * sizeof(int32_t)) != hipSuccess) {
+            h->d_range = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of range flags", who, h->B * sizeof(int32_t));
+        }
+        if (hipMemsetAsync(h->d_range, 0, h->B * sizeof(int32_t), h->stream) != hipSuccess ||
+            hipStreamSynchronize(h->stream) != hipSuccess)
+            return fail(h, LJMD_ERR_HIP, "%s: cannot clear the range flags", who);
         return ensure_records(h, 1);
     };
     const int rc_ = body();
@@ -365,6 +432,7 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
         if (g.stream) (void)hipStreamSynchronize(g.stream);
     if (h->d_rec) (void)hipFree(h->d_rec);
     if (h->d_table) (void)hipFree(h->d_table);
+    if (h->d_range) (void)hipFree(h->d_range);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -413,6 +481,7 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
         if (rc_ != LJMD_OK) return rc_;
     }
     LJMD_HIP(h, hipMemsetAsync(plane(h, LJMD_A, 0), 0, 3 * h->total * sizeof(double), h->stream));
+    LJMD_HIP(h, hipMemsetAsync(h->d_range, 0, h->B * sizeof(int32_t), h->stream));
     LJMD_HIP(h, hipStreamSynchronize(h->stream));
     h->have_state = true;
     h->have_accel = false;
@@ -480,11 +549,11 @@ int ljmd_batch_compute_forces(ljmd_batch_t *h, double *epot, double *d_epot, dou
     LJMD_HIP(h, hipSetDevice(h->device));
     int rc_ = run_groups(h, base_args(h, kModeForces), 0, nullptr, "ljmd_batch_compute_forces");
     if (rc_ != LJMD_OK) return rc_;
-    rc_ = fetch_records(h, 1);
+    rc_ = fetch_records(h, 1, "ljmd_batch_compute_forces");
     if (rc_ != LJMD_OK) return rc_;
     h->have_accel = true;
     for (size_t b = 0; b < h->B; ++b)
-        combine(h, b, h->h_rec.data() + b * kBatchRecWords, epot ? epot + b : nullptr, nullptr,
+        combine(h, b, h->h_rec.data() + b * rec_words(h), epot ? epot + b : nullptr, nullptr,
                 d_epot ? d_epot + b : nullptr, dd_epot ? dd_epot + b : nullptr);
     return LJMD_OK;
 }
@@ -499,9 +568,12 @@ int ljmd_batch_kinetic_energy(ljmd_batch_t *h, double *ekin)
     LJMD_HIP(h, hipSetDevice(h->device));
     int rc_ = run_groups(h, base_args(h, kModeKinetic), 0, nullptr, "ljmd_batch_kinetic_energy");
     if (rc_ != LJMD_OK) return rc_;
-    rc_ = fetch_records(h, 1);
+    rc_ = fetch_records(h, 1, "ljmd_batch_kinetic_energy");
     if (rc_ != LJMD_OK) return rc_;
-    for (size_t b = 0; b < h->B; ++b) ekin[b] = 0.5 * h->h_rec[b * kBatchRecWords + 2];   // md_simulation_program.f90:238-240
+    for (size_t b = 0; b < h->B; ++b) {
+        if (reproducible(h)) combine(h, b, h->h_rec.data() + b * kExactWords, nullptr, ekin + b, nullptr, nullptr);
+        else ekin[b] = 0.5 * h->h_rec[b * kBatchRecWords + 2];   // md_simulation_program.f90:238-240
+    }
     return LJMD_OK;
 }
 
@@ -539,7 +611,7 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     rc_ = run_groups(h, a, nsteps, &launches, "ljmd_batch_steps");
     if (rc_ != LJMD_OK) return rc_;
     LJMD_HIP(h, hipEventRecord(h->ev[1], h->stream));
-    rc_ = fetch_records(h, samples);
+    rc_ = fetch_records(h, samples, "ljmd_batch_steps");
     if (rc_ != LJMD_OK) return rc_;
     float ms = 0.0f;
     LJMD_HIP(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
@@ -548,9 +620,25 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     for (size_t s = 0; s < samples; ++s)
         for (size_t b = 0; b < h->B; ++b) {
             const size_t o = s * h->B + b;
-            combine(h, b, h->h_rec.data() + o * kBatchRecWords, epot ? epot + o : nullptr, ekin ? ekin + o : nullptr,
+            combine(h, b, h->h_rec.data() + o * rec_words(h), epot ? epot + o : nullptr, ekin ? ekin + o : nullptr,
                     d_epot ? d_epot + o : nullptr, dd_epot ? dd_epot + o : nullptr);
         }
+    return LJMD_OK;
+}
+
+int ljmd_batch_set_precision(ljmd_batch_t *h, int32_t precision_mode)
+{
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_precision: NULL handle");
+    if (precision_mode != LJMD_PRECISION_FP64 && precision_mode != LJMD_PRECISION_FP64_REPRODUCIBLE)
+        return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_set_precision: precision_mode %d not available for batches "
+                                              "(LJMD_PRECISION_FP64 or LJMD_PRECISION_FP64_REPRODUCIBLE)", precision_mode);
+    if (precision_mode == h->mode) return LJMD_OK;
+    // the range words and a poisoned handle stay as they are: have_state = false below makes ljmd_batch_set_state the
+    // only way on, and that call clears both
+    h->mode = precision_mode;
+    for (BatchGroup &g : h->groups) launch_shape(g.n_max, g.count, reproducible(h), &g.chunk, &g.steps_per_launch);
+    h->have_state = false;            // the resident accelerations belong to the old mode
+    h->have_accel = false;
     return LJMD_OK;
 }
 

@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
 
 namespace ljmdb {
 
@@ -63,6 +64,16 @@ inline int batch_class(int n) { return n <= 128 ? 0 : n <= 512 ? 1 : n <= 1024 ?
 // one launch of n_blocks table entries, all of batch_class(n_max), each at most n_max particles; the workgroup has
 // batch_threads(n_max) threads, of which an entry of fewer particles uses its own batch_threads(n)
 hipError_t launch_batch(const BatchArgs &a, int n_max, int n_blocks, hipStream_t s);
+
+// The same launch in the reproducible mode (ljmd_batch_fixed.hip).  b.rec is not used: the step records are exact,
+// LJMD_EXACT_PARTIAL_WORDS int64 words per (sample, replica) in the layout of ljmd_read_partials_exact -- S12 and S6
+// over the replica's ORDERED pairs, to be halved as integers -- record (s, b) at (s*B + b) * LJMD_EXACT_PARTIAL_WORDS.
+struct BatchFixedArgs {
+    BatchArgs b;
+    int64_t *rec;           // [n_samples][B][LJMD_EXACT_PARTIAL_WORDS]
+    int32_t *range;         // [B] sticky: set to 1 when a term of replica b was out of range, never cleared by a kernel
+};
+hipError_t launch_batch_fixed(const BatchFixedArgs &a, int n_max, int n_blocks, hipStream_t s);
 
 }  // namespace ljmdb
 

@@ -10,6 +10,7 @@
 
 #include <cstdarg>
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <optional>
 #include <string>
@@ -81,6 +82,13 @@ SimParams derive_params(int n, double box_length, double dt, double rc);
 // epot, d_epot, dd_epot from the unordered-pair sums of u^12 and u^6, ekin from the three sums of v^2 (NULL = not wanted)
 void scalars_from_sums(double s12, double s6, double kx, double ky, double kz, double te, double td, double tdd,
                        double *epot, double *ekin, double *d_epot, double *dd_epot);
+
+// The reproducible mode's form (ljmd_records.cpp), shared by the engine and the batch engine: `ordered` holds the exact
+// sums {S12, S6 over the ORDERED pairs, Kx, Ky, Kz}, signed 192-bit integers in units of 2^-64 as three little-endian
+// limbs.  The pair sums are halved and combined as integers, then ONE rounding per scalar, then the tail constants.
+// have_e / have_k false (the record carries no energy / kinetic sums): those scalars are NaN.
+void scalars_from_exact_sums(const uint64_t (&ordered)[5][3], double te, double td, double tdd, bool have_e, bool have_k,
+                             double *epot, double *ekin, double *d_epot, double *dd_epot);
 
 // Every LJMD_* environment variable an engine reads, with its default.  read_knobs() is called once per engine, when it
 // is created; the handle keeps the result, and a later change of the environment does not reach an existing engine.

@@ -60,29 +60,14 @@ void half192(uint64_t (&x)[3])
 }
 }  // namespace
 
-static_assert(LJMD_EXACT_PARTIAL_WORDS == kExactWords, "exact record layout out of sync with include/ljmd.h");
-
-int combine_exact(const ljmd_t *h, const int64_t *recs, int n_ranks, double *epot, double *ekin, double *d_epot,
-                  double *dd_epot)
+void scalars_from_exact_sums(const uint64_t (&ordered)[5][3], double te, double td, double tdd, bool have_e, bool have_k,
+                             double *epot, double *ekin, double *d_epot, double *dd_epot)
 {
-    uint64_t sum[5][3] = {};
-    int64_t flags = 0;
-    for (int g = 0; g < n_ranks; ++g) {          // integers: the rank order does not matter
-        const int64_t *r = recs + (size_t)g * kExactWords;
-        for (int k = 0; k < 5; ++k) {
-            const uint64_t o[3] = {(uint64_t)r[3 * k], (uint64_t)r[3 * k + 1], (uint64_t)r[3 * k + 2]};
-            add192(sum[k], o);
-        }
-        flags |= r[15];
-    }
-    if (flags & kFlagRange)
-        return fail(h, LJMD_ERR_RANGE, "reproducible mode: a pair or velocity term was not finite or |term| >= 2^40 "
-                                       "(particles closer than about 0.12 sigma?)");
+    uint64_t sum[5][3];
+    std::memcpy(sum, ordered, sizeof sum);
     half192(sum[0]);                             // ordered -> unordered pairs
     half192(sum[1]);
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    const double te = h->tail_on ? h->tail_e : 0.0, td = h->tail_on ? h->tail_d : 0.0, tdd = h->tail_on ? h->tail_dd : 0.0;
-    const bool have_e = !(flags & kFlagNoEnergy);
     if (epot) {                                  // 4 R(S12 - S6) + tail_e
         uint64_t x[3] = {sum[1][0], sum[1][1], sum[1][2]};
         neg192(x);
@@ -106,8 +91,31 @@ int combine_exact(const ljmd_t *h, const int64_t *recs, int n_ranks, double *epo
     }
     if (ekin) {                                  // 0.5 ((Kx + Ky) + Kz)
         const double kx = fixed_to_double(sum[2]), ky = fixed_to_double(sum[3]), kz = fixed_to_double(sum[4]);
-        *ekin = (flags & kFlagNoKinetic) ? nan : 0.5 * ((kx + ky) + kz);
+        *ekin = have_k ? 0.5 * ((kx + ky) + kz) : nan;
     }
+}
+
+static_assert(LJMD_EXACT_PARTIAL_WORDS == kExactWords, "exact record layout out of sync with include/ljmd.h");
+
+int combine_exact(const ljmd_t *h, const int64_t *recs, int n_ranks, double *epot, double *ekin, double *d_epot,
+                  double *dd_epot)
+{
+    uint64_t sum[5][3] = {};
+    int64_t flags = 0;
+    for (int g = 0; g < n_ranks; ++g) {          // integers: the rank order does not matter
+        const int64_t *r = recs + (size_t)g * kExactWords;
+        for (int k = 0; k < 5; ++k) {
+            const uint64_t o[3] = {(uint64_t)r[3 * k], (uint64_t)r[3 * k + 1], (uint64_t)r[3 * k + 2]};
+            add192(sum[k], o);
+        }
+        flags |= r[15];
+    }
+    if (flags & kFlagRange)
+        return fail(h, LJMD_ERR_RANGE, "reproducible mode: a pair or velocity term was not finite or |term| >= 2^40 "
+                                       "(particles closer than about 0.12 sigma?)");
+    const double te = h->tail_on ? h->tail_e : 0.0, td = h->tail_on ? h->tail_d : 0.0, tdd = h->tail_on ? h->tail_dd : 0.0;
+    scalars_from_exact_sums(sum, te, td, tdd, !(flags & kFlagNoEnergy), !(flags & kFlagNoKinetic), epot, ekin, d_epot,
+                            dd_epot);
     return LJMD_OK;
 }
 

@@ -25,7 +25,7 @@ module ljmd_c_api
   ! ljmd_batch_*)
   public :: ljmd_batch_create, ljmd_batch_create_per_replica, ljmd_batch_offsets, ljmd_batch_destroy, ljmd_batch_last_error, ljmd_batch_set_state, ljmd_batch_set_accel
   public :: ljmd_batch_set_unwrapped, ljmd_batch_get_state, ljmd_batch_compute_forces, ljmd_batch_kinetic_energy
-  public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_profile_read
+  public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_set_precision, ljmd_batch_profile_read
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -300,6 +300,14 @@ module ljmd_c_api
       import :: c_int, c_int32_t, c_ptr
       type(c_ptr), value :: handle
       integer(c_int32_t), value :: on
+      integer(c_int) :: status
+    end function
+
+    ! LJMD_PRECISION_FP64 or LJMD_PRECISION_FP64_REPRODUCIBLE; a change of mode asks for ljmd_batch_set_state again
+    function ljmd_batch_set_precision(handle, precision_mode) bind(C, name="ljmd_batch_set_precision") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: precision_mode
       integer(c_int) :: status
     end function
 

@@ -16,8 +16,11 @@
 ! Each run is the physics of md_simulation_gpu (the batch engine's contract, ljmd.h); the runs differ from it only by
 ! the summation order of the forces.  Every file of a run is byte-identical to what this program writes with
 ! LJMD_RUNS=1 and that run's parameters as the shared input.
-! Environment: LJMD_RUNS (default 10, the reference's n_runs_default, run_many_md.f90:26), LJMD_DEVICE (default 0).
-! Batches are fp64 only and take n <= LJMD_BATCH_MAX_N.
+! Environment: LJMD_RUNS (default 10, the reference's n_runs_default, run_many_md.f90:26), LJMD_DEVICE (default 0),
+! LJMD_REPRODUCIBLE (default 0; 1: the batch handle runs in the LJMD_PRECISION_FP64_REPRODUCIBLE mode,
+! ljmd_batch_set_precision -- every file of a run is then byte-identical to what md_simulation_gpu writes for that run
+! with LJMD_REPRODUCIBLE=1).
+! Batches take n <= LJMD_BATCH_MAX_N.
 !==============================================================================
 program md_simulation_many_gpu
   use, intrinsic :: iso_c_binding
@@ -49,7 +52,7 @@ program md_simulation_many_gpu
   real(kind=dp_kind) :: time, etot, temp_inst, press_inst
   integer(kind=int_kind) :: step, k, num_samples, n, ni, rest
   integer :: n_runs, i, ios, device, iu
-  integer(c_int32_t) :: n_runs_c
+  integer(c_int32_t) :: n_runs_c, precision_mode
   integer(kind=8) :: c0, c1, crate, o, total
   type(c_ptr) :: batch
   character(len=32) :: env
@@ -64,6 +67,11 @@ program md_simulation_many_gpu
   device = 0
   call get_environment_variable('LJMD_DEVICE', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) device
+  precision_mode = LJMD_PRECISION_FP64
+  call get_environment_variable('LJMD_REPRODUCIBLE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) then
+    if (trim(env) /= '0') precision_mode = LJMD_PRECISION_FP64_REPRODUCIBLE
+  end if
 
   allocate(rparams(n_runs), own_params(n_runs), off(n_runs + 1), time_run(n_runs))
   allocate(s_epot(n_runs), s_ekin(n_runs), s_depot(n_runs), s_ddepot(n_runs))
@@ -102,6 +110,8 @@ program md_simulation_many_gpu
                                             LJMD_PRECISION_FP64, int(device, c_int32_t)), c_null_ptr, 'ljmd_batch_create')
   end if
   n_runs_c = int(n_runs, c_int32_t)
+  ! a new batch handle is fp64 (the creators take no other mode); the mode is set before the state
+  call ljmd_batch_check(ljmd_batch_set_precision(batch, precision_mode), batch, 'ljmd_batch_set_precision')
   call ljmd_batch_check(ljmd_batch_set_tail_corrections(batch, merge(1_c_int32_t, 0_c_int32_t, use_tail_corrections)), &
                         batch, 'ljmd_batch_set_tail_corrections')
   ! H2D; the library sets ru <- r (md_simulation_program.f90:229-231)

@@ -376,9 +376,14 @@ class Engine:
 class BatchEngine:
     """n_replicas independent systems of the same (n, L, dt, rc) on one GPU (ljmd_batch_*, include/ljmd.h): the ensemble
     runs of the reference's run-many framework, one workgroup per replica.  Each replica is the physics of an Engine.
-    Per-particle arrays are (B, n) per component, per-replica scalars (B,); fp64 only, n <= 4096."""
+    Per-particle arrays are (B, n) per component, per-replica scalars (B,); n <= 4096.  precision_mode is
+    PRECISION_FP64 or PRECISION_FP64_REPRODUCIBLE (per replica the bits of Engine(precision_mode=2) and of
+    tests/reproducible_model.py); set_precision changes it later, after which the state has to be set again."""
 
-    def __init__(self, params: SimParams, n_replicas: int, device: int = 0):
+    BATCH_PRECISION_MODES = (_lib.PRECISION_FP64, _lib.PRECISION_FP64_REPRODUCIBLE)
+
+    def __init__(self, params: SimParams, n_replicas: int, device: int = 0, precision_mode: int = _lib.PRECISION_FP64):
+        self._check_mode(precision_mode)
         self._lib = _lib.load()
         self.params = params
         self.n_replicas = int(n_replicas)
@@ -386,6 +391,29 @@ class BatchEngine:
         _lib.check_batch(self._lib.ljmd_batch_create(C.byref(h), self.n_replicas, params.n, params.box_length,
                                                      params.dt, params.rc, _lib.PRECISION_FP64, device))
         self._h = h
+        self._open_in(precision_mode)
+
+    @classmethod
+    def _check_mode(cls, mode) -> None:
+        if mode not in cls.BATCH_PRECISION_MODES:
+            raise ValueError(f"precision_mode must be one of {cls.BATCH_PRECISION_MODES} for a batch, got {mode!r}")
+
+    def _open_in(self, mode: int) -> None:
+        """a new handle is fp64 (the creators take no other mode): switch it, and release it if that fails"""
+        self.precision_mode = _lib.PRECISION_FP64
+        if mode != _lib.PRECISION_FP64:
+            try:
+                self.set_precision(mode)
+            except Exception:
+                self.close()
+                raise
+
+    def set_precision(self, mode: int) -> None:
+        """ljmd_batch_set_precision: PRECISION_FP64 or PRECISION_FP64_REPRODUCIBLE.  A change of mode drops the resident
+        state: set_state has to follow (steps / compute_forces raise LJMD_ERR_STATE until then).  The library, not this
+        wrapper, refuses any other mode (LJMD_ERR_INVALID_ARG), and the handle keeps its mode."""
+        self._ck(self._lib.ljmd_batch_set_precision(self._h, int(mode)))
+        self.precision_mode = int(mode)
 
     # -- lifecycle ---------------------------------------------------------
     def close(self) -> None:
@@ -487,9 +515,10 @@ class BatchEngine:
         return {"kernel_ms": ms.value, "launches": c.value}
 
     @staticmethod
-    def per_replica(params_list, device: int = 0) -> "PerReplicaBatchEngine":
+    def per_replica(params_list, device: int = 0,
+                    precision_mode: int = _lib.PRECISION_FP64) -> "PerReplicaBatchEngine":
         """one handle of len(params_list) replicas, replica b with its own (n, L, dt, rc) = params_list[b]"""
-        return PerReplicaBatchEngine(params_list, device)
+        return PerReplicaBatchEngine(params_list, device, precision_mode)
 
 
 class PerReplicaBatchEngine(BatchEngine):
@@ -498,7 +527,8 @@ class PerReplicaBatchEngine(BatchEngine):
     Per-particle arguments and results are lists of B arrays of shape (n_b,); per-replica scalars stay (B,) and the
     scalars of steps() (samples, B).  offsets[b] .. offsets[b + 1] is replica b's range in the library's planes."""
 
-    def __init__(self, params_list, device: int = 0):
+    def __init__(self, params_list, device: int = 0, precision_mode: int = _lib.PRECISION_FP64):
+        self._check_mode(precision_mode)
         self._lib = _lib.load()
         self.params_list = list(params_list)
         self.n_replicas = len(self.params_list)
@@ -516,6 +546,7 @@ class PerReplicaBatchEngine(BatchEngine):
         off = np.empty(self.n_replicas + 1, dtype=np.int64)
         self._ck(self._lib.ljmd_batch_offsets(self._h, off.ctypes.data_as(_lib.c_int64_p)))
         self.offsets = off
+        self._open_in(precision_mode)
 
     @property
     def params(self):
