@@ -453,6 +453,13 @@ int ljmd_profile_read_stats(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, d
  * fails with LJMD_ERR_INVALID_ARG.  All guards run before the device probe; without a device ljmd_batch_create
  * returns LJMD_ERR_NO_DEVICE.
  *
+ * g(r) (ljmd_batch_rdf_*): the pair-distance histogram of every replica's resident wrapped positions, accumulated on
+ * the device into [B][nbins] 64-bit counts -- per replica exactly the integers ljmd_rdf_histogram adds for that
+ * snapshot (weight 2 per unordered pair with r < rmax_b, bin int(r / dr_b), dr_b = rmax_b / nbins; all particles, no
+ * subsampling), so the counts are independent of B, slot, launch grouping, streams and precision mode.
+ * ljmd_batch_rdf_accumulate adds one snapshot; with every > 0 ljmd_batch_steps adds the positions after steps every,
+ * 2 every, ... of each call by itself, leaving r, ru, v, a and the sampled scalars bitwise what they are without it.
+ *
  * Sequence: ljmd_batch_steps before ljmd_batch_set_state, or before valid accelerations (ljmd_batch_compute_forces
  * or ljmd_batch_set_accel), returns LJMD_ERR_STATE.  A launch that fails poisons the handle (LJMD_ERR_STATE) until
  * ljmd_batch_set_state.  A handle is not thread-safe; one handle is one device.
@@ -504,11 +511,31 @@ int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on);
  * Setting the mode the handle already has changes nothing.  Works on both kinds of handle. */
 int ljmd_batch_set_precision(ljmd_batch_t *h, int32_t precision_mode);
 /* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL.
+ * Both include the g(r) launches of that call (ljmd_batch_rdf_configure with every > 0).
  * Replicas of different kernel classes (n <= 128, 512, 1024, 2048, 4096) run as separate groups of launches, by
  * default each on a stream of its own (LJMD_BATCH_GROUP_STREAMS=0: one after another on the handle's stream); the
  * kernel time is then the span from the first group's first launch to the last group's end, not a sum over groups,
  * and the launch count is the total over all groups. */
 int ljmd_batch_profile_read(const ljmd_batch_t *h, double *kernel_ms, int32_t *launches);
+/*
+ * g(r) histograms on the device.  configure: nbins bins per replica (1 <= nbins <= 8192; 0 switches the feature off
+ * and frees the histogram), rmax[B] (each finite and > 0) or NULL = 0.5 L_b, every >= 0; allocates and zeroes the
+ * [B][nbins] counts and the snapshot count; calling it again reconfigures and zeroes.  A failed guard returns
+ * LJMD_ERR_INVALID_ARG ("ljmd_batch_rdf_configure: replica <b>: ..." where one replica is at fault) and leaves the
+ * earlier configuration in place.  every > 0: ljmd_batch_steps accumulates the positions after steps every,
+ * 2 every, ... of each call (independent of sample_every); its nsteps must then be a multiple of every
+ * (LJMD_ERR_INVALID_ARG before anything is launched).  ljmd_batch_set_precision and ljmd_batch_set_state leave the
+ * configuration and the counts alone.  If a reproducible ljmd_batch_steps call fails with LJMD_ERR_RANGE, the counts
+ * accumulated in that call are unspecified until ljmd_batch_rdf_reset.
+ * accumulate: adds the histogram of the positions resident now, for every replica, stream-ordered (no host wait); the
+ * snapshot count goes up by one.  LJMD_ERR_STATE before configure, before ljmd_batch_set_state or on a poisoned handle.
+ * read: waits for the device, copies hist[B][nbins] (or NULL) and the snapshot count (or NULL); clears nothing.
+ * reset: zeroes both.  read and reset return LJMD_ERR_STATE before configure.
+ */
+int ljmd_batch_rdf_configure(ljmd_batch_t *h, int32_t nbins, const double *rmax, int32_t every);
+int ljmd_batch_rdf_accumulate(ljmd_batch_t *h);
+int ljmd_batch_rdf_read(ljmd_batch_t *h, uint64_t *hist, int64_t *n_snapshots);
+int ljmd_batch_rdf_reset(ljmd_batch_t *h);
 
 #ifdef __cplusplus
 }

@@ -48,13 +48,20 @@ def compute_rdf(rx: np.ndarray, ry: np.ndarray, rz: np.ndarray, L: float, nbins:
     counts = np.zeros(nbins, dtype=np.uint64)
     for s in snap_idx:
         histogram(rx[s, part_idx], ry[s, part_idx], rz[s, part_idx], L, nbins, rmax, counts)
-    hist = counts.astype(np.float64)               # each unordered pair contributed 2 (i-j and j-i)
+    return rdf_from_histogram(counts, n_eff, L, nbins, rmax, len(snap_idx))
+
+
+def rdf_from_histogram(hist, n: int, L: float, nbins: int, rmax: float, n_snapshots: int):
+    """-> (r_centers, g_r) from pair-distance counts (2 per unordered pair, summed over n_snapshots snapshots of n
+    particles in a box of side L): the reference's normalisation (scripts/md_one_run_analysis.py:586-594).  The counts
+    of BatchEngine.rdf_read go in row by row."""
+    hist = np.asarray(hist).astype(np.float64)     # each unordered pair contributed 2 (i-j and j-i)
     vol = L ** 3
-    rho = n_eff / vol
+    rho = n / vol
     r_edges = np.linspace(0.0, rmax, nbins + 1)
     r_centers = 0.5 * (r_edges[:-1] + r_edges[1:])
     shell_vol = (4.0 / 3.0) * math.pi * (r_edges[1:] ** 3 - r_edges[:-1] ** 3)
-    norm = len(snap_idx) * n_eff * rho * shell_vol
+    norm = n_snapshots * n * rho * shell_vol
     g = np.zeros_like(r_centers)
     mask = norm > 0
     g[mask] = hist[mask] / norm[mask]

@@ -2,7 +2,7 @@
 // device, each with its own (n, L, dt, rc) (ljmd_batch_create: all the same), stepped by one kernel (ljmd_batch.hip)
 // with one workgroup per replica.  Handle lifecycle, guards, device state, launch planning per kernel class and the
 // combination of the per-replica step records, in the fp64 mode and in the reproducible mode (ljmd_batch_fixed.hip:
-// exact integer records, a sticky range flag per replica).
+// exact integer records, a sticky range flag per replica), and the g(r) accumulation (ljmd_batch_rdf.hip).
 #include "ljmd_batch.h"
 #include "ljmd_common.h"
 #include "ljmd_internal.h"
@@ -30,6 +30,7 @@ struct BatchGroup {
     int n_max = 0;
     size_t chunk = 0;
     int steps_per_launch = 0;
+    size_t rdf_chunk = 0;             // replicas per g(r) launch: launch_shape's pair bound of the fp64 mode, one step
     hipStream_t stream = nullptr;     // own stream when the handle runs its groups concurrently, else the handle's
     hipEvent_t done = nullptr;
 };
@@ -60,6 +61,11 @@ struct ljmd_batch {
     std::vector<int32_t> h_range;
     double last_ms = 0.0;             // kernel time of the last ljmd_batch_steps call
     int32_t last_launches = 0;
+    // g(r) accumulation (ljmd_batch_rdf_*): off while rdf_nbins == 0
+    int32_t rdf_nbins = 0, rdf_every = 0;
+    int64_t rdf_snapshots = 0;
+    unsigned long long *d_rdf_hist = nullptr;   // [B][rdf_nbins]
+    BatchRdfReplica *d_rdf_table = nullptr;     // [B], replica order
     std::string err;
 };
 
@@ -200,11 +206,36 @@ int upload(ljmd_batch *h, int which, int axis, const double *src)
     return LJMD_OK;
 }
 
+// the g(r) launches of group g on stream s: the positions resident now, chunks of at most rdf_chunk replicas
+int enqueue_rdf(ljmd_batch *h, const BatchGroup &g, hipStream_t s, int32_t *count, const char *who)
+{
+    BatchRdfArgs ra{};
+    ra.r = plane(h, LJMD_R, 0);
+    ra.rep = h->d_table;
+    ra.rdf = h->d_rdf_table;
+    ra.hist = h->d_rdf_hist;
+    ra.plane = h->total;
+    ra.nbins = h->rdf_nbins;
+    for (size_t c0 = 0; c0 < g.count; c0 += g.rdf_chunk) {
+        ra.g0 = (int)(g.first + c0);
+        const hipError_t e = launch_batch_rdf(ra, g.n_max, (int)std::min(g.rdf_chunk, g.count - c0), s);
+        ++*count;
+        if (e != hipSuccess) {
+            h->poisoned = true;
+            return fail(h, LJMD_ERR_HIP, "%s: g(r) launch failed: %s; the handle is poisoned until ljmd_batch_set_state",
+                         who, hipGetErrorString(e));
+        }
+    }
+    return LJMD_OK;
+}
+
 // one pass of the kernel over every replica in `mode`: nsteps steps (kModeSteps) or one evaluation.  Group by group,
 // launches of at most chunk replicas and steps_per_launch steps, in the order steps-outer, replicas-inner.  With
 // concurrent groups every group runs on its own stream between a fork from and a join into the handle's stream, so
 // what the handle's stream does next (the record copy) follows all of them.  A failed launch poisons the handle.
-int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const char *who)
+// rdf_every > 0 (kModeSteps only): a launch ends at the steps rdf_every, 2 rdf_every, ..., and the group's g(r)
+// launches follow it on the same stream; 0 is the launch sequence without g(r).
+int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int rdf_every, int32_t *launches, const char *who)
 {
     if (h->concurrent) {
         LJMD_HIP(h, hipEventRecord(h->fork, h->stream));
@@ -215,9 +246,11 @@ int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const 
     for (const BatchGroup &g : h->groups) {
         hipStream_t s = h->concurrent ? g.stream : h->stream;
         const int spl = steps ? g.steps_per_launch : 1;
-        for (int s0 = 0; s0 < (steps ? nsteps : 1); s0 += spl) {
+        for (int s0 = 0, len = 0; s0 < (steps ? nsteps : 1); s0 += len) {
+            len = std::min(spl, (steps ? nsteps : 1) - s0);
+            if (rdf_every > 0) len = std::min(len, rdf_every - s0 % rdf_every);
             a.step0 = s0;
-            a.nsteps = steps ? std::min(spl, nsteps - s0) : 0;
+            a.nsteps = steps ? len : 0;
             for (size_t c0 = 0; c0 < g.count; c0 += g.chunk) {
                 a.g0 = (int)(g.first + c0);
                 const int blocks = (int)std::min(g.chunk, g.count - c0);
@@ -234,6 +267,10 @@ int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const 
                     return fail(h, LJMD_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
                 }
             }
+            if (rdf_every > 0 && (s0 + len) % rdf_every == 0) {
+                const int rc_ = enqueue_rdf(h, g, s, &count, who);
+                if (rc_ != LJMD_OK) return rc_;
+            }
         }
         if (h->concurrent) {
             LJMD_HIP(h, hipEventRecord(g.done, s));
@@ -242,6 +279,19 @@ int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int32_t *launches, const 
     }
     if (launches) *launches = count;
     return LJMD_OK;
+}
+
+// releases the g(r) buffers after what may still use them
+void rdf_release(ljmd_batch *h)
+{
+    if (h->stream && (h->d_rdf_hist || h->d_rdf_table)) (void)hipStreamSynchronize(h->stream);
+    if (h->d_rdf_hist) (void)hipFree(h->d_rdf_hist);
+    if (h->d_rdf_table) (void)hipFree(h->d_rdf_table);
+    h->d_rdf_hist = nullptr;
+    h->d_rdf_table = nullptr;
+    h->rdf_nbins = 0;
+    h->rdf_every = 0;
+    h->rdf_snapshots = 0;
 }
 
 // the handle from its replicas' parameters, after the guards and the probe: groups, stream(s), device memory
@@ -287,6 +337,8 @@ int create_handle(ljmd_batch_t **out, std::vector<BatchRep> &&reps, int32_t devi
             g.count = table.size() - g.first;
             if (g.count == 0) continue;
             launch_shape(g.n_max, g.count, reproducible(h), &g.chunk, &g.steps_per_launch);
+            int one_step = 0;
+            launch_shape(g.n_max, g.count, false, &g.rdf_chunk, &one_step);
             h->groups.push_back(g);
         }
         // several groups run concurrently unless LJMD_BATCH_GROUP_STREAMS=0 (one after another on the handle's stream)
@@ -433,6 +485,7 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
     if (h->d_rec) (void)hipFree(h->d_rec);
     if (h->d_table) (void)hipFree(h->d_table);
     if (h->d_range) (void)hipFree(h->d_range);
+    rdf_release(h);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -547,7 +600,7 @@ int ljmd_batch_compute_forces(ljmd_batch_t *h, double *epot, double *d_epot, dou
         return fail(h, LJMD_ERR_STATE, "ljmd_batch_compute_forces: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
     LJMD_HIP(h, hipSetDevice(h->device));
-    int rc_ = run_groups(h, base_args(h, kModeForces), 0, nullptr, "ljmd_batch_compute_forces");
+    int rc_ = run_groups(h, base_args(h, kModeForces), 0, 0, nullptr, "ljmd_batch_compute_forces");
     if (rc_ != LJMD_OK) return rc_;
     rc_ = fetch_records(h, 1, "ljmd_batch_compute_forces");
     if (rc_ != LJMD_OK) return rc_;
@@ -566,7 +619,7 @@ int ljmd_batch_kinetic_energy(ljmd_batch_t *h, double *ekin)
         return fail(h, LJMD_ERR_STATE, "ljmd_batch_kinetic_energy: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
     LJMD_HIP(h, hipSetDevice(h->device));
-    int rc_ = run_groups(h, base_args(h, kModeKinetic), 0, nullptr, "ljmd_batch_kinetic_energy");
+    int rc_ = run_groups(h, base_args(h, kModeKinetic), 0, 0, nullptr, "ljmd_batch_kinetic_energy");
     if (rc_ != LJMD_OK) return rc_;
     rc_ = fetch_records(h, 1, "ljmd_batch_kinetic_energy");
     if (rc_ != LJMD_OK) return rc_;
@@ -599,6 +652,10 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     if (h->poisoned)
         return fail(h, LJMD_ERR_STATE, "ljmd_batch_steps: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
+    const int rdf_every = h->rdf_nbins > 0 ? h->rdf_every : 0;
+    if (rdf_every > 0 && nsteps % rdf_every != 0)
+        return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: nsteps %d is not a multiple of the g(r) interval %d "
+                                              "(ljmd_batch_rdf_configure: every)", nsteps, rdf_every);
     if (nsteps == 0) return LJMD_OK;
     LJMD_HIP(h, hipSetDevice(h->device));
     const size_t samples = sampling ? (size_t)(nsteps / sample_every) : 0;
@@ -608,8 +665,9 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     a.sample_every = sampling ? sample_every : 0;
     int32_t launches = 0;
     LJMD_HIP(h, hipEventRecord(h->ev[0], h->stream));
-    rc_ = run_groups(h, a, nsteps, &launches, "ljmd_batch_steps");
+    rc_ = run_groups(h, a, nsteps, rdf_every, &launches, "ljmd_batch_steps");
     if (rc_ != LJMD_OK) return rc_;
+    if (rdf_every > 0) h->rdf_snapshots += nsteps / rdf_every;
     LJMD_HIP(h, hipEventRecord(h->ev[1], h->stream));
     rc_ = fetch_records(h, samples, "ljmd_batch_steps");
     if (rc_ != LJMD_OK) return rc_;
@@ -654,6 +712,109 @@ int ljmd_batch_profile_read(const ljmd_batch_t *h, double *kernel_ms, int32_t *l
     if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_batch_profile_read: NULL handle");
     if (kernel_ms) *kernel_ms = h->last_ms;
     if (launches) *launches = h->last_launches;
+    return LJMD_OK;
+}
+
+// ---- g(r) accumulation ---------------------------------------------------------------------------------------------
+
+int ljmd_batch_rdf_configure(ljmd_batch_t *h, int32_t nbins, const double *rmax, int32_t every)
+{
+    static const char *who = "ljmd_batch_rdf_configure";
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (nbins < 0 || nbins > kBatchRdfMaxBins)
+        return fail(h, LJMD_ERR_INVALID_ARG, "%s: nbins = %d outside 1..%d (0 switches g(r) off)", who, nbins,
+                     kBatchRdfMaxBins);
+    if (every < 0) return fail(h, LJMD_ERR_INVALID_ARG, "%s: every must be >= 0", who);
+    if (nbins > 0 && rmax)
+        for (size_t b = 0; b < h->B; ++b)
+            if (!(std::isfinite(rmax[b]) && rmax[b] > 0.0))
+                return fail(h, LJMD_ERR_INVALID_ARG, "%s: replica %zu: rmax must be finite and > 0", who, b);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    rdf_release(h);
+    if (nbins == 0) return LJMD_OK;
+    std::vector<BatchRdfReplica> table;
+    try {
+        table.resize(h->B);
+    } catch (const std::bad_alloc &) {
+        return fail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+    }
+    for (size_t b = 0; b < h->B; ++b) {
+        BatchRdfReplica &e = table[b];
+        e.rmax = rmax ? rmax[b] : 0.5 * h->rep[b].L;
+        e.dr = e.rmax / nbins;                       // as the reference: dr = rmax / nbins
+        e.inv_dr = 1.0 / e.dr;
+    }
+    const size_t hbytes = h->B * (size_t)nbins * sizeof(unsigned long long), tbytes = h->B * sizeof(BatchRdfReplica);
+    auto body = [&]() -> int {
+        if (hipMalloc(&h->d_rdf_hist, hbytes) != hipSuccess) {
+            h->d_rdf_hist = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of histograms", who, hbytes);
+        }
+        if (hipMalloc(&h->d_rdf_table, tbytes) != hipSuccess) {
+            h->d_rdf_table = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of the g(r) table", who, tbytes);
+        }
+        LJMD_HIP(h, hipMemsetAsync(h->d_rdf_hist, 0, hbytes, h->stream));
+        LJMD_HIP(h, hipMemcpyAsync(h->d_rdf_table, table.data(), tbytes, hipMemcpyHostToDevice, h->stream));
+        LJMD_HIP(h, hipStreamSynchronize(h->stream));    // table goes out of scope
+        return LJMD_OK;
+    };
+    const int rc_ = body();
+    if (rc_ != LJMD_OK) {
+        rdf_release(h);
+        return rc_;
+    }
+    h->rdf_nbins = nbins;
+    h->rdf_every = every;
+    return LJMD_OK;
+}
+
+int ljmd_batch_rdf_accumulate(ljmd_batch_t *h)
+{
+    static const char *who = "ljmd_batch_rdf_accumulate";
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (h->rdf_nbins == 0) return fail(h, LJMD_ERR_STATE, "%s: call ljmd_batch_rdf_configure first", who);
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "%s: no state has been set", who);
+    if (h->poisoned)
+        return fail(h, LJMD_ERR_STATE, "%s: handle poisoned by an earlier failure; call ljmd_batch_set_state", who);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    int32_t count = 0;
+    for (const BatchGroup &g : h->groups) {
+        const int rc_ = enqueue_rdf(h, g, h->stream, &count, who);
+        if (rc_ != LJMD_OK) return rc_;
+    }
+    ++h->rdf_snapshots;
+    return LJMD_OK;
+}
+
+int ljmd_batch_rdf_read(ljmd_batch_t *h, uint64_t *hist, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_batch_rdf_read";
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (h->rdf_nbins == 0) return fail(h, LJMD_ERR_STATE, "%s: call ljmd_batch_rdf_configure first", who);
+    static_assert(sizeof(uint64_t) == sizeof(unsigned long long), "histogram word");
+    LJMD_HIP(h, hipSetDevice(h->device));
+    if (hist)
+        LJMD_HIP(h, hipMemcpyAsync(hist, h->d_rdf_hist, h->B * (size_t)h->rdf_nbins * sizeof(uint64_t),
+                                    hipMemcpyDeviceToHost, h->stream));
+    const hipError_t e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        h->poisoned = true;
+        return fail(h, LJMD_ERR_HIP, "%s: kernel or copy failed: %s; the handle is poisoned until ljmd_batch_set_state",
+                     who, hipGetErrorString(e));
+    }
+    if (n_snapshots) *n_snapshots = h->rdf_snapshots;
+    return LJMD_OK;
+}
+
+int ljmd_batch_rdf_reset(ljmd_batch_t *h)
+{
+    static const char *who = "ljmd_batch_rdf_reset";
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (h->rdf_nbins == 0) return fail(h, LJMD_ERR_STATE, "%s: call ljmd_batch_rdf_configure first", who);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    LJMD_HIP(h, hipMemsetAsync(h->d_rdf_hist, 0, h->B * (size_t)h->rdf_nbins * sizeof(unsigned long long), h->stream));
+    h->rdf_snapshots = 0;
     return LJMD_OK;
 }
 

@@ -75,6 +75,23 @@ struct BatchFixedArgs {
 };
 hipError_t launch_batch_fixed(const BatchFixedArgs &a, int n_max, int n_blocks, hipStream_t s);
 
+// g(r) accumulation (ljmd_batch_rdf.hip): the pair-distance histogram of every replica's resident positions, added to
+// the replica's row of hist.  Same launch geometry as launch_batch; the kernel class sets only the LDS of the positions.
+constexpr int kBatchRdfMaxBins = 8192;                 // 32 KiB of 32-bit LDS bins beside <= 96 KiB of positions
+struct BatchRdfReplica {    // entry b of the handle's second table, replica order
+    double rmax, dr, inv_dr;  // dr = rmax / nbins, inv_dr = 1 / dr
+};
+struct BatchRdfArgs {
+    const double *r;        // [3][plane]: the wrapped positions (planes rx ry rz of the state)
+    const BatchReplica *rep;
+    const BatchRdfReplica *rdf;   // [B]
+    unsigned long long *hist;     // [B][nbins], row b written by replica b's workgroup alone
+    size_t plane;
+    int g0;
+    int nbins;
+};
+hipError_t launch_batch_rdf(const BatchRdfArgs &a, int n_max, int n_blocks, hipStream_t s);
+
 }  // namespace ljmdb
 
 #endif  // LJMD_BATCH_KERNEL_H

@@ -26,6 +26,7 @@ module ljmd_c_api
   public :: ljmd_batch_create, ljmd_batch_create_per_replica, ljmd_batch_offsets, ljmd_batch_destroy, ljmd_batch_last_error, ljmd_batch_set_state, ljmd_batch_set_accel
   public :: ljmd_batch_set_unwrapped, ljmd_batch_get_state, ljmd_batch_compute_forces, ljmd_batch_kinetic_energy
   public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_set_precision, ljmd_batch_profile_read
+  public :: ljmd_batch_rdf_configure, ljmd_batch_rdf_accumulate, ljmd_batch_rdf_read, ljmd_batch_rdf_reset
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -317,6 +318,34 @@ module ljmd_c_api
       type(c_ptr), value :: handle
       real(c_double), intent(out) :: kernel_ms
       integer(c_int32_t), intent(out) :: launches
+      integer(c_int) :: status
+    end function
+
+    ! g(r) on the device: rmax = c_null_ptr (0.5 L of each replica) or B doubles; hist = [nbins, B] 64-bit counts
+    function ljmd_batch_rdf_configure(handle, nbins, rmax, every) bind(C, name="ljmd_batch_rdf_configure") &
+        result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle, rmax
+      integer(c_int32_t), value :: nbins, every
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rdf_accumulate(handle) bind(C, name="ljmd_batch_rdf_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rdf_read(handle, hist, n_snapshots) bind(C, name="ljmd_batch_rdf_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, hist
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rdf_reset(handle) bind(C, name="ljmd_batch_rdf_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
       integer(c_int) :: status
     end function
   end interface

@@ -19,7 +19,10 @@
 ! Environment: LJMD_RUNS (default 10, the reference's n_runs_default, run_many_md.f90:26), LJMD_DEVICE (default 0),
 ! LJMD_REPRODUCIBLE (default 0; 1: the batch handle runs in the LJMD_PRECISION_FP64_REPRODUCIBLE mode,
 ! ljmd_batch_set_precision -- every file of a run is then byte-identical to what md_simulation_gpu writes for that run
-! with LJMD_REPRODUCIBLE=1).
+! with LJMD_REPRODUCIBLE=1), LJMD_RDF_BINS (default 0 = off; nbins > 0: g(r) of every run on the device,
+! ljmd_batch_rdf_*: the pair-distance histogram up to L/2 of all particles is accumulated at every sampling instant that
+! writes an rva.dat record, and outputs/run_NNNN/rdf_gpu.dat gets nbins lines of bin centre, integer count (2 per
+! unordered pair) and g(r) with the reference's normalisation, scripts/md_one_run_analysis.py:586-594).
 ! Batches take n <= LJMD_BATCH_MAX_N.
 !==============================================================================
 program md_simulation_many_gpu
@@ -56,6 +59,9 @@ program md_simulation_many_gpu
   integer(kind=8) :: c0, c1, crate, o, total
   type(c_ptr) :: batch
   character(len=32) :: env
+  integer :: rdf_bins
+  integer(c_int64_t), allocatable, target :: rdf_hist(:, :)     ! [rdf_bins, n_runs]
+  integer(c_int64_t) :: rdf_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -72,6 +78,10 @@ program md_simulation_many_gpu
   if (ios == 0 .and. len_trim(env) > 0) then
     if (trim(env) /= '0') precision_mode = LJMD_PRECISION_FP64_REPRODUCIBLE
   end if
+  rdf_bins = 0
+  call get_environment_variable('LJMD_RDF_BINS', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rdf_bins
+  if (rdf_bins < 0) stop 'md_simulation_many: LJMD_RDF_BINS must be >= 0.'
 
   allocate(rparams(n_runs), own_params(n_runs), off(n_runs + 1), time_run(n_runs))
   allocate(s_epot(n_runs), s_ekin(n_runs), s_depot(n_runs), s_ddepot(n_runs))
@@ -117,6 +127,8 @@ program md_simulation_many_gpu
   ! H2D; the library sets ru <- r (md_simulation_program.f90:229-231)
   call ljmd_batch_check(ljmd_batch_set_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(vx), c_loc(vy), &
                                              c_loc(vz)), batch, 'ljmd_batch_set_state')
+  if (rdf_bins > 0) call ljmd_batch_check(ljmd_batch_rdf_configure(batch, int(rdf_bins, c_int32_t), c_null_ptr, &
+                                                                   0_c_int32_t), batch, 'ljmd_batch_rdf_configure')
   ! t = 0 forces and energies of every run (:236-243)
   call ljmd_batch_check(ljmd_batch_compute_forces(batch, c_loc(s_epot), c_loc(s_depot), c_loc(s_ddepot)), batch, &
                         'ljmd_batch_compute_forces')
@@ -153,6 +165,7 @@ program md_simulation_many_gpu
     step = step + output_interval
     if (step <= warmup_steps) cycle
     num_samples = num_samples + 1
+    if (rdf_bins > 0) call ljmd_batch_check(ljmd_batch_rdf_accumulate(batch), batch, 'ljmd_batch_rdf_accumulate')
     call ljmd_batch_check(ljmd_batch_get_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(ux), c_loc(uy), &
                                                c_loc(uz), c_loc(vx), c_loc(vy), c_loc(vz), c_loc(ax), c_loc(ay), &
                                                c_loc(az)), batch, 'ljmd_batch_get_state')
@@ -173,6 +186,10 @@ program md_simulation_many_gpu
   if (rest > 0) call ljmd_batch_check(ljmd_batch_steps(batch, int(rest, c_int32_t), 1_c_int32_t, c_null_ptr, &
                                                        c_null_ptr, c_null_ptr, c_null_ptr), batch, 'ljmd_batch_steps')
   call system_clock(c1)
+  if (rdf_bins > 0) then
+    allocate(rdf_hist(rdf_bins, n_runs))
+    call ljmd_batch_check(ljmd_batch_rdf_read(batch, c_loc(rdf_hist), rdf_snapshots), batch, 'ljmd_batch_rdf_read')
+  end if
   call ljmd_batch_destroy(batch)
   do i = 1, n_runs
     close(iu_out(i))
@@ -189,6 +206,11 @@ program md_simulation_many_gpu
     write(iu, '(a)') trim(run_dir(i))
   end do
   close(iu)
+  if (rdf_bins > 0) then
+    do i = 1, n_runs
+      call write_rdf(i)
+    end do
+  end if
   if (any_own) then
     write(*, '(a,i0,a,i0,a,i0,a,f12.2,a)') 'md_simulation_many_gpu: particles=', total, ' runs=', n_runs_c, &
       ' steps=', total_steps, '  ', dble(n_runs) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), &
@@ -228,6 +250,30 @@ contains
       ' uses its own input_simulation_parameters.txt: N=', rparams(irun)%n, ' L=', rparams(irun)%box_length, &
       ' dt=', rparams(irun)%dt, ' rc=', rparams(irun)%rc
   end subroutine read_run_parameters
+
+  ! run i's rdf_gpu.dat: bin centre, count, g(r) = count / (snapshots N rho shell volume), edges k rmax / nbins
+  subroutine write_rdf(irun)
+    integer, intent(in) :: irun
+    real(kind=dp_kind), parameter :: pi = 3.141592653589793238462643383279502884d0
+    real(kind=dp_kind) :: rmax, dr, e0, e1, rho, norm, g
+    integer :: iu_rdf, ierr, kb
+    rmax = 0.5d0 * rparams(irun)%box_length
+    dr = rmax / dble(rdf_bins)
+    rho = dble(rparams(irun)%n) / rparams(irun)%box_length**3
+    open(newunit=iu_rdf, file=trim(run_dir(irun)) // '/rdf_gpu.dat', status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'md_simulation_many: cannot open rdf_gpu.dat of a run.'
+    write(iu_rdf, '(a)') '# r_center   count   g(r)'
+    do kb = 1, rdf_bins
+      e0 = dble(kb - 1) * dr
+      e1 = dble(kb) * dr
+      if (kb == rdf_bins) e1 = rmax
+      norm = dble(rdf_snapshots) * dble(rparams(irun)%n) * rho * ((4.d0 / 3.d0) * pi * (e1**3 - e0**3))
+      g = 0.d0
+      if (norm > 0.d0) g = dble(rdf_hist(kb, irun)) / norm
+      write(iu_rdf, '(es24.16e3,2x,i0,2x,es24.16e3)') 0.5d0 * (e0 + e1), rdf_hist(kb, irun), g
+    end do
+    close(iu_rdf)
+  end subroutine write_rdf
 
   ! run i's rv_init.dat: record 1 = rx ry rz, record 2 = vx vy vz (md_initial_config_program.f90:285-286)
   subroutine read_rv_init(irun)

@@ -514,6 +514,35 @@ class BatchEngine:
         self._ck(self._lib.ljmd_batch_profile_read(self._h, C.byref(ms), C.byref(c)))
         return {"kernel_ms": ms.value, "launches": c.value}
 
+    # -- g(r) on the device ------------------------------------------------
+    def rdf_configure(self, nbins: int, rmax=None, every: int = 0) -> None:
+        """ljmd_batch_rdf_configure: nbins bins per replica up to rmax (a scalar, B values, or None = 0.5 L of each
+        replica); every > 0: steps() accumulates the positions after steps every, 2 every, ... by itself.  nbins = 0
+        switches the feature off.  Zeroes the counts."""
+        ptr = None
+        if rmax is not None:
+            arr = np.ascontiguousarray(np.broadcast_to(np.asarray(rmax, dtype=np.float64), (self.n_replicas,)))
+            ptr = _ptr(arr)
+        self._ck(self._lib.ljmd_batch_rdf_configure(self._h, int(nbins), ptr, int(every)))
+        self._rdf_nbins = int(nbins)
+
+    def rdf_accumulate(self) -> None:
+        """adds the pair-distance histogram of every replica's resident positions (no host wait)"""
+        self._ck(self._lib.ljmd_batch_rdf_accumulate(self._h))
+
+    def rdf_read(self):
+        """-> (hist[B, nbins] uint64, n_snapshots): the counts so far (2 per unordered pair), not cleared"""
+        nbins = getattr(self, "_rdf_nbins", 0)
+        if nbins < 1:
+            raise ValueError("rdf_read: call rdf_configure with nbins >= 1 first")
+        hist = np.empty((self.n_replicas, nbins), dtype=np.uint64)
+        count = C.c_int64()
+        self._ck(self._lib.ljmd_batch_rdf_read(self._h, hist.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(count)))
+        return hist, count.value
+
+    def rdf_reset(self) -> None:
+        self._ck(self._lib.ljmd_batch_rdf_reset(self._h))
+
     @staticmethod
     def per_replica(params_list, device: int = 0,
                     precision_mode: int = _lib.PRECISION_FP64) -> "PerReplicaBatchEngine":
