@@ -12,6 +12,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 
 namespace ljmdb {
 
@@ -60,6 +61,27 @@ inline int batch_threads(int n)
 // kernel class (NMAX, K) of a replica of n particles: 0 <= 128 < 1 <= 512 < 2 <= 1024 < 3 <= 2048 < 4 <= 4096
 constexpr int kBatchClasses = 5;
 inline int batch_class(int n) { return n <= 128 ? 0 : n <= 512 ? 1 : n <= 1024 ? 2 : n <= 2048 ? 3 : 4; }
+
+// The classes in one place, for the kernel files: f(NMAX, K) -- both as std::integral_constant -- launches the caller's
+// kernel of the class of n_max.
+template <typename F>
+hipError_t dispatch_class(int n_max, int n_blocks, F &&f)
+{
+    if (n_max <= 0 || n_max > 4096 || n_blocks <= 0) return hipErrorInvalidValue;
+    auto launch = [&](auto nmax, auto k) {
+        static_assert(64 * ((nmax() + 64 * k() - 1) / (64 * k())) <= kBatchMaxThreads, "too many threads for the class");
+        f(nmax, k);
+        return hipGetLastError();
+    };
+    using std::integral_constant;
+    switch (batch_class(n_max)) {
+    case 0: return launch(integral_constant<int, 128>{}, integral_constant<int, 1>{});
+    case 1: return launch(integral_constant<int, 512>{}, integral_constant<int, 1>{});
+    case 2: return launch(integral_constant<int, 1024>{}, integral_constant<int, 1>{});
+    case 3: return launch(integral_constant<int, 2048>{}, integral_constant<int, 2>{});
+    default: return launch(integral_constant<int, 4096>{}, integral_constant<int, 4>{});
+    }
+}
 
 // one launch of n_blocks table entries, all of batch_class(n_max), each at most n_max particles; the workgroup has
 // batch_threads(n_max) threads, of which an entry of fewer particles uses its own batch_threads(n)

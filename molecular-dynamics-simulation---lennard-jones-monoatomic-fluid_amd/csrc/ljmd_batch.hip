@@ -1,11 +1,11 @@
 // ljmd_batch.hip -- gfx950 kernel of the batch engine (include/ljmd.h: ljmd_batch_*): many independent small systems,
 // each with its own (n, L, dt, rc), one workgroup per replica, many MD steps per launch.
 //
-// Per replica the arithmetic is the single engine's fast path:
-//   drift + wrap + half-kick + unwrapped update  = drift_kick_kernel<0> (ljmd_kernels.hip), same expression order;
-//   pair term                                    = pair_fast<true> (ljmd_kernels.hip), full-matrix gather form: every
-//                                                  ordered pair (i, j != i), the energy sums scaled by 0.5 afterwards
-//                                                  as the gather kernels' FinalizeArgs::pair_scale does;
+// Per replica the arithmetic is the single engine's fast path, the very functions (ljmd_internal.h, last section):
+//   drift + wrap + half-kick + unwrapped update  = drift_wrap, half_kick, as drift_kick_kernel<0> (ljmd_kernels.hip);
+//   pair term                                    = pair_fast<true>, full-matrix gather form: every ordered pair
+//                                                  (i, j != i), the energy sums scaled by 0.5 afterwards as the
+//                                                  gather kernels' FinalizeArgs::pair_scale does;
 //   second half-kick                             = kick_kernel<true>: a = 24 f, v += a dt/2, three separate sums of v^2.
 // Compiled with -ffp-contract=off (csrc/Makefile): FMAs only where the source says fma().
 //
@@ -20,81 +20,16 @@
 // workgroup, so every position read is a broadcast.  A thread tid < T owns particles tid, tid + T, ... (K of them); their
 // ru, v, a stay in HBM (read and written by the owning thread only), their pair accumulators in registers.
 #include "ljmd_batch.h"
+#include "ljmd_internal.h"
 
 namespace ljmdb {
 namespace {
 
-// ---- restated from ljmd_kernels.hip (which stays untouched): mic_fast, rcp_newton, pair_fast, wave_sum ------------
-// Fast-path preconditions, checked on the host (ljmd_batch.cpp): (a) every coordinate span < 2.4 L,
-// (b) rc <= (1 - 1e-9) L/2.  See the comment above mic_fast in ljmd_kernels.hip.
-__device__ __forceinline__ double mic_fast(double d, double L, double invL)
-{
-    return fma(-L, __builtin_rint(d * invL), d);
-}
-
-__device__ __forceinline__ double rcp_newton(double x)
-{
-    // v_rcp_f64 + one Halley step, within 1 ulp of the IEEE quotient (ljmd_kernels.hip: rcp_newton)
-    const double y0 = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, y0, 1.0);
-    const double t = fma(e, e, e);
-    return fma(y0, t, y0);
-}
-
-// = pair_fast<true>; ENERGY = false leaves out the two energy sums (forces-only steps; the forces are the same bits)
-template <bool ENERGY>
-__device__ __forceinline__ void pair_batch(double xi, double yi, double zi, double xj, double yj, double zj,
-                                           double L, double invL, double rc2, bool is_self,
-                                           double &ax, double &ay, double &az, double &s12, double &s6)
-{
-    const double dx = mic_fast(xi - xj, L, invL);
-    const double dy = mic_fast(yi - yj, L, invL);
-    const double dz = mic_fast(zi - zj, L, invL);
-    const double r2 = fma(dz, dz, fma(dy, dy, dx * dx));
-    const bool in = r2 < rc2 && !is_self;                // strict <; NaN (an unused own slot) never passes
-    if (in) {
-        const double u = rcp_newton(r2);
-        const double u3 = u * u * u;
-        const double u6 = u3 * u3;
-        if constexpr (ENERGY) {
-            s12 += u6;
-            s6 += u3;
-        }
-        const double g = fma(2.0, u6, -u3) * u;          // = -dU_r * inv_r2
-        ax = fma(g, dx, ax);
-        ay = fma(g, dy, ay);
-        az = fma(g, dz, az);
-    }
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;  // valid in lane 0
-}
-
-// fixed-order sum over the first W <= kBatchMaxWaves waves of the workgroup (the replica's own); every thread of the
-// workgroup calls it (it holds a barrier), the waves from W on contribute nothing.  The result is valid in thread 0
-template <int NVAL>
-__device__ __forceinline__ void block_sum_waves(double (&v)[NVAL], double *red /* [NVAL * kBatchMaxWaves] */, int W)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NVAL; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) red[k * kBatchMaxWaves + wave] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NVAL; ++k) {
-            double s = red[k * kBatchMaxWaves];
-            for (int w = 1; w < W; ++w) s += red[k * kBatchMaxWaves + w];
-            v[k] = s;
-        }
-    }
-}
+using ljmdk::block_sum;
+using ljmdk::Drift;
+using ljmdk::drift_wrap;
+using ljmdk::half_kick;
+using ljmdk::pair_fast;
 
 // gather over all n positions of the replica for the K own particles of this thread
 template <int NMAX, int K, bool ENERGY>
@@ -109,8 +44,8 @@ __device__ __forceinline__ void gather(const double *pos, int n, const double (&
         const double xj = pos[j], yj = pos[NMAX + j], zj = pos[2 * NMAX + j];
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            pair_batch<ENERGY>(xi[k], yi[k], zi[k], xj, yj, zj, L, invL, rc2, j == ii[k],
-                               f[0][k], f[1][k], f[2][k], e[0][k], e[1][k]);
+            pair_fast<true, ENERGY>(xi[k], yi[k], zi[k], xj, yj, zj, L, invL, rc2, j == ii[k],
+                                    f[0][k], f[1][k], f[2][k], e[0][k], e[1][k]);
     }
 }
 
@@ -118,7 +53,7 @@ template <int NMAX, int K>
 __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
 {
     __shared__ double pos[3 * NMAX];
-    __shared__ double red[kBatchRecWords * kBatchMaxWaves];
+    __shared__ double red[kBatchRecWords * kBatchMaxWaves];   // block_sum over the replica's own T / 64 waves
     const BatchReplica &rp = a.rep[a.g0 + blockIdx.x];
     const int n = rp.n, T = rp.threads, tid = threadIdx.x;
     const double L = rp.L, invL = rp.invL, rc2 = rp.rc2, dt = rp.dt, dt_half = rp.dt_half, dt_sq_half = rp.dt_sq_half;
@@ -142,7 +77,7 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
                 s[0] += vx * vx + vy * vy + vz * vz;
             }
         }
-        block_sum_waves<1>(s, red, T >> 6);
+        block_sum<1>(s, red, kBatchMaxWaves, T >> 6);
         if (tid == 0) {
             double *w = a.rec + b * kBatchRecWords;
             w[0] = 0.0;
@@ -176,14 +111,10 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
                     for (int ax = 0; ax < 3; ++ax) {
                         const size_t o = ax * plane + base + i;
                         const double v0 = V[o], acc = A[o];
-                        const double r0 = pos[ax * NMAX + i];
-                        double r1 = (r0 + v0 * dt) + acc * dt_sq_half;
-                        r1 = r1 - L * __builtin_floor(r1 * invL);
-                        double d = r1 - r0;
-                        d = d - L * __builtin_round(d * invL);
-                        pos[ax * NMAX + i] = r1;
-                        RU[o] = RU[o] + d;
-                        V[o] = v0 + acc * dt_half;
+                        const Drift h = drift_wrap(pos[ax * NMAX + i], v0, acc, dt, dt_sq_half, L, invL);
+                        pos[ax * NMAX + i] = h.r1;
+                        RU[o] = RU[o] + h.d;
+                        V[o] = half_kick(v0, acc, dt_half);
                     }
                 }
             }
@@ -234,7 +165,7 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
         }
         if (sampled) {
             double v[kBatchRecWords] = {e12, e6, kk[0], kk[1], kk[2]};
-            block_sum_waves<kBatchRecWords>(v, red, T >> 6);
+            block_sum<kBatchRecWords>(v, red, kBatchMaxWaves, T >> 6);
             if (tid == 0) {
                 const size_t rec = steps ? (size_t)(gstep / a.sample_every - 1) : 0;
                 double *w = a.rec + (rec * a.B + b) * kBatchRecWords;
@@ -260,26 +191,13 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_md_kernel(BatchArgs a)
     }
 }
 
-template <int NMAX, int K>
-hipError_t launch_class(const BatchArgs &a, int n_max, int n_blocks, hipStream_t s)
-{
-    static_assert(64 * ((NMAX + 64 * K - 1) / (64 * K)) <= kBatchMaxThreads, "too many threads for the class");
-    hipLaunchKernelGGL((batch_md_kernel<NMAX, K>), dim3(n_blocks), dim3(batch_threads(n_max)), 0, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_batch(const BatchArgs &a, int n_max, int n_blocks, hipStream_t s)
 {
-    if (n_max <= 0 || n_max > 4096 || n_blocks <= 0) return hipErrorInvalidValue;
-    switch (batch_class(n_max)) {
-    case 0: return launch_class<128, 1>(a, n_max, n_blocks, s);
-    case 1: return launch_class<512, 1>(a, n_max, n_blocks, s);
-    case 2: return launch_class<1024, 1>(a, n_max, n_blocks, s);
-    case 3: return launch_class<2048, 2>(a, n_max, n_blocks, s);
-    default: return launch_class<4096, 4>(a, n_max, n_blocks, s);
-    }
+    return dispatch_class(n_max, n_blocks, [&](auto nmax, auto k) {
+        hipLaunchKernelGGL((batch_md_kernel<nmax(), k()>), dim3(n_blocks), dim3(batch_threads(n_max)), 0, s, a);
+    });
 }
 
 }  // namespace ljmdb

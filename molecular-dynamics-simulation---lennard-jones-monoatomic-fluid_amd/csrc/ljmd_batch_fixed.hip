@@ -4,8 +4,8 @@
 //
 // Structure as ljmd_batch.hip: one workgroup per replica, its positions SoA in LDS for the whole launch, j uniform
 // across the workgroup, the replica table, the kernel classes and the three modes.  What differs:
-//   pair term   = pair_fixed (ljmd_kernels.hip): round() minimum image, unfused r2, strict <, IEEE divide,
-//                 fx = (m dx) u.  Every term enters a per-particle signed 128-bit sum as Q(t) = RNE(t 2^64);
+//   pair term   = pair_fixed (ljmd_internal.h, the single engine's): round() minimum image, unfused r2, strict <,
+//                 IEEE divide, fx = (m dx) u.  Every term enters a per-particle signed 128-bit sum as Q(t) = RNE(t 2^64);
 //   kick        = fixed_tail_kernel: a = 24 R(particle sum) with ONE rounding, v += a dt/2, Q(v^2) per axis;
 //   drift       = ljmd_batch.hip's, unchanged (drift_kick_kernel<0>, which the reproducible single engine uses too);
 //   record      = kExactWords int64 per (sample, replica), the layout of ljmd_read_partials_exact: {S12, S6} over the
@@ -22,87 +22,19 @@
 namespace ljmdb {
 namespace {
 
-using ljmdk::add192;
+using ljmdk::block_sum192;
+using ljmdk::Drift;
+using ljmdk::drift_wrap;
+using ljmdk::fixed_add;
+using ljmdk::fixed_out_of_range;
 using ljmdk::fixed_to_double;
 using ljmdk::from128;
+using ljmdk::half_kick;
 using ljmdk::kExactWords;
-using ljmdk::kFixedBound;
 using ljmdk::kFlagNoEnergy;
 using ljmdk::kFlagNoKinetic;
 using ljmdk::kFlagRange;
-
-// ---- restated from ljmd_kernels.hip (which stays untouched): fixed_add, fixed_out_of_range, pair_fixed ------------
-// acc += Q(t), |t| < 2^40.  v = RNE(t 2^64) is an integer-valued double, |v| < 2^104; split exactly at 2^62:
-// hi = trunc(v 2^-62), lo = v - hi 2^62 (|lo| < 2^62, a multiple of ulp(v): representable), both convert exactly.
-__device__ __forceinline__ void fixed_add(__int128 &acc, double t)
-{
-    const double v = __builtin_rint(t * 0x1p64);
-    const double hi = __builtin_trunc(v * 0x1p-62);
-    const double lo = v - hi * 0x1p62;
-    acc += ((__int128)(int64_t)hi << 62) + (__int128)(int64_t)lo;
-}
-
-__device__ __forceinline__ bool fixed_out_of_range(double t) { return !(__builtin_fabs(t) < kFixedBound); }
-
-template <bool ENERGY>
-__device__ __forceinline__ void pair_fixed(double xi, double yi, double zi, double xj, double yj, double zj, double L,
-                                           double invL, double rc2, bool is_self, __int128 &ax, __int128 &ay,
-                                           __int128 &az, __int128 &s12, __int128 &s6, bool &bad)
-{
-    const double dx0 = xi - xj, dy0 = yi - yj, dz0 = zi - zj;
-    const double dx = dx0 - L * __builtin_round(dx0 * invL);          // geometry_pbc.f90:86
-    const double dy = dy0 - L * __builtin_round(dy0 * invL);
-    const double dz = dz0 - L * __builtin_round(dz0 * invL);
-    const double r2 = dx * dx + dy * dy + dz * dz;                    // lj_potential_energy.f90:129
-    if (r2 < rc2 && !is_self) {                                       // :132; NaN (an unused own slot) never passes
-        const double u = 1.0 / r2;                                    // :135
-        const double u3 = u * u * u;                                  // :136
-        const double u6 = u3 * u3;                                    // :137
-        const double mdu = 2.0 * u6 - u3;                             // :143
-        const double fx = mdu * dx * u, fy = mdu * dy * u, fz = mdu * dz * u;   // :148-155
-        // u^3 <= max(1, u^6): the u^6 test covers it, and both instantiations test the same terms
-        const bool oob = fixed_out_of_range(fx) || fixed_out_of_range(fy) || fixed_out_of_range(fz) ||
-                         fixed_out_of_range(u6);
-        bad = bad || oob;
-        fixed_add(ax, oob ? 0.0 : fx);
-        fixed_add(ay, oob ? 0.0 : fy);
-        fixed_add(az, oob ? 0.0 : fz);
-        if constexpr (ENERGY) {
-            fixed_add(s12, oob ? 0.0 : u6);
-            fixed_add(s6, oob ? 0.0 : u3);
-        }
-    }
-}
-
-// Sum of five signed 192-bit values per thread over the workgroup (cf. block_sum192, ljmd_kernels.hip): integer
-// shuffles inside a wave, then the first W waves (the replica's own; the others hold zeros) through LDS.  Every thread
-// of the workgroup calls it (it holds a barrier); the result is valid in thread 0.
-__device__ __forceinline__ void block_sum192(uint64_t (&q)[5][3], uint64_t (*lds)[5][3] /* [kBatchMaxWaves] */, int W)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll 1
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            uint64_t o[3];
-#pragma unroll
-            for (int w = 0; w < 3; ++w) o[w] = __shfl_down(q[k][w], off, 64);
-            add192(q[k], o);
-        }
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-#pragma unroll
-            for (int w = 0; w < 3; ++w) lds[wave][k][w] = q[k][w];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int v = 1; v < W; ++v)
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const uint64_t o[3] = {lds[v][k][0], lds[v][k][1], lds[v][k][2]};
-                add192(q[k], o);
-            }
-}
+using ljmdk::pair_fixed;
 
 // thread 0: the exact record of (sample, replica)
 __device__ __forceinline__ void write_record(int64_t *w, const uint64_t (&q)[5][3], int64_t flags)
@@ -146,7 +78,7 @@ template <int NMAX, int K>
 __global__ __launch_bounds__(kBatchMaxThreads) void batch_fixed_kernel(BatchFixedArgs fa)
 {
     __shared__ double pos[3 * NMAX];
-    __shared__ uint64_t red[kBatchMaxWaves][5][3];
+    __shared__ uint64_t red[kBatchMaxWaves][5][3];    // block_sum192 over the replica's T / 64 waves (the others hold zeros)
     const BatchArgs &a = fa.b;
     const BatchReplica &rp = a.rep[a.g0 + blockIdx.x];
     const int n = rp.n, T = rp.threads, tid = threadIdx.x;
@@ -176,7 +108,7 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_fixed_kernel(BatchFixe
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) from128(q[2 + ax], kq[ax]);
         const bool any_bad = __syncthreads_or(bad);
-        block_sum192(q, red, T >> 6);
+        block_sum192<true>(q, red, T >> 6);
         if (tid == 0) {
             write_record(fa.rec + b * kExactWords, q, (any_bad ? kFlagRange : 0) | kFlagNoEnergy);
             if (any_bad) fa.range[b] = 1;
@@ -210,14 +142,10 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_fixed_kernel(BatchFixe
                     for (int ax = 0; ax < 3; ++ax) {
                         const size_t o = ax * plane + base + i;
                         const double v0 = V[o], acc = A[o];
-                        const double r0 = pos[ax * NMAX + i];
-                        double r1 = (r0 + v0 * dt) + acc * dt_sq_half;
-                        r1 = r1 - L * __builtin_floor(r1 * invL);
-                        double d = r1 - r0;
-                        d = d - L * __builtin_round(d * invL);
-                        pos[ax * NMAX + i] = r1;
-                        RU[o] = RU[o] + d;
-                        V[o] = v0 + acc * dt_half;
+                        const Drift h = drift_wrap(pos[ax * NMAX + i], v0, acc, dt, dt_sq_half, L, invL);
+                        pos[ax * NMAX + i] = h.r1;
+                        RU[o] = RU[o] + h.d;
+                        V[o] = half_kick(v0, acc, dt_half);
                     }
                 }
             }
@@ -262,7 +190,7 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_fixed_kernel(BatchFixe
 #pragma unroll
             for (int ax = 0; ax < 3; ++ax) from128(q[2 + ax], kq[ax]);
             const bool any_bad = __syncthreads_or(bad);     // this or an earlier step of the launch
-            block_sum192(q, red, T >> 6);
+            block_sum192<true>(q, red, T >> 6);
             if (tid == 0) {
                 const size_t rec = steps ? (size_t)(gstep / a.sample_every - 1) : 0;
                 write_record(fa.rec + (rec * a.B + b) * kExactWords, q,
@@ -285,26 +213,13 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_fixed_kernel(BatchFixe
     }
 }
 
-template <int NMAX, int K>
-hipError_t launch_class(const BatchFixedArgs &a, int n_max, int n_blocks, hipStream_t s)
-{
-    static_assert(64 * ((NMAX + 64 * K - 1) / (64 * K)) <= kBatchMaxThreads, "too many threads for the class");
-    hipLaunchKernelGGL((batch_fixed_kernel<NMAX, K>), dim3(n_blocks), dim3(batch_threads(n_max)), 0, s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_batch_fixed(const BatchFixedArgs &a, int n_max, int n_blocks, hipStream_t s)
 {
-    if (n_max <= 0 || n_max > 4096 || n_blocks <= 0) return hipErrorInvalidValue;
-    switch (batch_class(n_max)) {
-    case 0: return launch_class<128, 1>(a, n_max, n_blocks, s);
-    case 1: return launch_class<512, 1>(a, n_max, n_blocks, s);
-    case 2: return launch_class<1024, 1>(a, n_max, n_blocks, s);
-    case 3: return launch_class<2048, 2>(a, n_max, n_blocks, s);
-    default: return launch_class<4096, 4>(a, n_max, n_blocks, s);
-    }
+    return dispatch_class(n_max, n_blocks, [&](auto nmax, auto k) {
+        hipLaunchKernelGGL((batch_fixed_kernel<nmax(), k()>), dim3(n_blocks), dim3(batch_threads(n_max)), 0, s, a);
+    });
 }
 
 }  // namespace ljmdb

@@ -2,7 +2,8 @@
 // pair-distance histogram of the positions resident now, of every replica of a launch, one workgroup per replica.
 //
 // Per replica b, with its own n, L, rmax and dr = rmax / nbins, exactly what ljmd_rdf_histogram (rdf_histogram_kernel,
-// ljmd_kernels.hip) computes for one snapshot of one system -- the reference's numpy arithmetic with its roundings
+// ljmd_kernels.hip) computes for one snapshot of one system, through the same rdf_image and rdf_bin (ljmd_internal.h) --
+// the reference's numpy arithmetic with its roundings
 // (scripts/md_one_run_analysis.py:570-584):
 //   d = x_j - x_i ; d -= L * rint(d / L)      (np.rint = half-to-even; a true division)
 //   r = sqrt(dx*dx + dy*dy + dz*dz)           (unfused, correctly rounded sqrt)
@@ -17,29 +18,13 @@
 // 1.68e7 to a bin) and is added after a barrier into the replica's own row of the handle's 64-bit histogram with plain
 // loads, adds and stores: the workgroup is the row's only writer, and launches on one stream follow one another.
 #include "ljmd_batch.h"
+#include "ljmd_internal.h"
 
 namespace ljmdb {
 namespace {
 
-// ---- restated from ljmd_kernels.hip (which stays untouched): rdf_image and the bin rule of rdf_histogram_kernel ----
-// rint(d / L) without the division: d * (1/L) is within 2 ulp of the true quotient, so its nearest integer is the
-// reference's unless the product sits within 1e-9 of a half-integer -- then the true division decides.
-__device__ __forceinline__ double rdf_image(double d, double L, double invL)
-{
-    const double q = d * invL;
-    double n = __builtin_rint(q);
-    if (fabs(q - n) > 0.5 - 1e-9) n = __builtin_rint(d / L);
-    return n;
-}
-
-// int(r / dr): the product with 1/dr decides unless it lands within 1e-9 of an integer
-__device__ __forceinline__ int rdf_bin(double r, double dr, double inv_dr)
-{
-    const double q = r * inv_dr;
-    int bin = (int)q;
-    if (q - (double)bin < 1e-9 || (double)(bin + 1) - q < 1e-9) bin = (int)(r / dr);
-    return bin;
-}
+using ljmdk::rdf_bin;
+using ljmdk::rdf_image;
 
 template <int NMAX, int K>
 __global__ __launch_bounds__(kBatchMaxThreads) void batch_rdf_kernel(BatchRdfArgs a)
@@ -92,29 +77,16 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_rdf_kernel(BatchRdfArg
     }
 }
 
-template <int NMAX, int K>
-hipError_t launch_class(const BatchRdfArgs &a, int n_max, int n_blocks, hipStream_t s)
-{
-    static_assert(64 * ((NMAX + 64 * K - 1) / (64 * K)) <= kBatchMaxThreads, "too many threads for the class");
-    static_assert(3 * NMAX * sizeof(double) + kBatchRdfMaxBins * sizeof(unsigned) <= 160 * 1024, "LDS of one CU");
-    hipLaunchKernelGGL((batch_rdf_kernel<NMAX, K>), dim3(n_blocks), dim3(batch_threads(n_max)),
-                       (size_t)a.nbins * sizeof(unsigned), s, a);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_batch_rdf(const BatchRdfArgs &a, int n_max, int n_blocks, hipStream_t s)
 {
-    if (n_max <= 0 || n_max > 4096 || n_blocks <= 0 || a.nbins < 1 || a.nbins > kBatchRdfMaxBins)
-        return hipErrorInvalidValue;
-    switch (batch_class(n_max)) {
-    case 0: return launch_class<128, 1>(a, n_max, n_blocks, s);
-    case 1: return launch_class<512, 1>(a, n_max, n_blocks, s);
-    case 2: return launch_class<1024, 1>(a, n_max, n_blocks, s);
-    case 3: return launch_class<2048, 2>(a, n_max, n_blocks, s);
-    default: return launch_class<4096, 4>(a, n_max, n_blocks, s);
-    }
+    if (a.nbins < 1 || a.nbins > kBatchRdfMaxBins) return hipErrorInvalidValue;
+    return dispatch_class(n_max, n_blocks, [&](auto nmax, auto k) {
+        static_assert(3 * nmax() * sizeof(double) + kBatchRdfMaxBins * sizeof(unsigned) <= 160 * 1024, "LDS of one CU");
+        hipLaunchKernelGGL((batch_rdf_kernel<nmax(), k()>), dim3(n_blocks), dim3(batch_threads(n_max)),
+                           (size_t)a.nbins * sizeof(unsigned), s, a);
+    });
 }
 
 }  // namespace ljmdb

@@ -1,4 +1,5 @@
-// ljmd_internal.h -- argument blocks shared by the kernels and the C-ABI host code.
+// ljmd_internal.h -- argument blocks shared by the kernels and the C-ABI host code, and (last section) the device
+// arithmetic shared by the kernel files.
 //
 // HBM layout (all fp64, structure of arrays):
 //   n      total particles, G ranks, S = n / G particles per rank ("shard"),
@@ -309,6 +310,221 @@ hipError_t launch_migrate_select(const double *pos_all, const double *mig_all, c
                                  double *v, double *a, int *gid0, int S, int P, hipStream_t s);
 hipError_t launch_gather3(const double *src, double *dst, const int *idx, int P, hipStream_t s);
 hipError_t launch_gather_perm(const int *src, int *dst, const int *idx, int P, hipStream_t s);
+
+// ---- device arithmetic shared by the kernel files ----
+// The device functions whose exact sequence of roundings is part of the documented results, ONE copy each for
+// ljmd_kernels.hip and the batch kernels (ljmd_batch*.hip): a batch replica equals a single engine bit for bit because
+// both compile this text.  It lives in this file, not in a header of its own, because this is one of the two files whose
+// hash decides whether a committed profile still describes the kernels (bench.py, tools/pmc_*.py).
+// Everything here is built with -ffp-contract=off: FMAs only where the source says fma().
+
+// wave / block reductions with a FIXED combination order: every floating-point sum of the kernels is bitwise
+// reproducible run to run.  The only atomics are integer ones that cannot change a result: the blocks-done ticket of
+// kick_finalize_kernel and the integer histograms of the g(r) kernels.
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;  // valid in lane 0
+}
+
+// Fixed-order sum of NVAL values per thread over the first W waves of the workgroup, wave w of value k parked at
+// lds[k * stride + w].  Every thread of the workgroup calls it (it holds a barrier); waves from W on contribute
+// nothing (the batch kernels: W = the replica's own waves).  The result is valid in thread 0.
+template <int NVAL>
+__device__ __forceinline__ void block_sum(double (&v)[NVAL], double *lds /* [NVAL * stride] */,
+                                          int stride = kWavesPerBlock, int W = kWavesPerBlock)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NVAL; ++k) {
+        const double s = wave_sum(v[k]);
+        if (lane == 0) lds[k * stride + wave] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < NVAL; ++k) {
+            double s = lds[k * stride];
+            for (int w = 1; w < W; ++w) s += lds[k * stride + w];
+            v[k] = s;
+        }
+    }
+}
+
+// FAST path building blocks.  Preconditions (checked on the host):
+//   (a) every coordinate lies within a span < 2.4 L (true after any wrap), so |d/L| < 2.5,
+//       n = rndne(d/L) has |n| <= 2 and L*n is exact: fma(-L, n, d) == d - L*n rounded once,
+//       i.e. the same value the reference computes;
+//   (b) rc <= (1 - 1e-9) L/2: rndne and dnint differ only on exact ties of d/L, where
+//       |d_mic| ~ L/2 > rc, so the pair fails r^2 < rc^2 either way.
+// Differences from the reference per pair, all <= ~1 ulp of the term: r^2 and the force
+// use fma contraction, 1/r^2 is v_rcp_f64 + one Halley step instead of the IEEE divide.
+__device__ __forceinline__ double mic_fast(double d, double L, double invL)
+{
+    return fma(-L, __builtin_rint(d * invL), d);
+}
+
+__device__ __forceinline__ double rcp_newton(double x)
+{
+    // v_rcp_f64 delivers ~24-26 good bits; ONE cubically convergent (Halley) step takes the relative
+    // error e to e^3 (< 2^-70): y = y0 (1 + e + e^2), e = 1 - x y0.  3 fma instead of the 4 of two
+    // Newton steps; result within 1 ulp of the IEEE quotient (tests/test_gpu_parity.py).
+    const double y0 = __builtin_amdgcn_rcp(x);
+    const double e = fma(-x, y0, 1.0);
+    const double t = fma(e, e, e);
+    return fma(y0, t, y0);
+}
+
+// ENERGY = false leaves out the two energy sums (forces-only steps of the batch kernel; the forces are the same bits)
+template <bool EXCLUDE_SELF, bool ENERGY = true>
+__device__ __forceinline__ void pair_fast(double xi, double yi, double zi,
+                                          double xj, double yj, double zj,
+                                          double L, double invL, double rc2, bool is_self,
+                                          double &ax, double &ay, double &az,
+                                          double &s12, double &s6)
+{
+    const double dx = mic_fast(xi - xj, L, invL);
+    const double dy = mic_fast(yi - yj, L, invL);
+    const double dz = mic_fast(zi - zj, L, invL);
+    const double r2 = fma(dz, dz, fma(dy, dy, dx * dx));
+    bool in = r2 < rc2;                                  // strict <; NaN (padding, an unused own slot) never passes
+    if constexpr (EXCLUDE_SELF) in = in && !is_self;
+    if (in) {
+        const double u = rcp_newton(r2);
+        const double u3 = u * u * u;
+        const double u6 = u3 * u3;
+        if constexpr (ENERGY) {
+            s12 += u6;
+            s6 += u3;
+        }
+        const double g = fma(2.0, u6, -u3) * u;          // = -dU_r * inv_r2
+        ax = fma(g, dx, ax);
+        ay = fma(g, dy, ay);
+        az = fma(g, dz, az);
+    }
+}
+
+// First half of a velocity-Verlet step for one coordinate of one particle (drift_kick_kernel, tile_tail_kernel, the
+// batch kernels), every operation rounded on its own, left to right:
+//   r1 = (r0 + v0*dt) + acc*dt_square_half    verlet.f90:58-60
+//   r1 = r1 - L*floor(r1*invL)                geometry_pbc.f90:54-56
+//   d  = mic(r1 - r0)                         md_simulation_program.f90:341-351 (dnint): what the unwrapped position gains
+//   v1 = v0 + acc*dt_half                     verlet.f90:72-74
+// In two parts: the callers store r1 and ru + d before they work out v1 (their instruction schedules depend on it), and
+// the multi-rank engine runs the two in separate launches (drift_kick_kernel: PHASE).
+struct Drift {
+    double r1, d;
+};
+__device__ __forceinline__ Drift drift_wrap(double r0, double v0, double acc, double dt, double dt_sq_half, double L,
+                                            double invL)
+{
+    double r1 = (r0 + v0 * dt) + acc * dt_sq_half;
+    r1 = r1 - L * __builtin_floor(r1 * invL);
+    double d = r1 - r0;
+    d = d - L * __builtin_round(d * invL);
+    return {r1, d};
+}
+
+__device__ __forceinline__ double half_kick(double v0, double acc, double dt_half) { return v0 + acc * dt_half; }
+
+// g(r) pair pass (rdf_histogram_kernel, batch_rdf_kernel).
+// rint(d / L) without the division: d * (1/L) is within 2 ulp of the true quotient, so its nearest integer is the
+// reference's unless the product sits within 1e-9 of a half-integer -- then (practically never) the true
+// division decides.  Same integer, hence the same bits downstream.
+__device__ __forceinline__ double rdf_image(double d, double L, double invL)
+{
+    const double q = d * invL;
+    double n = __builtin_rint(q);
+    if (fabs(q - n) > 0.5 - 1e-9) n = __builtin_rint(d / L);
+    return n;
+}
+
+// int(r / dr): the product with 1/dr decides unless it lands within 1e-9 of an integer
+__device__ __forceinline__ int rdf_bin(double r, double dr, double inv_dr)
+{
+    const double q = r * inv_dr;
+    int bin = (int)q;
+    if (q - (double)bin < 1e-9 || (double)(bin + 1) - q < 1e-9) bin = (int)(r / dr);
+    return bin;
+}
+
+// Reproducible mode (above: "exact fixed-point sums").
+// acc += Q(t), |t| < 2^40.  v = RNE(t 2^64) is an integer-valued double, |v| < 2^104; split exactly at 2^62:
+// hi = trunc(v 2^-62), lo = v - hi 2^62 (|lo| < 2^62, a multiple of ulp(v): representable), both convert exactly.
+__device__ __forceinline__ void fixed_add(__int128 &acc, double t)
+{
+    const double v = __builtin_rint(t * 0x1p64);
+    const double hi = __builtin_trunc(v * 0x1p-62);
+    const double lo = v - hi * 0x1p62;
+    acc += ((__int128)(int64_t)hi << 62) + (__int128)(int64_t)lo;
+}
+
+__device__ __forceinline__ bool fixed_out_of_range(double t) { return !(__builtin_fabs(t) < kFixedBound); }
+
+// Per ordered pair the generic kernel's arithmetic -- the reference's own terms -- every term entering its integer sum
+template <bool ENERGY>
+__device__ __forceinline__ void pair_fixed(double xi, double yi, double zi, double xj, double yj, double zj, double L,
+                                           double invL, double rc2, bool is_self, __int128 &ax, __int128 &ay,
+                                           __int128 &az, __int128 &s12, __int128 &s6, bool &bad)
+{
+    const double dx0 = xi - xj, dy0 = yi - yj, dz0 = zi - zj;
+    const double dx = dx0 - L * __builtin_round(dx0 * invL);          // geometry_pbc.f90:86
+    const double dy = dy0 - L * __builtin_round(dy0 * invL);
+    const double dz = dz0 - L * __builtin_round(dz0 * invL);
+    const double r2 = dx * dx + dy * dy + dz * dz;                    // lj_potential_energy.f90:129
+    if (r2 < rc2 && !is_self) {                                       // :132; NaN (padding, an unused own slot) never passes
+        const double u = 1.0 / r2;                                    // :135
+        const double u3 = u * u * u;                                  // :136
+        const double u6 = u3 * u3;                                    // :137
+        const double mdu = 2.0 * u6 - u3;                             // :143
+        const double fx = mdu * dx * u, fy = mdu * dy * u, fz = mdu * dz * u;   // :148-155
+        // u^3 <= max(1, u^6): the u^6 test covers it, and both instantiations test the same terms
+        const bool oob = fixed_out_of_range(fx) || fixed_out_of_range(fy) || fixed_out_of_range(fz) ||
+                         fixed_out_of_range(u6);
+        bad = bad || oob;
+        fixed_add(ax, oob ? 0.0 : fx);
+        fixed_add(ay, oob ? 0.0 : fy);
+        fixed_add(az, oob ? 0.0 : fz);
+        if constexpr (ENERGY) {
+            fixed_add(s12, oob ? 0.0 : u6);
+            fixed_add(s6, oob ? 0.0 : u3);
+        }
+    }
+}
+
+// Sum of five signed 192-bit values per thread over the first W waves of the workgroup: integer shuffles inside a
+// wave, then the waves through LDS.  Every thread of the workgroup calls it (it holds a barrier), waves from W on must
+// hold zeros; the result is valid in thread 0.  ROLLED keeps the shuffle tree a loop (the batch kernel, whose pair loop
+// leaves no registers to spare); the sum is the same integer either way.
+template <bool ROLLED = false>
+__device__ __forceinline__ void block_sum192(uint64_t (&q)[5][3], uint64_t (*lds)[5][3] /* [>= W] */,
+                                             int W = kWavesPerBlock)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll ROLLED ? 1 : 6
+    for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            uint64_t o[3];
+#pragma unroll
+            for (int w = 0; w < 3; ++w) o[w] = __shfl_down(q[k][w], off, 64);
+            add192(q[k], o);
+        }
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < 5; ++k)
+#pragma unroll
+            for (int w = 0; w < 3; ++w) lds[wave][k][w] = q[k][w];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int v = 1; v < W; ++v)
+#pragma unroll
+            for (int k = 0; k < 5; ++k) {
+                const uint64_t o[3] = {lds[v][k][0], lds[v][k][1], lds[v][k][2]};
+                add192(q[k], o);
+            }
+}
 
 }  // namespace ljmdk
 #endif

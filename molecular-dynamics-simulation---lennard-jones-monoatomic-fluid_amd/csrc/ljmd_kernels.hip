@@ -18,18 +18,7 @@
 
 namespace ljmdk {
 
-// ---------------------------------------------------------------------------
-// wave / block reductions with a FIXED combination order: every floating-point sum in this file
-// is bitwise reproducible run to run.  The only atomics are integer ones that cannot change a result:
-// the blocks-done ticket of kick_finalize_kernel and the integer histogram of rdf_histogram_kernel.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;  // valid in lane 0
-}
-
+// wave reductions beside wave_sum / block_sum (ljmd_internal.h)
 __device__ __forceinline__ double wave_min(double v)
 {
 #pragma unroll
@@ -42,27 +31,6 @@ __device__ __forceinline__ double wave_max(double v)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
     return v;
-}
-
-template <int NVAL>
-__device__ __forceinline__ void block_sum(double (&v)[NVAL], double *lds /* [NVAL*kWavesPerBlock] */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NVAL; ++k) {
-        const double s = wave_sum(v[k]);
-        if (lane == 0) lds[k * kWavesPerBlock + wave] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < NVAL; ++k) {
-            double s = lds[k * kWavesPerBlock];
-#pragma unroll
-            for (int w = 1; w < kWavesPerBlock; ++w) s += lds[k * kWavesPerBlock + w];
-            v[k] = s;
-        }
-    }
 }
 
 // ===========================================================================
@@ -124,58 +92,6 @@ __global__ __launch_bounds__(kBlock) void pair_rows_generic_kernel(PairArgs a)
         double *w = a.wg_part + 2 * ((size_t)blockIdx.y * gridDim.x + blockIdx.x);
         w[0] = v[0];
         w[1] = v[1];
-    }
-}
-
-// ===========================================================================
-// FAST path building blocks.  Preconditions (checked on the host):
-//   (a) every coordinate lies within a span < 2.4 L (true after any wrap), so |d/L| < 2.5,
-//       n = rndne(d/L) has |n| <= 2 and L*n is exact: fma(-L, n, d) == d - L*n rounded once,
-//       i.e. the same value the reference computes;
-//   (b) rc <= (1 - 1e-9) L/2: rndne and dnint differ only on exact ties of d/L, where
-//       |d_mic| ~ L/2 > rc, so the pair fails r^2 < rc^2 either way.
-// Differences from the reference per pair, all <= ~1 ulp of the term: r^2 and the force
-// use fma contraction, 1/r^2 is v_rcp_f64 + one Halley step instead of the IEEE divide.
-// ===========================================================================
-__device__ __forceinline__ double mic_fast(double d, double L, double invL)
-{
-    return fma(-L, __builtin_rint(d * invL), d);
-}
-
-__device__ __forceinline__ double rcp_newton(double x)
-{
-    // v_rcp_f64 delivers ~24-26 good bits; ONE cubically convergent (Halley) step takes the relative
-    // error e to e^3 (< 2^-70): y = y0 (1 + e + e^2), e = 1 - x y0.  3 fma instead of the 4 of two
-    // Newton steps; result within 1 ulp of the IEEE quotient (tests/test_gpu_parity.py).
-    const double y0 = __builtin_amdgcn_rcp(x);
-    const double e = fma(-x, y0, 1.0);
-    const double t = fma(e, e, e);
-    return fma(y0, t, y0);
-}
-
-template <bool EXCLUDE_SELF>
-__device__ __forceinline__ void pair_fast(double xi, double yi, double zi,
-                                          double xj, double yj, double zj,
-                                          double L, double invL, double rc2, bool is_self,
-                                          double &ax, double &ay, double &az,
-                                          double &s12, double &s6)
-{
-    const double dx = mic_fast(xi - xj, L, invL);
-    const double dy = mic_fast(yi - yj, L, invL);
-    const double dz = mic_fast(zi - zj, L, invL);
-    const double r2 = fma(dz, dz, fma(dy, dy, dx * dx));
-    bool in = r2 < rc2;                                  // strict <; NaN (padding) never passes
-    if constexpr (EXCLUDE_SELF) in = in && !is_self;
-    if (in) {
-        const double u = rcp_newton(r2);
-        const double u3 = u * u * u;
-        const double u6 = u3 * u3;
-        s12 += u6;
-        s6 += u3;
-        const double g = fma(2.0, u6, -u3) * u;          // = -dU_r * inv_r2
-        ax = fma(g, dx, ax);
-        ay = fma(g, dy, ay);
-        az = fma(g, dz, az);
     }
 }
 
@@ -904,10 +820,226 @@ __device__ __forceinline__ void n3_tile_pass(const N3Args &a, int lane, int c, i
 #undef LJMD_LOOP
 }
 
-// (defined with the geometry pre-pass below)
+// ---------------------------------------------------------------------------
+// Geometry pre-pass 3 (Newton-3 kernel): one 32-bit descriptor per (owned row group, column tile) -- everything the
+// pair kernel needs to know about a pass, computed ONCE by one lane here instead of redundantly by the 64 lanes of the
+// wave in the pair kernel's prologue (~120 fp64 VALU instructions per pass there, 2 % of the kernel):
+//   bits  0..3   row tiles of the group whose mask bit for this column tile is set (tile_mask_kernel)
+//   bits  4..8   loop variant nu (pair_n3): image class of the (row group, column tile) pair
+//   bit   9      INNER: every pair provably inside the cutoff
+//   bit   10     FULL: no padding slot in the row group or the column tile
+//   bits 11..19  common image per axis, n + 2 in 3 bits each (shift = n L)
+//   bit   20     CLUSTER: the pass runs cluster by cluster (n3_cluster_pass) with the direction / thresholds in desc2
+//   bit   21     PERTILE: the row tiles are shifted by whole box lengths on axis (bits 22-23) for this pass, tile k by
+//                (bits 24 + 2k .. 25 + 2k) - 1; the column tile's common image on that axis is the first active tile's
+//   bits 22..27  (PERTILE clear) straddle passes, nu 27..30: bit 22 + q = axis q straddles a half-box distance, bit 25 + q =
+//                that distance is (n + 1/2) L rather than (n - 1/2) L, n = the axis' image field (pair_disp)
+// Same expressions as the former in-kernel classification; the row group's box is the union of its tiles' exact
+// boxes (= min / max over its 256 particles).
+// ---------------------------------------------------------------------------
+// -> false: the pair kernel does not visit (row group Al, column tile c).  desc_far / desc2: NULL = not wanted.
+// (RT = tiles per row group, a template parameter: the loops over the row tiles unroll and their small arrays stay in registers)
 template <int RT>
 __device__ __forceinline__ bool tile_class(const GeometryArgs &a, double invL, double rc2, int S, int Al, int c,
-                                           unsigned &desc_out, unsigned *desc_far, float *desc2);
+                                           unsigned &desc_out, unsigned *desc_far, float *desc2)
+{
+    {   // only the (row group, column group) pairs the pair kernel visits: offset d = (B - A) mod NG in 0 .. NG / 2,
+        // the pair at exactly NG / 2 from its lower-numbered side (pair_n3_kernel's own_pair)
+        const int NG = a.T / RT, A = a.rank * (a.TB / RT) + Al, B = c / RT;
+        int d = B - A;
+        if (d < 0) d += NG;
+        if (!(d == 0 || 2 * d < NG || (2 * d == NG && (A < B || a.both_ties)))) return false;
+    }
+    double glo[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()};
+    double ghi[3] = {-__builtin_inf(), -__builtin_inf(), -__builtin_inf()};
+    const double *cbx = a.bbox + (size_t)c * kBoxStride;
+    unsigned mb = 0, mb_far = 0;
+    bool vfar = true;
+    for (int k = 0; k < RT; ++k) {
+        const int tl = RT * Al + k, I = a.rank * a.TB + tl;
+        const double *bb = a.bbox + (size_t)I * kBoxStride;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            glo[q] = fmin(glo[q], bb[q]);                      // fmin / fmax ignore the NaN of an all-padding tile
+            ghi[q] = fmax(ghi[q], bb[3 + q]);
+        }
+        // the tile-pair test of tile_mask_kernel (same expressions): the bit is cleared only when the boxes prove every
+        // pair to be outside the cutoff; mixed precision splits the kept pairs into NEAR (fp64) and FAR (fp32)
+        double d2 = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const double g = axis_gap(bb[q] - cbx[3 + q], bb[3 + q] - cbx[q], a.L);
+            d2 += g * g;
+        }
+        bool keep = !(d2 > a.rc2_skin) || (c == I);
+        if (desc_far) {
+            const bool near = (d2 <= a.rsplit2) || (c / RT == I / RT);
+            mb_far |= (unsigned)(keep && !near) << k;
+            if (keep && !near && !(d2 > a.rvfar2)) vfar = false;   // a far row tile closer than the VERY FAR radius
+            keep = keep && near;
+        }
+        mb |= (unsigned)keep << k;
+    }
+    if (mb == 0 && mb_far == 0) {                            // nothing inside the cutoff: the pair kernels look no further
+        desc_out = 0;
+        if (desc_far) desc_far[(size_t)Al * a.T + c] = 0;
+        return true;
+    }
+    double sx = 0.0, sy = 0.0, sz = 0.0;
+    const double lo[3] = {glo[0] - cbx[3], glo[1] - cbx[4], glo[2] - cbx[5]};
+    const double hi[3] = {ghi[0] - cbx[0], ghi[1] - cbx[1], ghi[2] - cbx[2]};
+    const bool ux = uniform_image(lo[0], hi[0], a.L, invL, sx);
+    const bool uy = uniform_image(lo[1], hi[1], a.L, invL, sy);
+    const bool uz = uniform_image(lo[2], hi[2], a.L, invL, sz);
+    int nu = (ux ? 0 : 1) | (uy ? 0 : 2) | (uz ? 0 : 4);
+    // ONE axis without a common image for the row GROUP (its box, 4 tiles, straddles +-L/2 against the column tile): the
+    // row TILES, half as wide, mostly have one each.  Then the column tile takes the image of the first active row tile
+    // and the other row tiles are shifted by -1 / 0 / +1 box lengths for this pass (pair_n3_kernel: shift_rows): the pass
+    // runs the plain loop (3 instructions per pair less than the general minimum image) and may run cluster by cluster.
+    // 19-23 % of the passes of the liquid have a general axis; about half of them go this way.
+    int pq = -1;                                              // the axis, -1 = none
+    int pm[4] = {0, 0, 0, 0};                                  // per row tile: image relative to the first active tile's
+    if (a.pertile_images && !desc_far && RT > 1 && mb != 0 && (nu == 1 || nu == 2 || nu == 4)) {
+        const int q = nu == 1 ? 0 : nu == 2 ? 1 : 2;
+        int nk[4] = {0, 0, 0, 0}, nbase = 0;
+        bool ok = true, have = false;
+        for (int k = 0; k < RT && ok; ++k) {
+            if (!((mb >> k) & 1u)) continue;
+            const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
+            double sk = 0.0;
+            ok = uniform_image(bb[q] - cbx[3 + q], bb[3 + q] - cbx[q], a.L, invL, sk);
+            nk[k] = (int)__builtin_rint(sk * invL);
+            if (ok && !have) { nbase = nk[k]; have = true; }
+            ok = ok && nk[k] - nbase >= -1 && nk[k] - nbase <= 1;
+        }
+        if (ok && have) {
+            pq = q;
+            for (int k = 0; k < RT; ++k) pm[k] = ((mb >> k) & 1u) ? nk[k] - nbase : 0;
+            const double sb = (double)nbase * a.L;
+            if (q == 0) sx = sb; else if (q == 1) sy = sb; else sz = sb;
+            nu = 0;                                             // a common image on every axis now
+        }
+    }
+    // box of row tile k on axis q as the pass sees it
+    auto row_lo = [&](const double *bb, int k, int q) { return bb[q] - (q == pq ? (double)pm[k] * a.L : 0.0); };
+    auto row_hi = [&](const double *bb, int k, int q) { return bb[3 + q] - (q == pq ? (double)pm[k] * a.L : 0.0); };
+    const bool group_full = (RT * Al + RT) * kTile <= S;
+    const bool full = group_full && ((c - (a.G == 1 ? 0 : c / a.TB) * a.TB) + 1) * kTile <= S;
+    // INNER: every pair of every ACTIVE row tile provably inside the cutoff (farthest corners of the exact tile boxes;
+    // the group's box, the union, proves less: 33 % instead of 44 % of the passes of the bench configuration)
+    bool inner = nu == 0 && full && mb != 0;
+    for (int k = 0; k < RT && inner; ++k) {
+        if (!((mb >> k) & 1u)) continue;
+        const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
+        const double sh[3] = {sx, sy, sz};
+        double far2 = 0.0;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const double f = fmax(fabs((row_lo(bb, k, q) - cbx[3 + q]) - sh[q]), fabs((row_hi(bb, k, q) - cbx[q]) - sh[q]));
+            far2 += f * f;
+        }
+        inner = far2 < rc2 * (1.0 - 1e-10);
+    }
+    // Axes without a common image: the straddle form (pair_disp) whenever the range of differences lies strictly inside
+    // ((h - 1) L, (h + 1) L) around the half-integer h = n +- 1/2 it contains -- always, with tile frames, unless a tile is
+    // wider than half the box -- and every such axis of the pass qualifies; else the general minimum image on all axes.
+    unsigned straddle_axes = 0, straddle_signs = 0;
+    if (nu != 0) {
+        bool ok = true;
+        for (int q = 0; q < 3 && ok; ++q) {
+            if (!((nu >> q) & 1)) continue;
+            const double tlo = lo[q] * invL, thi = hi[q] * invL;
+            const double n = __builtin_rint(0.5 * (tlo + thi));         // = sh[q] / L (uniform_image)
+            const bool up = 0.5 * (tlo + thi) >= n;                       // the half-integer on this side of n
+            const double h = up ? n + 0.5 : n - 0.5;
+            ok = fabs(n) <= 2.0 && tlo > h - 1.0 + 1e-9 && thi < h + 1.0 - 1e-9;
+            straddle_axes |= 1u << q;
+            straddle_signs |= (up ? 1u : 0u) << q;
+        }
+        if (ok) {
+            nu = (straddle_axes == 1u) ? 27 : (straddle_axes == 2u) ? 28 : (straddle_axes == 4u) ? 29 : 30;
+        } else {
+            straddle_axes = straddle_signs = 0;
+            sx = sy = sz = 0.0;                                           // rndne finds every image itself
+            nu = 7;
+        }
+    }
+    if (nu == 0) {
+        const int nz = (sx != 0.0 ? 1 : 0) | (sy != 0.0 ? 2 : 0) | (sz != 0.0 ? 4 : 0);
+        nu = nz == 0 ? 8 : nz == 1 ? 16 : nz == 2 ? 17 : nz == 4 ? 18 : 0;   // none / one axis / several
+    }
+    // shift = n L with |n| <= 2 (uniform_image): recover n exactly
+    const int nx = (int)__builtin_rint(sx * invL), ny = (int)__builtin_rint(sy * invL), nzs = (int)__builtin_rint(sz * invL);
+    unsigned cls = ((unsigned)nu << 4) | ((unsigned)inner << 9) | ((unsigned)full << 10) |
+                   ((unsigned)(nx + 2) << 11) | ((unsigned)(ny + 2) << 14) | ((unsigned)(nzs + 2) << 17);
+    if (pq >= 0) {                                            // bit 21: per-tile images; 22-23: the axis; 24..31: image + 1 per row tile
+        cls |= (1u << 21) | ((unsigned)pq << 22);
+        for (int k = 0; k < 4; ++k) cls |= (unsigned)(pm[k] + 1) << (24 + 2 * k);
+    } else {
+        cls |= (straddle_axes << 22) | (straddle_signs << 25);   // (bit 21 clear: these bits name the straddling axes)
+    }
+    // Cluster pass (pair_n3_kernel: n3_cluster_pass): a pass at the cutoff boundary with a common image on every axis, no
+    // padding slot, not inside the diagonal group.  desc2 = the unit direction n from the row group to the (shifted)
+    // column tile, and per row tile k the threshold  thr_k = max over the tile's box of n.x  +  rc  +  margin:
+    // a column particle with  n.(xj + s) > thr_k  is farther than rc from every particle of row tile k.  The margin
+    // (1e-3) covers the fp32 roundings of n, of the kernel's projection and of thr itself (each < 1e-5 at L = 110).
+    if (desc2 && mb != 0 && !inner && full && c / RT != a.rank * (a.TB / RT) + Al &&
+        (nu == 8 || nu == 16 || nu == 17 || nu == 18 || nu == 0)) {
+        double dir[3], len2 = 0.0;
+        const double sh[3] = {sx, sy, sz};
+        if (pq >= 0) {                                         // the group's box as the pass sees it: its tiles shifted
+            glo[pq] = __builtin_inf();
+            ghi[pq] = -__builtin_inf();
+            for (int k = 0; k < RT; ++k) {
+                const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
+                glo[pq] = fmin(glo[pq], row_lo(bb, k, pq));
+                ghi[pq] = fmax(ghi[pq], row_hi(bb, k, pq));
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            dir[q] = (0.5 * (cbx[q] + cbx[3 + q]) + sh[q]) - 0.5 * (glo[q] + ghi[q]);
+            len2 += dir[q] * dir[q];
+        }
+        if (len2 > 1.0) {                                      // (boxes on top of each other: no boundary to speak of)
+            const double inv = 1.0 / sqrt(len2);
+            float nf[3];
+            double nn = 0.0;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                nf[q] = (float)(dir[q] * inv);
+                nn += (double)nf[q] * (double)nf[q];
+            }
+            if (nn <= 1.0 + 1e-6) {
+                float *o = desc2 + ((size_t)Al * a.T + c) * 8;
+                o[0] = nf[0]; o[1] = nf[1]; o[2] = nf[2];
+                const double rc = sqrt(rc2);
+                for (int k = 0; k < RT; ++k) {
+                    const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
+                    double supp = 0.0;
+#pragma unroll
+                    for (int q = 0; q < 3; ++q) supp += fmax((double)nf[q] * row_lo(bb, k, q), (double)nf[q] * row_hi(bb, k, q));
+                    o[3 + k] = (float)(supp + rc + 1e-3);
+                }
+                for (int k = RT; k < 4; ++k) o[3 + k] = 0.0f;
+                o[7] = 0.0f;
+                // ... and only where some cluster CAN be skipped: the largest projection the column tile's box allows
+                // must exceed the threshold of at least one active row tile
+                double colmax = 0.0;
+#pragma unroll
+                for (int q = 0; q < 3; ++q) colmax += fmax((double)nf[q] * (cbx[q] + sh[q]), (double)nf[q] * (cbx[3 + q] + sh[q]));
+                bool useful = false;
+                for (int k = 0; k < RT; ++k) useful = useful || (((mb >> k) & 1u) && colmax > (double)o[3 + k]);
+                if (useful) cls |= 1u << 20;
+            }
+        }
+    }
+    desc_out = mb | cls;
+    // far pass: bit 28 (free here: no per-tile images in the mixed mode) = VERY FAR
+    // (FULL passes only: the kernel multiplies offsets with force sums, and a padding slot's offset is NaN)
+    if (desc_far) desc_far[(size_t)Al * a.T + c] = mb_far | cls | ((unsigned)(vfar && full && mb_far != 0) << 28);
+    return true;
+}
 
 template <int MIN_WAVES, int RT, int W, bool ENERGY>
 __global__ __launch_bounds__(kTile * W, MIN_WAVES) void pair_n3_kernel(N3Args a)
@@ -1450,227 +1582,6 @@ __global__ __launch_bounds__(kBlock) void tile_mask_kernel(GeometryArgs a)
     if (lane == 0) a.mask[(size_t)Il * a.W + w] = word;
 }
 
-// ---------------------------------------------------------------------------
-// Geometry pre-pass 3 (Newton-3 kernel): one 32-bit descriptor per (owned row group, column tile) -- everything the
-// pair kernel needs to know about a pass, computed ONCE by one lane here instead of redundantly by the 64 lanes of the
-// wave in the pair kernel's prologue (~120 fp64 VALU instructions per pass there, 2 % of the kernel):
-//   bits  0..3   row tiles of the group whose mask bit for this column tile is set (tile_mask_kernel)
-//   bits  4..8   loop variant nu (pair_n3): image class of the (row group, column tile) pair
-//   bit   9      INNER: every pair provably inside the cutoff
-//   bit   10     FULL: no padding slot in the row group or the column tile
-//   bits 11..19  common image per axis, n + 2 in 3 bits each (shift = n L)
-//   bit   20     CLUSTER: the pass runs cluster by cluster (n3_cluster_pass) with the direction / thresholds in desc2
-//   bit   21     PERTILE: the row tiles are shifted by whole box lengths on axis (bits 22-23) for this pass, tile k by
-//                (bits 24 + 2k .. 25 + 2k) - 1; the column tile's common image on that axis is the first active tile's
-//   bits 22..27  (PERTILE clear) straddle passes, nu 27..30: bit 22 + q = axis q straddles a half-box distance, bit 25 + q =
-//                that distance is (n + 1/2) L rather than (n - 1/2) L, n = the axis' image field (pair_disp)
-// Same expressions as the former in-kernel classification; the row group's box is the union of its tiles' exact
-// boxes (= min / max over its 256 particles).
-// ---------------------------------------------------------------------------
-// -> false: the pair kernel does not visit (row group Al, column tile c).  desc_far / desc2: NULL = not wanted.
-// (RT = tiles per row group, a template parameter: the loops over the row tiles unroll and their small arrays stay in registers)
-template <int RT>
-__device__ __forceinline__ bool tile_class(const GeometryArgs &a, double invL, double rc2, int S, int Al, int c,
-                                           unsigned &desc_out, unsigned *desc_far, float *desc2)
-{
-    {   // only the (row group, column group) pairs the pair kernel visits: offset d = (B - A) mod NG in 0 .. NG / 2,
-        // the pair at exactly NG / 2 from its lower-numbered side (pair_n3_kernel's own_pair)
-        const int NG = a.T / RT, A = a.rank * (a.TB / RT) + Al, B = c / RT;
-        int d = B - A;
-        if (d < 0) d += NG;
-        if (!(d == 0 || 2 * d < NG || (2 * d == NG && (A < B || a.both_ties)))) return false;
-    }
-    double glo[3] = {__builtin_inf(), __builtin_inf(), __builtin_inf()};
-    double ghi[3] = {-__builtin_inf(), -__builtin_inf(), -__builtin_inf()};
-    const double *cbx = a.bbox + (size_t)c * kBoxStride;
-    unsigned mb = 0, mb_far = 0;
-    bool vfar = true;
-    for (int k = 0; k < RT; ++k) {
-        const int tl = RT * Al + k, I = a.rank * a.TB + tl;
-        const double *bb = a.bbox + (size_t)I * kBoxStride;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            glo[q] = fmin(glo[q], bb[q]);                      // fmin / fmax ignore the NaN of an all-padding tile
-            ghi[q] = fmax(ghi[q], bb[3 + q]);
-        }
-        // the tile-pair test of tile_mask_kernel (same expressions): the bit is cleared only when the boxes prove every
-        // pair to be outside the cutoff; mixed precision splits the kept pairs into NEAR (fp64) and FAR (fp32)
-        double d2 = 0.0;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const double g = axis_gap(bb[q] - cbx[3 + q], bb[3 + q] - cbx[q], a.L);
-            d2 += g * g;
-        }
-        bool keep = !(d2 > a.rc2_skin) || (c == I);
-        if (desc_far) {
-            const bool near = (d2 <= a.rsplit2) || (c / RT == I / RT);
-            mb_far |= (unsigned)(keep && !near) << k;
-            if (keep && !near && !(d2 > a.rvfar2)) vfar = false;   // a far row tile closer than the VERY FAR radius
-            keep = keep && near;
-        }
-        mb |= (unsigned)keep << k;
-    }
-    if (mb == 0 && mb_far == 0) {                            // nothing inside the cutoff: the pair kernels look no further
-        desc_out = 0;
-        if (desc_far) desc_far[(size_t)Al * a.T + c] = 0;
-        return true;
-    }
-    double sx = 0.0, sy = 0.0, sz = 0.0;
-    const double lo[3] = {glo[0] - cbx[3], glo[1] - cbx[4], glo[2] - cbx[5]};
-    const double hi[3] = {ghi[0] - cbx[0], ghi[1] - cbx[1], ghi[2] - cbx[2]};
-    const bool ux = uniform_image(lo[0], hi[0], a.L, invL, sx);
-    const bool uy = uniform_image(lo[1], hi[1], a.L, invL, sy);
-    const bool uz = uniform_image(lo[2], hi[2], a.L, invL, sz);
-    int nu = (ux ? 0 : 1) | (uy ? 0 : 2) | (uz ? 0 : 4);
-    // ONE axis without a common image for the row GROUP (its box, 4 tiles, straddles +-L/2 against the column tile): the
-    // row TILES, half as wide, mostly have one each.  Then the column tile takes the image of the first active row tile
-    // and the other row tiles are shifted by -1 / 0 / +1 box lengths for this pass (pair_n3_kernel: shift_rows): the pass
-    // runs the plain loop (3 instructions per pair less than the general minimum image) and may run cluster by cluster.
-    // 19-23 % of the passes of the liquid have a general axis; about half of them go this way.
-    int pq = -1;                                              // the axis, -1 = none
-    int pm[4] = {0, 0, 0, 0};                                  // per row tile: image relative to the first active tile's
-    if (a.pertile_images && !desc_far && RT > 1 && mb != 0 && (nu == 1 || nu == 2 || nu == 4)) {
-        const int q = nu == 1 ? 0 : nu == 2 ? 1 : 2;
-        int nk[4] = {0, 0, 0, 0}, nbase = 0;
-        bool ok = true, have = false;
-        for (int k = 0; k < RT && ok; ++k) {
-            if (!((mb >> k) & 1u)) continue;
-            const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
-            double sk = 0.0;
-            ok = uniform_image(bb[q] - cbx[3 + q], bb[3 + q] - cbx[q], a.L, invL, sk);
-            nk[k] = (int)__builtin_rint(sk * invL);
-            if (ok && !have) { nbase = nk[k]; have = true; }
-            ok = ok && nk[k] - nbase >= -1 && nk[k] - nbase <= 1;
-        }
-        if (ok && have) {
-            pq = q;
-            for (int k = 0; k < RT; ++k) pm[k] = ((mb >> k) & 1u) ? nk[k] - nbase : 0;
-            const double sb = (double)nbase * a.L;
-            if (q == 0) sx = sb; else if (q == 1) sy = sb; else sz = sb;
-            nu = 0;                                             // a common image on every axis now
-        }
-    }
-    // box of row tile k on axis q as the pass sees it
-    auto row_lo = [&](const double *bb, int k, int q) { return bb[q] - (q == pq ? (double)pm[k] * a.L : 0.0); };
-    auto row_hi = [&](const double *bb, int k, int q) { return bb[3 + q] - (q == pq ? (double)pm[k] * a.L : 0.0); };
-    const bool group_full = (RT * Al + RT) * kTile <= S;
-    const bool full = group_full && ((c - (a.G == 1 ? 0 : c / a.TB) * a.TB) + 1) * kTile <= S;
-    // INNER: every pair of every ACTIVE row tile provably inside the cutoff (farthest corners of the exact tile boxes;
-    // the group's box, the union, proves less: 33 % instead of 44 % of the passes of the bench configuration)
-    bool inner = nu == 0 && full && mb != 0;
-    for (int k = 0; k < RT && inner; ++k) {
-        if (!((mb >> k) & 1u)) continue;
-        const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
-        const double sh[3] = {sx, sy, sz};
-        double far2 = 0.0;
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const double f = fmax(fabs((row_lo(bb, k, q) - cbx[3 + q]) - sh[q]), fabs((row_hi(bb, k, q) - cbx[q]) - sh[q]));
-            far2 += f * f;
-        }
-        inner = far2 < rc2 * (1.0 - 1e-10);
-    }
-    // Axes without a common image: the straddle form (pair_disp) whenever the range of differences lies strictly inside
-    // ((h - 1) L, (h + 1) L) around the half-integer h = n +- 1/2 it contains -- always, with tile frames, unless a tile is
-    // wider than half the box -- and every such axis of the pass qualifies; else the general minimum image on all axes.
-    unsigned straddle_axes = 0, straddle_signs = 0;
-    if (nu != 0) {
-        bool ok = true;
-        for (int q = 0; q < 3 && ok; ++q) {
-            if (!((nu >> q) & 1)) continue;
-            const double tlo = lo[q] * invL, thi = hi[q] * invL;
-            const double n = __builtin_rint(0.5 * (tlo + thi));         // = sh[q] / L (uniform_image)
-            const bool up = 0.5 * (tlo + thi) >= n;                       // the half-integer on this side of n
-            const double h = up ? n + 0.5 : n - 0.5;
-            ok = fabs(n) <= 2.0 && tlo > h - 1.0 + 1e-9 && thi < h + 1.0 - 1e-9;
-            straddle_axes |= 1u << q;
-            straddle_signs |= (up ? 1u : 0u) << q;
-        }
-        if (ok) {
-            nu = (straddle_axes == 1u) ? 27 : (straddle_axes == 2u) ? 28 : (straddle_axes == 4u) ? 29 : 30;
-        } else {
-            straddle_axes = straddle_signs = 0;
-            sx = sy = sz = 0.0;                                           // rndne finds every image itself
-            nu = 7;
-        }
-    }
-    if (nu == 0) {
-        const int nz = (sx != 0.0 ? 1 : 0) | (sy != 0.0 ? 2 : 0) | (sz != 0.0 ? 4 : 0);
-        nu = nz == 0 ? 8 : nz == 1 ? 16 : nz == 2 ? 17 : nz == 4 ? 18 : 0;   // none / one axis / several
-    }
-    // shift = n L with |n| <= 2 (uniform_image): recover n exactly
-    const int nx = (int)__builtin_rint(sx * invL), ny = (int)__builtin_rint(sy * invL), nzs = (int)__builtin_rint(sz * invL);
-    unsigned cls = ((unsigned)nu << 4) | ((unsigned)inner << 9) | ((unsigned)full << 10) |
-                   ((unsigned)(nx + 2) << 11) | ((unsigned)(ny + 2) << 14) | ((unsigned)(nzs + 2) << 17);
-    if (pq >= 0) {                                            // bit 21: per-tile images; 22-23: the axis; 24..31: image + 1 per row tile
-        cls |= (1u << 21) | ((unsigned)pq << 22);
-        for (int k = 0; k < 4; ++k) cls |= (unsigned)(pm[k] + 1) << (24 + 2 * k);
-    } else {
-        cls |= (straddle_axes << 22) | (straddle_signs << 25);   // (bit 21 clear: these bits name the straddling axes)
-    }
-    // Cluster pass (pair_n3_kernel: n3_cluster_pass): a pass at the cutoff boundary with a common image on every axis, no
-    // padding slot, not inside the diagonal group.  desc2 = the unit direction n from the row group to the (shifted)
-    // column tile, and per row tile k the threshold  thr_k = max over the tile's box of n.x  +  rc  +  margin:
-    // a column particle with  n.(xj + s) > thr_k  is farther than rc from every particle of row tile k.  The margin
-    // (1e-3) covers the fp32 roundings of n, of the kernel's projection and of thr itself (each < 1e-5 at L = 110).
-    if (desc2 && mb != 0 && !inner && full && c / RT != a.rank * (a.TB / RT) + Al &&
-        (nu == 8 || nu == 16 || nu == 17 || nu == 18 || nu == 0)) {
-        double dir[3], len2 = 0.0;
-        const double sh[3] = {sx, sy, sz};
-        if (pq >= 0) {                                         // the group's box as the pass sees it: its tiles shifted
-            glo[pq] = __builtin_inf();
-            ghi[pq] = -__builtin_inf();
-            for (int k = 0; k < RT; ++k) {
-                const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
-                glo[pq] = fmin(glo[pq], row_lo(bb, k, pq));
-                ghi[pq] = fmax(ghi[pq], row_hi(bb, k, pq));
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            dir[q] = (0.5 * (cbx[q] + cbx[3 + q]) + sh[q]) - 0.5 * (glo[q] + ghi[q]);
-            len2 += dir[q] * dir[q];
-        }
-        if (len2 > 1.0) {                                      // (boxes on top of each other: no boundary to speak of)
-            const double inv = 1.0 / sqrt(len2);
-            float nf[3];
-            double nn = 0.0;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                nf[q] = (float)(dir[q] * inv);
-                nn += (double)nf[q] * (double)nf[q];
-            }
-            if (nn <= 1.0 + 1e-6) {
-                float *o = desc2 + ((size_t)Al * a.T + c) * 8;
-                o[0] = nf[0]; o[1] = nf[1]; o[2] = nf[2];
-                const double rc = sqrt(rc2);
-                for (int k = 0; k < RT; ++k) {
-                    const double *bb = a.bbox + (size_t)(a.rank * a.TB + RT * Al + k) * kBoxStride;
-                    double supp = 0.0;
-#pragma unroll
-                    for (int q = 0; q < 3; ++q) supp += fmax((double)nf[q] * row_lo(bb, k, q), (double)nf[q] * row_hi(bb, k, q));
-                    o[3 + k] = (float)(supp + rc + 1e-3);
-                }
-                for (int k = RT; k < 4; ++k) o[3 + k] = 0.0f;
-                o[7] = 0.0f;
-                // ... and only where some cluster CAN be skipped: the largest projection the column tile's box allows
-                // must exceed the threshold of at least one active row tile
-                double colmax = 0.0;
-#pragma unroll
-                for (int q = 0; q < 3; ++q) colmax += fmax((double)nf[q] * (cbx[q] + sh[q]), (double)nf[q] * (cbx[3 + q] + sh[q]));
-                bool useful = false;
-                for (int k = 0; k < RT; ++k) useful = useful || (((mb >> k) & 1u) && colmax > (double)o[3 + k]);
-                if (useful) cls |= 1u << 20;
-            }
-        }
-    }
-    desc_out = mb | cls;
-    // far pass: bit 28 (free here: no per-tile images in the mixed mode) = VERY FAR
-    // (FULL passes only: the kernel multiplies offsets with force sums, and a padding slot's offset is NaN)
-    if (desc_far) desc_far[(size_t)Al * a.T + c] = mb_far | cls | ((unsigned)(vfar && full && mb_far != 0) << 28);
-    return true;
-}
-
 template <int RT>
 __global__ __launch_bounds__(kBlock) void tile_class_kernel(GeometryArgs a, double invL, double rc2, int S, unsigned *desc,
                                                             unsigned *desc_far, float *desc2)
@@ -1704,16 +1615,12 @@ __global__ __launch_bounds__(kBlock) void drift_kick_kernel(IntegrateArgs a)
         const size_t o = (size_t)ax * a.P + i;
         const double v0 = a.v[o], acc = a.a[o];
         if constexpr (PHASE != 2) {
-            const double r0 = a.r[o];
-            double r1 = (r0 + v0 * a.dt) + acc * a.dt_sq_half;
-            r1 = r1 - a.L * __builtin_floor(r1 * a.invL);
-            double d = r1 - r0;
-            d = d - a.L * __builtin_round(d * a.invL);
-            a.r[o] = r1;
-            a.ru[o] = a.ru[o] + d;
-            rn[ax] = r1;
+            const Drift h = drift_wrap(a.r[o], v0, acc, a.dt, a.dt_sq_half, a.L, a.invL);
+            a.r[o] = h.r1;
+            a.ru[o] = a.ru[o] + h.d;
+            rn[ax] = h.r1;
         }
-        if constexpr (PHASE != 1) a.v[o] = v0 + acc * a.dt_half;
+        if constexpr (PHASE != 1) a.v[o] = half_kick(v0, acc, a.dt_half);
     }
     if constexpr (BOXES && PHASE != 2) {
         // single rank: the wave holds exactly one tile -- emit its bounding box here (same values, same
@@ -2091,15 +1998,11 @@ __global__ __launch_bounds__(kBlock * TPB) void tile_tail_kernel(ReduceArgs ra, 
             k2 = vel * vel;
         }
         if constexpr (DRIFT) {                                  // drift_kick_kernel<0> of the next step
-            const double r0 = r_in;
-            double r1 = (r0 + vel * a.dt) + acc * a.dt_sq_half;
-            r1 = r1 - a.L * __builtin_floor(r1 * a.invL);
-            double d = r1 - r0;
-            d = d - a.L * __builtin_round(d * a.invL);
-            a.r[o] = r1;
-            a.ru[o] = ru_in + d;
-            rn = r1;
-            vel = vel + acc * a.dt_half;
+            const Drift h = drift_wrap(r_in, vel, acc, a.dt, a.dt_sq_half, a.L, a.invL);
+            a.r[o] = h.r1;
+            a.ru[o] = ru_in + h.d;
+            rn = h.r1;
+            vel = half_kick(vel, acc, a.dt_half);
         }
         if constexpr (KICK || DRIFT) a.v[o] = vel;
         if constexpr (KICK) {
@@ -2158,17 +2061,6 @@ __global__ __launch_bounds__(kBlock * TPB) void tile_tail_kernel(ReduceArgs ra, 
 // One thread per i, j broadcast through scalar loads, histogram in LDS (ds_add_u32), one
 // 64-bit global atomic per bin and block; integer sums are order independent.
 // ===========================================================================
-// rint(d / L) without the division: d * (1/L) is within 2 ulp of the true quotient, so its nearest integer is the
-// reference's unless the product sits within 1e-9 of a half-integer -- then (practically never) the true
-// division decides.  Same integer, hence the same bits downstream.
-__device__ __forceinline__ double rdf_image(double d, double L, double invL)
-{
-    const double q = d * invL;
-    double n = __builtin_rint(q);
-    if (fabs(q - n) > 0.5 - 1e-9) n = __builtin_rint(d / L);
-    return n;
-}
-
 __global__ __launch_bounds__(kBlock) void rdf_histogram_kernel(RdfArgs a)
 {
     extern __shared__ unsigned lhist[];
@@ -2188,10 +2080,7 @@ __global__ __launch_bounds__(kBlock) void rdf_histogram_kernel(RdfArgs a)
         dz = dz - a.L * rdf_image(dz, a.L, a.invL);
         const double r = __builtin_sqrt(dx * dx + dy * dy + dz * dz);
         if (live && j > i && r < a.rmax) {
-            // int(r / dr): the product with 1/dr decides unless it lands within 1e-9 of an integer
-            const double q = r * a.inv_dr;
-            int bin = (int)q;
-            if (q - (double)bin < 1e-9 || (double)(bin + 1) - q < 1e-9) bin = (int)(r / a.dr);
+            const int bin = rdf_bin(r, a.dr, a.inv_dr);
             if (bin < a.nbins) atomicAdd(&lhist[bin], 2u);
         }
     }
@@ -2234,48 +2123,7 @@ __global__ __launch_bounds__(kBlock) void time_origin_kernel(TimeOriginArgs a)
 // Integer sums are exact in any order, so the slice count, the tile order, the re-sort, the rank split and the launch
 // form cannot change a bit of the result.
 // ===========================================================================
-
-// acc += Q(t), |t| < 2^40.  v = RNE(t 2^64) is an integer-valued double, |v| < 2^104; split exactly at 2^62:
-// hi = trunc(v 2^-62), lo = v - hi 2^62 (|lo| < 2^62, a multiple of ulp(v): representable), both convert exactly.
-__device__ __forceinline__ void fixed_add(__int128 &acc, double t)
-{
-    const double v = __builtin_rint(t * 0x1p64);
-    const double hi = __builtin_trunc(v * 0x1p-62);
-    const double lo = v - hi * 0x1p62;
-    acc += ((__int128)(int64_t)hi << 62) + (__int128)(int64_t)lo;
-}
-
-__device__ __forceinline__ bool fixed_out_of_range(double t) { return !(__builtin_fabs(t) < kFixedBound); }
-
-template <bool ENERGY>
-__device__ __forceinline__ void pair_fixed(double xi, double yi, double zi, double xj, double yj, double zj, double L,
-                                           double invL, double rc2, bool is_self, __int128 &ax, __int128 &ay,
-                                           __int128 &az, __int128 &s12, __int128 &s6, bool &bad)
-{
-    const double dx0 = xi - xj, dy0 = yi - yj, dz0 = zi - zj;
-    const double dx = dx0 - L * __builtin_round(dx0 * invL);          // geometry_pbc.f90:86
-    const double dy = dy0 - L * __builtin_round(dy0 * invL);
-    const double dz = dz0 - L * __builtin_round(dz0 * invL);
-    const double r2 = dx * dx + dy * dy + dz * dz;                    // lj_potential_energy.f90:129
-    if (r2 < rc2 && !is_self) {                                       // :132
-        const double u = 1.0 / r2;                                    // :135
-        const double u3 = u * u * u;                                  // :136
-        const double u6 = u3 * u3;                                    // :137
-        const double mdu = 2.0 * u6 - u3;                             // :143
-        const double fx = mdu * dx * u, fy = mdu * dy * u, fz = mdu * dz * u;   // :148-155
-        // u^3 <= max(1, u^6): the u^6 test covers it, and both instantiations test the same terms
-        const bool oob = fixed_out_of_range(fx) || fixed_out_of_range(fy) || fixed_out_of_range(fz) ||
-                         fixed_out_of_range(u6);
-        bad = bad || oob;
-        fixed_add(ax, oob ? 0.0 : fx);
-        fixed_add(ay, oob ? 0.0 : fy);
-        fixed_add(az, oob ? 0.0 : fz);
-        if constexpr (ENERGY) {
-            fixed_add(s12, oob ? 0.0 : u6);
-            fixed_add(s6, oob ? 0.0 : u3);
-        }
-    }
-}
+// (fixed_add, pair_fixed, block_sum192: ljmd_internal.h)
 
 // ---------------------------------------------------------------------------
 // Pair kernel of the reproducible mode: pair_tiles_kernel's structure -- one wave per 64-particle row tile, the
@@ -2334,34 +2182,6 @@ __global__ __launch_bounds__(kBlock) void pair_fixed_kernel(FixedArgs a)
     }
     const uint64_t any_bad = __ballot(bad);
     if (lane == 0) a.fflag[(size_t)blockIdx.y * a.TB + Il] = any_bad != 0ull ? 1u : 0u;
-}
-
-// Block-wide sum of five signed 192-bit values per thread; the result is valid in thread 0.
-__device__ __forceinline__ void block_sum192(uint64_t (&q)[5][3], uint64_t (*lds)[5][3] /* [kWavesPerBlock] */)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            uint64_t o[3];
-#pragma unroll
-            for (int w = 0; w < 3; ++w) o[w] = __shfl_down(q[k][w], off, 64);
-            add192(q[k], o);
-        }
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < 5; ++k)
-#pragma unroll
-            for (int w = 0; w < 3; ++w) lds[wave][k][w] = q[k][w];
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int v = 1; v < kWavesPerBlock; ++v)
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const uint64_t o[3] = {lds[v][k][0], lds[v][k][1], lds[v][k][2]};
-                add192(q[k], o);
-            }
 }
 
 // ---------------------------------------------------------------------------
