@@ -511,7 +511,8 @@ int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on);
  * Setting the mode the handle already has changes nothing.  Works on both kinds of handle. */
 int ljmd_batch_set_precision(ljmd_batch_t *h, int32_t precision_mode);
 /* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL.
- * Both include the g(r) launches of that call (ljmd_batch_rdf_configure with every > 0).
+ * Both include the g(r) and MSD / VACF launches of that call (ljmd_batch_rdf_configure / ljmd_batch_tcf_configure with
+ * every > 0).
  * Replicas of different kernel classes (n <= 128, 512, 1024, 2048, 4096) run as separate groups of launches, by
  * default each on a stream of its own (LJMD_BATCH_GROUP_STREAMS=0: one after another on the handle's stream); the
  * kernel time is then the span from the first group's first launch to the last group's end, not a sum over groups,
@@ -536,6 +537,62 @@ int ljmd_batch_rdf_configure(ljmd_batch_t *h, int32_t nbins, const double *rmax,
 int ljmd_batch_rdf_accumulate(ljmd_batch_t *h);
 int ljmd_batch_rdf_read(ljmd_batch_t *h, uint64_t *hist, int64_t *n_snapshots);
 int ljmd_batch_rdf_reset(ljmd_batch_t *h);
+/*
+ * MSD(tau) and VACF(tau), time-origin averaged, on the device (ljmd_batch_tcf_*) -- compute_msd_tau_timeorig /
+ * compute_vacf_tau_timeorig of the reference (scripts/md_one_run_analysis.py:404-489) for every replica, as exact
+ * integers before their normalisation.
+ *
+ * Definition.  Snapshots of a handle are numbered s = 0, 1, 2, ... from the last configure, reset or
+ * ljmd_batch_set_state; a snapshot is the resident ru and v of every replica at that moment.  1 <= max_lag <=
+ * LJMD_BATCH_TCF_MAX_LAG, origin_stride >= 1, max_lag / origin_stride + 1 <= LJMD_BATCH_TCF_MAX_ORIGINS.  Per replica b,
+ * particle i, origin t0 and lag l, the reference's numpy expressions with no contraction:
+ *   MSD  term: d = ru(t0 + l) - ru(t0) per axis, t = (dx*dx + dy*dy) + dz*dz
+ *   VACF term: t = (vx(t0 + l)*vx(t0) + vy(t0 + l)*vy(t0)) + vz(t0 + l)*vz(t0)
+ * Every term enters an exact signed integer sum as Q(t) = RNE(t 2^64).  Device state per replica: S[kind][l], kind 0 =
+ * MSD, 1 = VACF, l = 0 .. max_lag, each a signed 192-bit integer of three little-endian 64-bit limbs; the host keeps
+ * count[l], the same for all replicas.  When snapshot s arrives:
+ *   1. for every stored origin t0 with t0 % origin_stride == 0 and 1 <= s - t0 <= max_lag:
+ *      S[kind][s - t0] += sum_i Q(term_i), count[s - t0] += 1; if s - t0 == 1 also the lag-0 term of that origin:
+ *      S[kind][0] += sum_i Q(term_i(t0, t0)), count[0] += 1 (the reference does not use the last snapshot as an origin;
+ *      deferring lag 0 to the next snapshot reproduces that for any stopping point);
+ *   2. if s % origin_stride == 0, snapshot s is stored as an origin, in ring slot (s / origin_stride) % slots, slots =
+ *      max_lag / origin_stride + 1.
+ * Result: msd[b][l] = fixed(S[0][l]) / ((double)n_b * (double)count[l]), fixed = ONE correctly rounded conversion of the
+ * integer times 2^-64; vacf from S[1] likewise; 0 where count[l] == 0.  This equals the reference's functions on the same
+ * snapshots to rounding (<= 1e-13 max|value|); the integers themselves are independent of B, slot, launch grouping,
+ * streams, precision mode and the order of the particles.
+ * Range: a term that is not finite or has |t| >= 2^40 enters as 0 and sets a sticky per-replica word in device memory
+ * (an arithmetic flag: nothing wraps, nothing faults); read / read_exact then fail with LJMD_ERR_RANGE, the message
+ * naming the lowest such replica ("replica <b>"), until ljmd_batch_tcf_reset.  Stepping is not affected and the handle
+ * is not poisoned.  n <= 4096 terms below 2^104 fit 128 bits per (snapshot, origin); 192 bits hold any number of origins.
+ *
+ * configure: max_lag = 0 switches the feature off and frees everything; otherwise allocates and zeroes S, the range
+ * words and the origin ring (slots x 6 planes of offsets[B] doubles); calling it again reconfigures and zeroes.  A
+ * failed guard returns LJMD_ERR_INVALID_ARG and leaves the earlier configuration in place; a failed allocation
+ * LJMD_ERR_ALLOC with the feature off.  every > 0: ljmd_batch_steps takes the snapshots after steps every, 2 every, ...
+ * of each call; its nsteps must then be a multiple of every (LJMD_ERR_INVALID_ARG before anything is launched).  With
+ * g(r) configured with an every too, a launch ends at the multiples of either.  r, ru, v, a and the sampled scalars
+ * stay bitwise what they are without the feature; ljmd_batch_profile_read counts the new launches and their time.
+ * accumulate: the resident state is the next snapshot, stream-ordered (no host wait).  LJMD_ERR_STATE before
+ * configure, before ljmd_batch_set_state or on a poisoned handle.
+ * read: waits for the device; msd[B][max_lag + 1], vacf[B][max_lag + 1], counts[max_lag + 1], the number of snapshots
+ * taken since configure / reset -- any pointer may be NULL; clears nothing.  read_exact: words[B][2][max_lag + 1][3]
+ * instead of the two quotients.  Both return LJMD_ERR_STATE before configure.
+ * reset: zeroes the sums, counts, snapshot numbering and range words.
+ * ljmd_batch_set_state starts a new trajectory: the stored origins are dropped and the numbering restarts at 0, the
+ * sums and counts are kept, so several trajectories run one after another on one handle average together.
+ * ljmd_batch_set_precision, ljmd_batch_set_unwrapped and ljmd_batch_set_accel leave everything alone.  If a call that
+ * takes snapshots fails half-way (a poisoned handle), sums and counts are unspecified until ljmd_batch_tcf_reset.
+ * ljmd_tcf_from_exact: one sum of 3 limbs -> fixed(S) / ((double)n * (double)count), 0 for count == 0; host code only.
+ */
+#define LJMD_BATCH_TCF_MAX_LAG 4096
+#define LJMD_BATCH_TCF_MAX_ORIGINS 512
+int ljmd_batch_tcf_configure(ljmd_batch_t *h, int32_t max_lag, int32_t origin_stride, int32_t every);
+int ljmd_batch_tcf_accumulate(ljmd_batch_t *h);
+int ljmd_batch_tcf_read(ljmd_batch_t *h, double *msd, double *vacf, int64_t *counts, int64_t *n_snapshots);
+int ljmd_batch_tcf_read_exact(ljmd_batch_t *h, int64_t *words, int64_t *counts, int64_t *n_snapshots);
+int ljmd_batch_tcf_reset(ljmd_batch_t *h);
+int ljmd_tcf_from_exact(const int64_t *words, int32_t n, int64_t count, double *out);
 
 #ifdef __cplusplus
 }

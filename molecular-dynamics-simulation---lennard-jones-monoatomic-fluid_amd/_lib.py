@@ -130,9 +130,17 @@ PROTOTYPES = {
     "ljmd_batch_rdf_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_batch_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
     "ljmd_batch_rdf_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_tcf_configure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]),
+    "ljmd_batch_tcf_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_tcf_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int64_p, c_int64_p]),
+    "ljmd_batch_tcf_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]),
+    "ljmd_batch_tcf_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_tcf_from_exact": (C.c_int, [c_int64_p, C.c_int32, C.c_int64, c_double_p]),
 }
 
 BATCH_MAX_N = 4096
+BATCH_TCF_MAX_LAG = 4096
+BATCH_TCF_MAX_ORIGINS = 512
 
 _lib = None
 

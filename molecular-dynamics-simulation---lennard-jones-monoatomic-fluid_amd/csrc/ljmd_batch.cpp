@@ -2,7 +2,8 @@
 // device, each with its own (n, L, dt, rc) (ljmd_batch_create: all the same), stepped by one kernel (ljmd_batch.hip)
 // with one workgroup per replica.  Handle lifecycle, guards, device state, launch planning per kernel class and the
 // combination of the per-replica step records, in the fp64 mode and in the reproducible mode (ljmd_batch_fixed.hip:
-// exact integer records, a sticky range flag per replica), and the g(r) accumulation (ljmd_batch_rdf.hip).
+// exact integer records, a sticky range flag per replica), the g(r) accumulation (ljmd_batch_rdf.hip) and the MSD / VACF
+// accumulation (ljmd_batch_tcf.hip).
 #include "ljmd_batch.h"
 #include "ljmd_common.h"
 #include "ljmd_internal.h"
@@ -66,6 +67,14 @@ struct ljmd_batch {
     int64_t rdf_snapshots = 0;
     unsigned long long *d_rdf_hist = nullptr;   // [B][rdf_nbins]
     BatchRdfReplica *d_rdf_table = nullptr;     // [B], replica order
+    // MSD / VACF accumulation (ljmd_batch_tcf_*): off while tcf_max_lag == 0
+    int32_t tcf_max_lag = 0, tcf_stride = 1, tcf_every = 0, tcf_slots = 0;
+    int64_t tcf_s = 0;                // number of the next snapshot of this trajectory (0 after ljmd_batch_set_state)
+    int64_t tcf_snapshots = 0;        // snapshots since configure / reset, over all trajectories
+    std::vector<int64_t> tcf_counts;  // [max_lag + 1] origins that contributed to each lag: the same for all replicas
+    uint64_t *d_tcf_sums = nullptr;   // [B][2][max_lag + 1][3] signed 192-bit
+    int32_t *d_tcf_range = nullptr;   // [B] sticky until ljmd_batch_tcf_reset
+    double *d_tcf_ring = nullptr;     // [slots][6][offsets[B]]: ru and v of the stored origins
     std::string err;
 };
 
@@ -95,6 +104,8 @@ using ljmdk::kExactWords;
 using ljmdk::kFlagNoEnergy;
 using ljmdk::kFlagNoKinetic;
 static_assert(kExactWords == LJMD_EXACT_PARTIAL_WORDS, "exact record layout out of sync with include/ljmd.h");
+static_assert(kBatchTcfMaxLag == LJMD_BATCH_TCF_MAX_LAG && kBatchTcfMaxOrigins == LJMD_BATCH_TCF_MAX_ORIGINS,
+              "MSD / VACF limits out of sync with include/ljmd.h");
 
 bool reproducible(const ljmd_batch *h) { return h->mode == LJMD_PRECISION_FP64_REPRODUCIBLE; }
 size_t rec_words(const ljmd_batch *h) { return reproducible(h) ? kExactWords : kBatchRecWords; }
@@ -229,13 +240,75 @@ int enqueue_rdf(ljmd_batch *h, const BatchGroup &g, hipStream_t s, int32_t *coun
     return LJMD_OK;
 }
 
+// The live origins of snapshot s: the multiples t0 of the stride with 1 <= s - t0 <= max_lag (BatchTcfArgs)
+struct TcfLive {
+    int n_live = 0, lag_first = 0, slot_first = 0, store_slot = -1;
+};
+TcfLive tcf_live(const ljmd_batch *h, int64_t s)
+{
+    const int64_t stride = h->tcf_stride, lo = std::max<int64_t>(0, s - h->tcf_max_lag);
+    const int64_t first = (lo + stride - 1) / stride * stride, last = s >= 1 ? (s - 1) / stride * stride : -1;
+    TcfLive l;
+    if (last >= first) {
+        l.n_live = (int)((last - first) / stride) + 1;
+        l.lag_first = (int)(s - first);
+        l.slot_first = (int)(first / stride % h->tcf_slots);
+    }
+    if (s % stride == 0) l.store_slot = (int)(s / stride % h->tcf_slots);
+    return l;
+}
+
+// the MSD / VACF launch of group g on stream s_: the resident ru and v as snapshot number snap -- one launch per group
+int enqueue_tcf(ljmd_batch *h, const BatchGroup &g, hipStream_t s_, int64_t snap, int32_t *count, const char *who)
+{
+    const TcfLive l = tcf_live(h, snap);
+    if (l.n_live == 0 && l.store_slot < 0) return LJMD_OK;
+    BatchTcfArgs ta{};
+    ta.state = h->d_state;
+    ta.ring = h->d_tcf_ring;
+    ta.sums = h->d_tcf_sums;
+    ta.range = h->d_tcf_range;
+    ta.rep = h->d_table;
+    ta.plane = h->total;
+    ta.g0 = (int)g.first;
+    ta.max_lag = h->tcf_max_lag;
+    ta.stride = h->tcf_stride;
+    ta.slots = h->tcf_slots;
+    ta.n_live = l.n_live;
+    ta.lag_first = l.lag_first;
+    ta.slot_first = l.slot_first;
+    ta.store_slot = l.store_slot;
+    const hipError_t e = launch_batch_tcf(ta, g.n_max, (int)g.count, s_);
+    ++*count;
+    if (e != hipSuccess) {
+        h->poisoned = true;
+        return fail(h, LJMD_ERR_HIP, "%s: MSD / VACF launch failed: %s; the handle is poisoned until ljmd_batch_set_state",
+                     who, hipGetErrorString(e));
+    }
+    return LJMD_OK;
+}
+
+// the host's share of one snapshot, once every group's launch is enqueued: the counts and the numbering
+void tcf_advance(ljmd_batch *h)
+{
+    const TcfLive l = tcf_live(h, h->tcf_s);
+    for (int e = 0; e < l.n_live; ++e) {
+        const int lag = l.lag_first - e * h->tcf_stride;
+        ++h->tcf_counts[(size_t)lag];
+        if (lag == 1) ++h->tcf_counts[0];
+    }
+    ++h->tcf_s;
+    ++h->tcf_snapshots;
+}
+
 // one pass of the kernel over every replica in `mode`: nsteps steps (kModeSteps) or one evaluation.  Group by group,
 // launches of at most chunk replicas and steps_per_launch steps, in the order steps-outer, replicas-inner.  With
 // concurrent groups every group runs on its own stream between a fork from and a join into the handle's stream, so
 // what the handle's stream does next (the record copy) follows all of them.  A failed launch poisons the handle.
 // rdf_every > 0 (kModeSteps only): a launch ends at the steps rdf_every, 2 rdf_every, ..., and the group's g(r)
-// launches follow it on the same stream; 0 is the launch sequence without g(r).
-int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int rdf_every, int32_t *launches, const char *who)
+// launches follow it on the same stream; 0 is the launch sequence without g(r).  tcf_every > 0: the same for the
+// MSD / VACF snapshots, numbered on from h->tcf_s (the caller advances the numbering afterwards).
+int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int rdf_every, int tcf_every, int32_t *launches, const char *who)
 {
     if (h->concurrent) {
         LJMD_HIP(h, hipEventRecord(h->fork, h->stream));
@@ -249,6 +322,7 @@ int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int rdf_every, int32_t *l
         for (int s0 = 0, len = 0; s0 < (steps ? nsteps : 1); s0 += len) {
             len = std::min(spl, (steps ? nsteps : 1) - s0);
             if (rdf_every > 0) len = std::min(len, rdf_every - s0 % rdf_every);
+            if (tcf_every > 0) len = std::min(len, tcf_every - s0 % tcf_every);
             a.step0 = s0;
             a.nsteps = steps ? len : 0;
             for (size_t c0 = 0; c0 < g.count; c0 += g.chunk) {
@@ -269,6 +343,10 @@ int run_groups(ljmd_batch *h, BatchArgs a, int nsteps, int rdf_every, int32_t *l
             }
             if (rdf_every > 0 && (s0 + len) % rdf_every == 0) {
                 const int rc_ = enqueue_rdf(h, g, s, &count, who);
+                if (rc_ != LJMD_OK) return rc_;
+            }
+            if (tcf_every > 0 && (s0 + len) % tcf_every == 0) {
+                const int rc_ = enqueue_tcf(h, g, s, h->tcf_s + (s0 + len) / tcf_every - 1, &count, who);
                 if (rc_ != LJMD_OK) return rc_;
             }
         }
@@ -292,6 +370,58 @@ void rdf_release(ljmd_batch *h)
     h->rdf_nbins = 0;
     h->rdf_every = 0;
     h->rdf_snapshots = 0;
+}
+
+// releases the MSD / VACF buffers after what may still use them
+void tcf_release(ljmd_batch *h)
+{
+    if (h->stream && (h->d_tcf_sums || h->d_tcf_range || h->d_tcf_ring)) (void)hipStreamSynchronize(h->stream);
+    if (h->d_tcf_sums) (void)hipFree(h->d_tcf_sums);
+    if (h->d_tcf_range) (void)hipFree(h->d_tcf_range);
+    if (h->d_tcf_ring) (void)hipFree(h->d_tcf_ring);
+    h->d_tcf_sums = nullptr;
+    h->d_tcf_range = nullptr;
+    h->d_tcf_ring = nullptr;
+    h->tcf_max_lag = 0;
+    h->tcf_stride = 1;
+    h->tcf_every = 0;
+    h->tcf_slots = 0;
+    h->tcf_s = 0;
+    h->tcf_snapshots = 0;
+    h->tcf_counts.clear();
+}
+
+size_t tcf_sum_words(const ljmd_batch *h) { return h->B * 2 * ((size_t)h->tcf_max_lag + 1) * 3; }
+
+// the guards shared by ljmd_batch_tcf_read and ljmd_batch_tcf_read_exact, then the device's sums in h_words: waits for
+// the device; a set range word fails the call and names the lowest such replica
+int tcf_fetch(ljmd_batch *h, std::vector<uint64_t> *h_words, const char *who)
+{
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (h->tcf_max_lag == 0) return fail(h, LJMD_ERR_STATE, "%s: call ljmd_batch_tcf_configure first", who);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    std::vector<int32_t> range;
+    try {
+        range.resize(h->B);
+        if (h_words) h_words->resize(tcf_sum_words(h));
+    } catch (const std::bad_alloc &) {
+        return fail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+    }
+    hipError_t e = hipMemcpyAsync(range.data(), h->d_tcf_range, h->B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && h_words)
+        e = hipMemcpyAsync(h_words->data(), h->d_tcf_sums, h_words->size() * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                           h->stream);
+    const hipError_t s = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess || s != hipSuccess) {
+        h->poisoned = true;
+        return fail(h, LJMD_ERR_HIP, "%s: kernel or copy failed: %s; the handle is poisoned until ljmd_batch_set_state",
+                     who, hipGetErrorString(e != hipSuccess ? e : s));
+    }
+    for (size_t b = 0; b < h->B; ++b)
+        if (range[b] != 0)
+            return fail(h, LJMD_ERR_RANGE, "%s: replica %zu: an MSD or VACF term was not finite or |term| >= 2^40 and "
+                                           "entered as 0; the flag stays until ljmd_batch_tcf_reset", who, b);
+    return LJMD_OK;
 }
 
 // the handle from its replicas' parameters, after the guards and the probe: groups, stream(s), device memory
@@ -486,6 +616,7 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
     if (h->d_table) (void)hipFree(h->d_table);
     if (h->d_range) (void)hipFree(h->d_range);
     rdf_release(h);
+    tcf_release(h);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -538,6 +669,7 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
     LJMD_HIP(h, hipStreamSynchronize(h->stream));
     h->have_state = true;
     h->have_accel = false;
+    h->tcf_s = 0;                     // a new trajectory: no stored origin is live; the sums and counts stay
     return LJMD_OK;
 }
 
@@ -600,7 +732,7 @@ int ljmd_batch_compute_forces(ljmd_batch_t *h, double *epot, double *d_epot, dou
         return fail(h, LJMD_ERR_STATE, "ljmd_batch_compute_forces: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
     LJMD_HIP(h, hipSetDevice(h->device));
-    int rc_ = run_groups(h, base_args(h, kModeForces), 0, 0, nullptr, "ljmd_batch_compute_forces");
+    int rc_ = run_groups(h, base_args(h, kModeForces), 0, 0, 0, nullptr, "ljmd_batch_compute_forces");
     if (rc_ != LJMD_OK) return rc_;
     rc_ = fetch_records(h, 1, "ljmd_batch_compute_forces");
     if (rc_ != LJMD_OK) return rc_;
@@ -619,7 +751,7 @@ int ljmd_batch_kinetic_energy(ljmd_batch_t *h, double *ekin)
         return fail(h, LJMD_ERR_STATE, "ljmd_batch_kinetic_energy: handle poisoned by an earlier failure; call "
                                         "ljmd_batch_set_state");
     LJMD_HIP(h, hipSetDevice(h->device));
-    int rc_ = run_groups(h, base_args(h, kModeKinetic), 0, 0, nullptr, "ljmd_batch_kinetic_energy");
+    int rc_ = run_groups(h, base_args(h, kModeKinetic), 0, 0, 0, nullptr, "ljmd_batch_kinetic_energy");
     if (rc_ != LJMD_OK) return rc_;
     rc_ = fetch_records(h, 1, "ljmd_batch_kinetic_energy");
     if (rc_ != LJMD_OK) return rc_;
@@ -656,6 +788,10 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     if (rdf_every > 0 && nsteps % rdf_every != 0)
         return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: nsteps %d is not a multiple of the g(r) interval %d "
                                               "(ljmd_batch_rdf_configure: every)", nsteps, rdf_every);
+    const int tcf_every = h->tcf_max_lag > 0 ? h->tcf_every : 0;
+    if (tcf_every > 0 && nsteps % tcf_every != 0)
+        return fail(h, LJMD_ERR_INVALID_ARG, "ljmd_batch_steps: nsteps %d is not a multiple of the MSD / VACF interval "
+                                              "%d (ljmd_batch_tcf_configure: every)", nsteps, tcf_every);
     if (nsteps == 0) return LJMD_OK;
     LJMD_HIP(h, hipSetDevice(h->device));
     const size_t samples = sampling ? (size_t)(nsteps / sample_every) : 0;
@@ -665,9 +801,11 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
     a.sample_every = sampling ? sample_every : 0;
     int32_t launches = 0;
     LJMD_HIP(h, hipEventRecord(h->ev[0], h->stream));
-    rc_ = run_groups(h, a, nsteps, rdf_every, &launches, "ljmd_batch_steps");
+    rc_ = run_groups(h, a, nsteps, rdf_every, tcf_every, &launches, "ljmd_batch_steps");
     if (rc_ != LJMD_OK) return rc_;
     if (rdf_every > 0) h->rdf_snapshots += nsteps / rdf_every;
+    if (tcf_every > 0)
+        for (int k = 0; k < nsteps / tcf_every; ++k) tcf_advance(h);
     LJMD_HIP(h, hipEventRecord(h->ev[1], h->stream));
     rc_ = fetch_records(h, samples, "ljmd_batch_steps");
     if (rc_ != LJMD_OK) return rc_;
@@ -815,6 +953,137 @@ int ljmd_batch_rdf_reset(ljmd_batch_t *h)
     LJMD_HIP(h, hipSetDevice(h->device));
     LJMD_HIP(h, hipMemsetAsync(h->d_rdf_hist, 0, h->B * (size_t)h->rdf_nbins * sizeof(unsigned long long), h->stream));
     h->rdf_snapshots = 0;
+    return LJMD_OK;
+}
+
+// ---- MSD / VACF accumulation -----------------------------------------------------------------------------------------
+
+int ljmd_batch_tcf_configure(ljmd_batch_t *h, int32_t max_lag, int32_t origin_stride, int32_t every)
+{
+    static const char *who = "ljmd_batch_tcf_configure";
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (max_lag < 0 || max_lag > kBatchTcfMaxLag)
+        return fail(h, LJMD_ERR_INVALID_ARG, "%s: max_lag = %d outside 1..%d (0 switches MSD / VACF off)", who, max_lag,
+                     kBatchTcfMaxLag);
+    if (every < 0) return fail(h, LJMD_ERR_INVALID_ARG, "%s: every must be >= 0", who);
+    if (max_lag > 0 && origin_stride < 1) return fail(h, LJMD_ERR_INVALID_ARG, "%s: origin_stride must be >= 1", who);
+    if (max_lag > 0 && max_lag / origin_stride + 1 > kBatchTcfMaxOrigins)
+        return fail(h, LJMD_ERR_INVALID_ARG, "%s: max_lag / origin_stride + 1 = %d exceeds LJMD_BATCH_TCF_MAX_ORIGINS "
+                                              "(%d)", who, max_lag / origin_stride + 1, kBatchTcfMaxOrigins);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    tcf_release(h);
+    if (max_lag == 0) return LJMD_OK;
+    const int32_t slots = max_lag / origin_stride + 1;
+    const size_t sbytes = h->B * 2 * ((size_t)max_lag + 1) * 3 * sizeof(uint64_t), fbytes = h->B * sizeof(int32_t);
+    const size_t rbytes = (size_t)slots * 6 * h->total * sizeof(double);
+    auto body = [&]() -> int {
+        try {
+            h->tcf_counts.assign((size_t)max_lag + 1, 0);
+        } catch (const std::bad_alloc &) {
+            return fail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+        }
+        if (hipMalloc(&h->d_tcf_sums, sbytes) != hipSuccess) {
+            h->d_tcf_sums = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of sums", who, sbytes);
+        }
+        if (hipMalloc(&h->d_tcf_range, fbytes) != hipSuccess) {
+            h->d_tcf_range = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of range words", who, fbytes);
+        }
+        if (hipMalloc(&h->d_tcf_ring, rbytes) != hipSuccess) {
+            h->d_tcf_ring = nullptr;
+            return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of the origin ring (%d slots)", who, rbytes,
+                         slots);
+        }
+        LJMD_HIP(h, hipMemsetAsync(h->d_tcf_sums, 0, sbytes, h->stream));
+        LJMD_HIP(h, hipMemsetAsync(h->d_tcf_range, 0, fbytes, h->stream));
+        LJMD_HIP(h, hipMemsetAsync(h->d_tcf_ring, 0, rbytes, h->stream));
+        return LJMD_OK;
+    };
+    const int rc_ = body();
+    if (rc_ != LJMD_OK) {
+        (void)hipGetLastError();
+        tcf_release(h);
+        return rc_;
+    }
+    h->tcf_max_lag = max_lag;
+    h->tcf_stride = origin_stride;
+    h->tcf_every = every;
+    h->tcf_slots = slots;
+    return LJMD_OK;
+}
+
+int ljmd_batch_tcf_accumulate(ljmd_batch_t *h)
+{
+    static const char *who = "ljmd_batch_tcf_accumulate";
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (h->tcf_max_lag == 0) return fail(h, LJMD_ERR_STATE, "%s: call ljmd_batch_tcf_configure first", who);
+    if (!h->have_state) return fail(h, LJMD_ERR_STATE, "%s: no state has been set", who);
+    if (h->poisoned)
+        return fail(h, LJMD_ERR_STATE, "%s: handle poisoned by an earlier failure; call ljmd_batch_set_state", who);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    int32_t count = 0;
+    for (const BatchGroup &g : h->groups) {
+        const int rc_ = enqueue_tcf(h, g, h->stream, h->tcf_s, &count, who);
+        if (rc_ != LJMD_OK) return rc_;
+    }
+    tcf_advance(h);
+    return LJMD_OK;
+}
+
+int ljmd_tcf_from_exact(const int64_t *words, int32_t n, int64_t count, double *out)
+{
+    if (!words || !out) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_tcf_from_exact: NULL argument");
+    if (n < 1 || count < 0) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_tcf_from_exact: n must be >= 1, count >= 0");
+    const uint64_t x[3] = {(uint64_t)words[0], (uint64_t)words[1], (uint64_t)words[2]};
+    // one rounding of the integer, one division (n count < 2^53: the product is exact)
+    *out = count == 0 ? 0.0 : ljmdk::fixed_to_double(x) / ((double)n * (double)count);
+    return LJMD_OK;
+}
+
+int ljmd_batch_tcf_read(ljmd_batch_t *h, double *msd, double *vacf, int64_t *counts, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_batch_tcf_read";
+    std::vector<uint64_t> w;
+    const int rc_ = tcf_fetch(h, msd || vacf ? &w : nullptr, who);
+    if (rc_ != LJMD_OK) return rc_;
+    const size_t rows = (size_t)h->tcf_max_lag + 1;
+    double *const dst[2] = {msd, vacf};
+    for (size_t b = 0; b < h->B; ++b)
+        for (int kind = 0; kind < 2; ++kind)
+            for (size_t l = 0; dst[kind] && l < rows; ++l) {
+                int64_t x[3];
+                std::memcpy(x, w.data() + ((b * 2 + kind) * rows + l) * 3, sizeof x);
+                (void)ljmd_tcf_from_exact(x, h->rep[b].n, h->tcf_counts[l], dst[kind] + b * rows + l);
+            }
+    if (counts) std::copy(h->tcf_counts.begin(), h->tcf_counts.end(), counts);
+    if (n_snapshots) *n_snapshots = h->tcf_snapshots;
+    return LJMD_OK;
+}
+
+int ljmd_batch_tcf_read_exact(ljmd_batch_t *h, int64_t *words, int64_t *counts, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_batch_tcf_read_exact";
+    std::vector<uint64_t> w;
+    const int rc_ = tcf_fetch(h, words ? &w : nullptr, who);
+    if (rc_ != LJMD_OK) return rc_;
+    if (words) std::memcpy(words, w.data(), w.size() * sizeof(uint64_t));
+    if (counts) std::copy(h->tcf_counts.begin(), h->tcf_counts.end(), counts);
+    if (n_snapshots) *n_snapshots = h->tcf_snapshots;
+    return LJMD_OK;
+}
+
+int ljmd_batch_tcf_reset(ljmd_batch_t *h)
+{
+    static const char *who = "ljmd_batch_tcf_reset";
+    if (!h) return fail(nullptr, LJMD_ERR_INVALID_ARG, "%s: NULL handle", who);
+    if (h->tcf_max_lag == 0) return fail(h, LJMD_ERR_STATE, "%s: call ljmd_batch_tcf_configure first", who);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    LJMD_HIP(h, hipMemsetAsync(h->d_tcf_sums, 0, tcf_sum_words(h) * sizeof(uint64_t), h->stream));
+    LJMD_HIP(h, hipMemsetAsync(h->d_tcf_range, 0, h->B * sizeof(int32_t), h->stream));
+    std::fill(h->tcf_counts.begin(), h->tcf_counts.end(), 0);
+    h->tcf_s = 0;
+    h->tcf_snapshots = 0;
     return LJMD_OK;
 }
 

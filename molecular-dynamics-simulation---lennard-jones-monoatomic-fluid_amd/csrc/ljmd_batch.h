@@ -114,6 +114,29 @@ struct BatchRdfArgs {
 };
 hipError_t launch_batch_rdf(const BatchRdfArgs &a, int n_max, int n_blocks, hipStream_t s);
 
+// MSD / VACF accumulation (ljmd_batch_tcf.hip): one snapshot -- every replica's resident ru and v -- against the live
+// origins of the ring, the exact integer sums of Q(term) added to the replica's rows of sums; the snapshot is then stored
+// as an origin when its number is a multiple of the origin stride.  Same launch geometry as launch_batch.  The host
+// derives the live origins from the snapshot number s: origin e = 0 .. n_live - 1 is the snapshot t0 = t0_first +
+// e * stride, at lag s - t0 = lag_first - e * stride (1 <= lag <= max_lag), in ring slot (slot_first + e) % slots.  When
+// the newest origin is at lag 1 its lag-0 terms are added too.
+constexpr int kBatchTcfMaxLag = 4096;                  // LJMD_BATCH_TCF_MAX_LAG
+constexpr int kBatchTcfMaxOrigins = 512;               // LJMD_BATCH_TCF_MAX_ORIGINS: ring slots = max_lag / stride + 1
+struct BatchTcfArgs {
+    const double *state;    // [12][plane]: ru = planes 3..5, v = planes 6..8
+    double *ring;           // [slots][6][plane]: ru (3 planes) and v (3 planes) of the stored origins
+    uint64_t *sums;         // [B][2][max_lag + 1][3] signed 192-bit: kind 0 = MSD, 1 = VACF; replica b's rows are
+                            // written by its workgroup alone
+    int32_t *range;         // [B] sticky: set to 1 when a term of replica b was out of range
+    const BatchReplica *rep;
+    size_t plane;
+    int g0;
+    int max_lag, stride, slots;
+    int n_live, lag_first, slot_first;
+    int store_slot;         // ring slot that takes this snapshot, or -1: not an origin
+};
+hipError_t launch_batch_tcf(const BatchTcfArgs &a, int n_max, int n_blocks, hipStream_t s);
+
 }  // namespace ljmdb
 
 #endif  // LJMD_BATCH_KERNEL_H

@@ -1,0 +1,174 @@
+// ljmd_batch_tcf.hip -- gfx950 kernel of the batch engine's MSD / VACF accumulation (include/ljmd.h: ljmd_batch_tcf_*):
+// one snapshot of every replica of a launch against the origins stored in the ring, one workgroup per replica.
+//
+// Per replica, particle i, live origin t0 and lag l = s - t0 the reference's numpy expressions, unfused
+// (scripts/md_one_run_analysis.py:404-489; compiled with -ffp-contract=off, csrc/Makefile):
+//   MSD : d = ru(s) - ru(t0) per axis ; t = (dx*dx + dy*dy) + dz*dz
+//   VACF: t = (vx(s)*vx(t0) + vy(s)*vy(t0)) + vz(s)*vz(t0)
+// Every term enters an exact integer sum as Q(t) = RNE(t 2^64), |t| < 2^40 (else it enters as 0 and the replica's
+// sticky range word is set).  Integer sums depend on no order: not on B, on the replica's slot, on the grouping into
+// launches, on the streams, on the precision mode or on the order of the particles.
+//
+// Shape: the batch kernels' (ljmd_batch.hip), without a pair loop and without positions in LDS: the kernel streams.  A
+// thread tid < T = batch_threads(n) owns particles tid, tid + T, ... (K of them) and keeps their current ru and v in
+// registers (6 K doubles); per live origin it reads its own elements of the ring slot (coalesced) and forms the two
+// terms.  Q(t) is an integer-valued double below 2^104, split exactly at 2^52 into two int64 limbs; a wave's 64 K <= 256
+// terms sum to less than 2^60 per limb, so the limbs are reduced by integer shuffles, and lane 0 adds the wave's 128-bit
+// total into the origin's LDS entry: two 64-bit integer LDS adds, the carry of the low word taken from the value the
+// first add returns.  No barrier per origin.  After ONE barrier the workgroup adds its entries into its own rows of the
+// 192-bit sums with plain loads, add192 and stores: it is the rows' only writer, and launches on one stream follow
+// one another.  No global atomics, no floating-point atomics.  LDS: 32 bytes per live origin, one entry more for the
+// lag-0 terms: at most 513 * 32 = 16416 bytes.
+#include "ljmd_batch.h"
+#include "ljmd_internal.h"
+
+namespace ljmdb {
+namespace {
+
+using ljmdk::add192;
+using ljmdk::fixed_out_of_range;
+
+// hi 2^52 + lo += Q(t); an out-of-range term enters as 0
+__device__ __forceinline__ void tcf_add(long long &hi, long long &lo, double t, bool &bad)
+{
+    const bool oob = fixed_out_of_range(t);
+    bad = bad || oob;
+    const double v = __builtin_rint((oob ? 0.0 : t) * 0x1p64);    // integer-valued, |v| < 2^104
+    const double h = __builtin_trunc(v * 0x1p-52);                 // |h| < 2^52
+    hi += (long long)h;
+    lo += (long long)(v - h * 0x1p52);                             // |.| < 2^52, a multiple of ulp(v): exact
+}
+
+__device__ __forceinline__ long long wave_sum_i64(long long v)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;  // valid in lane 0
+}
+
+// lane 0 of a wave: entry += hi 2^52 + lo as a 128-bit integer {low word, high word}
+__device__ __forceinline__ void entry_add(unsigned long long *entry, long long hi, long long lo)
+{
+    const __int128 x = (__int128)hi * ((__int128)1 << 52) + (__int128)lo;
+    const unsigned long long x0 = (unsigned long long)x, x1 = (unsigned long long)(x >> 64);
+    const unsigned long long old = atomicAdd(&entry[0], x0);
+    const unsigned long long carry = (unsigned long long)(old + x0 < old);
+    atomicAdd(&entry[1], x1 + carry);
+}
+
+template <int NMAX, int K>
+__global__ __launch_bounds__(kBatchMaxThreads) void batch_tcf_kernel(BatchTcfArgs a)
+{
+    extern __shared__ unsigned long long acc[];     // [n_live (+ 1)][2 kinds][2 words]
+    const BatchReplica &rp = a.rep[a.g0 + blockIdx.x];
+    const int n = rp.n, T = rp.threads, tid = threadIdx.x;
+    const size_t plane = a.plane, base = rp.off;
+    const int n_live = a.n_live;
+    const bool lag0 = n_live > 0 && a.lag_first - (n_live - 1) * a.stride == 1;   // the newest origin is at lag 1
+    const int n_ent = n_live + (lag0 ? 1 : 0);
+
+    for (int k = tid; k < 4 * n_ent; k += blockDim.x) acc[k] = 0ull;
+    __syncthreads();
+
+    bool bad = false;
+    if (tid < T) {     // wave-uniform (T is a multiple of 64); the waves from T on own nothing
+        const int lane = tid & 63;
+        double cur[K][6];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int i = tid + k * T;
+#pragma unroll
+            for (int c = 0; c < 6; ++c) cur[k][c] = i < n ? a.state[(size_t)(3 + c) * plane + base + i] : 0.0;
+        }
+        int slot = a.slot_first;
+#pragma unroll 1
+        for (int e = 0; e < n_live; ++e) {
+            const double *const o = a.ring + (size_t)slot * 6 * plane + base;
+            slot = slot + 1 == a.slots ? 0 : slot + 1;
+            const bool with0 = lag0 && e == n_live - 1;
+            long long m_hi = 0, m_lo = 0, c_hi = 0, c_lo = 0;       // MSD and VACF limbs of this origin
+            long long z_hi = 0, z_lo = 0, w_hi = 0, w_lo = 0;       // ... and of its lag 0
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int i = tid + k * T;
+                const bool live = i < n;
+                double org[6];
+#pragma unroll
+                for (int c = 0; c < 6; ++c) org[c] = live ? o[(size_t)c * plane + i] : 0.0;
+                const double dx = cur[k][0] - org[0], dy = cur[k][1] - org[1], dz = cur[k][2] - org[2];
+                tcf_add(m_hi, m_lo, (dx * dx + dy * dy) + dz * dz, bad);
+                tcf_add(c_hi, c_lo, (cur[k][3] * org[3] + cur[k][4] * org[4]) + cur[k][5] * org[5], bad);
+                if (with0) {                                         // uniform across the workgroup
+                    const double ex = org[0] - org[0], ey = org[1] - org[1], ez = org[2] - org[2];
+                    tcf_add(z_hi, z_lo, (ex * ex + ey * ey) + ez * ez, bad);
+                    tcf_add(w_hi, w_lo, (org[3] * org[3] + org[4] * org[4]) + org[5] * org[5], bad);
+                }
+            }
+            m_hi = wave_sum_i64(m_hi);
+            m_lo = wave_sum_i64(m_lo);
+            c_hi = wave_sum_i64(c_hi);
+            c_lo = wave_sum_i64(c_lo);
+            if (with0) {
+                z_hi = wave_sum_i64(z_hi);
+                z_lo = wave_sum_i64(z_lo);
+                w_hi = wave_sum_i64(w_hi);
+                w_lo = wave_sum_i64(w_lo);
+            }
+            if (lane == 0) {
+                entry_add(acc + 4 * e, m_hi, m_lo);
+                entry_add(acc + 4 * e + 2, c_hi, c_lo);
+                if (with0) {
+                    entry_add(acc + 4 * n_live, z_hi, z_lo);
+                    entry_add(acc + 4 * n_live + 2, w_hi, w_lo);
+                }
+            }
+        }
+        // the snapshot becomes an origin: the slot's lag would be slots * stride > max_lag, so it was not read above,
+        // and a thread touches only its own particles' elements
+        if (a.store_slot >= 0) {
+            double *const o = a.ring + (size_t)a.store_slot * 6 * plane + base;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const int i = tid + k * T;
+                if (i < n)
+#pragma unroll
+                    for (int c = 0; c < 6; ++c) o[(size_t)c * plane + i] = cur[k][c];
+            }
+        }
+    }
+    if (bad) a.range[rp.b] = 1;
+    __syncthreads();
+
+    const int rows = a.max_lag + 1;
+    for (int k = tid; k < 2 * n_ent; k += blockDim.x) {
+        const int e = k >> 1, kind = k & 1;
+        const int lag = e < n_live ? a.lag_first - e * a.stride : 0;
+        if (lag < 0 || lag >= rows) continue;     // cannot happen with the host's arguments
+        const unsigned long long x0 = acc[4 * e + 2 * kind], x1 = acc[4 * e + 2 * kind + 1];
+        const uint64_t add[3] = {x0, x1, (long long)x1 < 0 ? ~0ull : 0ull};
+        uint64_t *const row = a.sums + (((size_t)rp.b * 2 + kind) * rows + lag) * 3;
+        uint64_t sum[3] = {row[0], row[1], row[2]};
+        add192(sum, add);
+        row[0] = sum[0];
+        row[1] = sum[1];
+        row[2] = sum[2];
+    }
+}
+
+}  // namespace
+
+hipError_t launch_batch_tcf(const BatchTcfArgs &a, int n_max, int n_blocks, hipStream_t s)
+{
+    if (a.max_lag < 1 || a.max_lag > kBatchTcfMaxLag || a.stride < 1 || a.slots < 1 || a.slots > kBatchTcfMaxOrigins ||
+        a.n_live < 0 || a.n_live > a.slots || a.slot_first < 0 || a.slot_first >= a.slots || a.store_slot >= a.slots)
+        return hipErrorInvalidValue;
+    if (a.n_live > 0 && (a.lag_first > a.max_lag || a.lag_first - (a.n_live - 1) * a.stride < 1))
+        return hipErrorInvalidValue;
+    return dispatch_class(n_max, n_blocks, [&](auto nmax, auto k) {
+        static_assert((kBatchTcfMaxOrigins + 1) * 32 <= 24 * 1024, "LDS budget of the accumulators");
+        hipLaunchKernelGGL((batch_tcf_kernel<nmax(), k()>), dim3(n_blocks), dim3(batch_threads(n_max)),
+                           (size_t)(a.n_live + 1) * 32, s, a);
+    });
+}
+
+}  // namespace ljmdb

@@ -27,6 +27,8 @@ module ljmd_c_api
   public :: ljmd_batch_set_unwrapped, ljmd_batch_get_state, ljmd_batch_compute_forces, ljmd_batch_kinetic_energy
   public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_set_precision, ljmd_batch_profile_read
   public :: ljmd_batch_rdf_configure, ljmd_batch_rdf_accumulate, ljmd_batch_rdf_read, ljmd_batch_rdf_reset
+  public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
+  public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -346,6 +348,53 @@ module ljmd_c_api
     function ljmd_batch_rdf_reset(handle) bind(C, name="ljmd_batch_rdf_reset") result(status)
       import :: c_int, c_ptr
       type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    ! MSD / VACF on the device (ljmd.h: ljmd_batch_tcf_*); msd, vacf [max_lag + 1, B], counts [max_lag + 1],
+    ! words [3, max_lag + 1, 2, B] in Fortran order; c_null_ptr skips an output
+    function ljmd_batch_tcf_configure(handle, max_lag, origin_stride, every) bind(C, name="ljmd_batch_tcf_configure") &
+        result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_lag, origin_stride, every
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_tcf_accumulate(handle) bind(C, name="ljmd_batch_tcf_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_tcf_read(handle, msd, vacf, counts, n_snapshots) bind(C, name="ljmd_batch_tcf_read") &
+        result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, msd, vacf, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_tcf_read_exact(handle, words, counts, n_snapshots) bind(C, name="ljmd_batch_tcf_read_exact") &
+        result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_tcf_reset(handle) bind(C, name="ljmd_batch_tcf_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_tcf_from_exact(words, n, count, out) bind(C, name="ljmd_tcf_from_exact") result(status)
+      import :: c_int, c_int32_t, c_int64_t, c_double
+      integer(c_int64_t), intent(in) :: words(3)
+      integer(c_int32_t), value :: n
+      integer(c_int64_t), value :: count
+      real(c_double), intent(out) :: out
       integer(c_int) :: status
     end function
   end interface

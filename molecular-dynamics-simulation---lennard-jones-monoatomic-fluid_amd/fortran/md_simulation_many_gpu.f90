@@ -22,7 +22,12 @@
 ! with LJMD_REPRODUCIBLE=1), LJMD_RDF_BINS (default 0 = off; nbins > 0: g(r) of every run on the device,
 ! ljmd_batch_rdf_*: the pair-distance histogram up to L/2 of all particles is accumulated at every sampling instant that
 ! writes an rva.dat record, and outputs/run_NNNN/rdf_gpu.dat gets nbins lines of bin centre, integer count (2 per
-! unordered pair) and g(r) with the reference's normalisation, scripts/md_one_run_analysis.py:586-594).
+! unordered pair) and g(r) with the reference's normalisation, scripts/md_one_run_analysis.py:586-594),
+! LJMD_TCF_MAX_LAG (default 0 = off; > 0: MSD(tau) and VACF(tau) of every run on the device, ljmd_batch_tcf_*, time-origin
+! averaged as compute_msd_tau_timeorig / compute_vacf_tau_timeorig, scripts/md_one_run_analysis.py:404-489, over the
+! sampling instants that write an rva.dat record, every LJMD_TCF_ORIGIN_STRIDE-th of them (default 1) an origin;
+! outputs/run_NNNN/msd_vacf_gpu.dat gets a header line and, per lag with at least one origin, lag, lag * output_interval *
+! dt, the number of origins, MSD and VACF).
 ! Batches take n <= LJMD_BATCH_MAX_N.
 !==============================================================================
 program md_simulation_many_gpu
@@ -62,6 +67,10 @@ program md_simulation_many_gpu
   integer :: rdf_bins
   integer(c_int64_t), allocatable, target :: rdf_hist(:, :)     ! [rdf_bins, n_runs]
   integer(c_int64_t) :: rdf_snapshots
+  integer :: tcf_max_lag, tcf_stride
+  real(c_double), allocatable, target :: tcf_msd(:, :), tcf_vacf(:, :)     ! [tcf_max_lag + 1, n_runs]
+  integer(c_int64_t), allocatable, target :: tcf_counts(:)
+  integer(c_int64_t) :: tcf_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -82,6 +91,14 @@ program md_simulation_many_gpu
   call get_environment_variable('LJMD_RDF_BINS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) rdf_bins
   if (rdf_bins < 0) stop 'md_simulation_many: LJMD_RDF_BINS must be >= 0.'
+  tcf_max_lag = 0
+  call get_environment_variable('LJMD_TCF_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) tcf_max_lag
+  if (tcf_max_lag < 0) stop 'md_simulation_many: LJMD_TCF_MAX_LAG must be >= 0.'
+  tcf_stride = 1
+  call get_environment_variable('LJMD_TCF_ORIGIN_STRIDE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) tcf_stride
+  if (tcf_stride < 1) stop 'md_simulation_many: LJMD_TCF_ORIGIN_STRIDE must be >= 1.'
 
   allocate(rparams(n_runs), own_params(n_runs), off(n_runs + 1), time_run(n_runs))
   allocate(s_epot(n_runs), s_ekin(n_runs), s_depot(n_runs), s_ddepot(n_runs))
@@ -129,6 +146,9 @@ program md_simulation_many_gpu
                                              c_loc(vz)), batch, 'ljmd_batch_set_state')
   if (rdf_bins > 0) call ljmd_batch_check(ljmd_batch_rdf_configure(batch, int(rdf_bins, c_int32_t), c_null_ptr, &
                                                                    0_c_int32_t), batch, 'ljmd_batch_rdf_configure')
+  if (tcf_max_lag > 0) call ljmd_batch_check(ljmd_batch_tcf_configure(batch, int(tcf_max_lag, c_int32_t), &
+                                                                      int(tcf_stride, c_int32_t), 0_c_int32_t), batch, &
+                                             'ljmd_batch_tcf_configure')
   ! t = 0 forces and energies of every run (:236-243)
   call ljmd_batch_check(ljmd_batch_compute_forces(batch, c_loc(s_epot), c_loc(s_depot), c_loc(s_ddepot)), batch, &
                         'ljmd_batch_compute_forces')
@@ -166,6 +186,7 @@ program md_simulation_many_gpu
     if (step <= warmup_steps) cycle
     num_samples = num_samples + 1
     if (rdf_bins > 0) call ljmd_batch_check(ljmd_batch_rdf_accumulate(batch), batch, 'ljmd_batch_rdf_accumulate')
+    if (tcf_max_lag > 0) call ljmd_batch_check(ljmd_batch_tcf_accumulate(batch), batch, 'ljmd_batch_tcf_accumulate')
     call ljmd_batch_check(ljmd_batch_get_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(ux), c_loc(uy), &
                                                c_loc(uz), c_loc(vx), c_loc(vy), c_loc(vz), c_loc(ax), c_loc(ay), &
                                                c_loc(az)), batch, 'ljmd_batch_get_state')
@@ -190,6 +211,11 @@ program md_simulation_many_gpu
     allocate(rdf_hist(rdf_bins, n_runs))
     call ljmd_batch_check(ljmd_batch_rdf_read(batch, c_loc(rdf_hist), rdf_snapshots), batch, 'ljmd_batch_rdf_read')
   end if
+  if (tcf_max_lag > 0) then
+    allocate(tcf_msd(0:tcf_max_lag, n_runs), tcf_vacf(0:tcf_max_lag, n_runs), tcf_counts(0:tcf_max_lag))
+    call ljmd_batch_check(ljmd_batch_tcf_read(batch, c_loc(tcf_msd), c_loc(tcf_vacf), c_loc(tcf_counts), &
+                                              tcf_snapshots), batch, 'ljmd_batch_tcf_read')
+  end if
   call ljmd_batch_destroy(batch)
   do i = 1, n_runs
     close(iu_out(i))
@@ -209,6 +235,11 @@ program md_simulation_many_gpu
   if (rdf_bins > 0) then
     do i = 1, n_runs
       call write_rdf(i)
+    end do
+  end if
+  if (tcf_max_lag > 0) then
+    do i = 1, n_runs
+      call write_msd_vacf(i)
     end do
   end if
   if (any_own) then
@@ -274,6 +305,22 @@ contains
     end do
     close(iu_rdf)
   end subroutine write_rdf
+
+  ! run i's msd_vacf_gpu.dat: per lag with at least one origin, lag, tau = lag * output_interval * dt of the run, the
+  ! origins, MSD and VACF (ljmd_batch_tcf_read)
+  subroutine write_msd_vacf(irun)
+    integer, intent(in) :: irun
+    integer :: iu_tcf, ierr, lag
+    open(newunit=iu_tcf, file=trim(run_dir(irun)) // '/msd_vacf_gpu.dat', status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'md_simulation_many: cannot open msd_vacf_gpu.dat of a run.'
+    write(iu_tcf, '(a)') '# lag   tau   origins   MSD   VACF'
+    do lag = 0, tcf_max_lag
+      if (tcf_counts(lag) <= 0) cycle
+      write(iu_tcf, '(i0,2x,es24.16e3,2x,i0,2(2x,es24.16e3))') lag, dble(lag) * dble(output_interval) * rparams(irun)%dt, &
+        tcf_counts(lag), tcf_msd(lag, irun), tcf_vacf(lag, irun)
+    end do
+    close(iu_tcf)
+  end subroutine write_msd_vacf
 
   ! run i's rv_init.dat: record 1 = rx ry rz, record 2 = vx vy vz (md_initial_config_program.f90:285-286)
   subroutine read_rv_init(irun)

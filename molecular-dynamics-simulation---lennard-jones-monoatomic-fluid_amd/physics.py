@@ -543,6 +543,59 @@ class BatchEngine:
     def rdf_reset(self) -> None:
         self._ck(self._lib.ljmd_batch_rdf_reset(self._h))
 
+    # -- MSD / VACF on the device ------------------------------------------
+    def tcf_configure(self, max_lag: int, origin_stride: int = 1, every: int = 0) -> None:
+        """ljmd_batch_tcf_configure: time-origin averaged MSD(tau) and VACF(tau) of every replica up to lag max_lag (in
+        snapshots), every origin_stride-th snapshot an origin; every > 0: steps() takes the snapshots after steps every,
+        2 every, ... by itself.  max_lag = 0 switches the feature off.  Zeroes the sums."""
+        for name, val in (("max_lag", max_lag), ("origin_stride", origin_stride), ("every", every)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise TypeError(f"tcf_configure: {name} must be an integer, got {val!r}")
+        self._ck(self._lib.ljmd_batch_tcf_configure(self._h, int(max_lag), int(origin_stride), int(every)))
+        self._tcf_max_lag = int(max_lag)
+
+    def tcf_accumulate(self) -> None:
+        """takes every replica's resident ru and v as the next snapshot (no host wait)"""
+        self._ck(self._lib.ljmd_batch_tcf_accumulate(self._h))
+
+    def _tcf_rows(self, who: str) -> int:
+        max_lag = getattr(self, "_tcf_max_lag", 0)
+        if max_lag < 1:
+            raise ValueError(f"{who}: call tcf_configure with max_lag >= 1 first")
+        return max_lag + 1
+
+    def tcf_read(self):
+        """-> (msd[B, max_lag + 1], vacf[B, max_lag + 1], counts[max_lag + 1] int64, n_snapshots); nothing is cleared"""
+        rows = self._tcf_rows("tcf_read")
+        msd = np.empty((self.n_replicas, rows), dtype=np.float64)
+        vacf = np.empty((self.n_replicas, rows), dtype=np.float64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_tcf_read(self._h, _ptr(msd), _ptr(vacf), counts.ctypes.data_as(_lib.c_int64_p),
+                                               C.byref(snaps)))
+        return msd, vacf, counts, snaps.value
+
+    def tcf_read_exact(self, raw: bool = False):
+        """-> (sums, counts, n_snapshots): the exact integer sums of Q(term) = RNE(term 2^64), sums[b, kind, lag] with
+        kind 0 = MSD, 1 = VACF, as Python ints in an object array -- or, raw=True, the library's int64 words
+        [B, 2, max_lag + 1, 3] (three little-endian limbs of a signed 192-bit integer)"""
+        rows = self._tcf_rows("tcf_read_exact")
+        words = np.empty((self.n_replicas, 2, rows, 3), dtype=np.int64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_tcf_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p),
+                                                     counts.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        if raw:
+            return words, counts, snaps.value
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:3], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums, counts, snaps.value
+
+    def tcf_reset(self) -> None:
+        self._ck(self._lib.ljmd_batch_tcf_reset(self._h))
+
     @staticmethod
     def per_replica(params_list, device: int = 0,
                     precision_mode: int = _lib.PRECISION_FP64) -> "PerReplicaBatchEngine":
