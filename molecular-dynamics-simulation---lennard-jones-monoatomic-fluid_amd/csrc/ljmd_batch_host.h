@@ -1,0 +1,156 @@
+// ljmd_batch_host.h -- what the host files of the batch engine share (ljmd_batch.cpp: lifecycle, planning, step loop;
+// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF): the handle, the entry guard, the poison and allocation
+// helpers, and the form in which the step loop sees an accumulator.  Host code only; the kernels' side is ljmd_batch.h.
+#ifndef LJMD_BATCH_HOST_H
+#define LJMD_BATCH_HOST_H
+
+#include "ljmd_batch.h"
+#include "ljmd_common.h"
+#include "ljmd_internal.h"
+
+#include <algorithm>
+#include <array>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace ljmdb __attribute__((visibility("hidden"))) {   // host-only: no symbol of libljmd.so
+
+// one replica's parameters and derived constants (host side)
+struct BatchRep : ljmdh::SimParams {
+    int n = 0;
+};
+
+// the replicas of one kernel class: entries [first, first + count) of the replica table, launched chunk replicas and
+// steps_per_launch steps at a time (launch_shape of n_max, the group's largest n)
+struct BatchGroup {
+    size_t first = 0, count = 0;
+    int n_max = 0;
+    size_t chunk = 0;
+    int steps_per_launch = 0;
+    size_t rdf_chunk = 0;             // replicas per g(r) launch: launch_shape's pair bound of the fp64 mode, one step
+    hipStream_t stream = nullptr;     // own stream when the handle runs its groups concurrently, else the handle's
+    hipEvent_t done = nullptr;
+};
+
+// g(r) accumulation (ljmd_batch_rdf.cpp): off while nbins == 0, and every is 0 then
+struct BatchRdf {
+    int32_t nbins = 0, every = 0;
+    int64_t snapshots = 0;
+    unsigned long long *d_hist = nullptr;   // [B][nbins]
+    BatchRdfReplica *d_table = nullptr;     // [B], replica order
+};
+
+// MSD / VACF accumulation (ljmd_batch_tcf.cpp): off while max_lag == 0, and every is 0 then
+struct BatchTcf {
+    int32_t max_lag = 0, stride = 1, every = 0, slots = 0;
+    int64_t s = 0;                    // number of the next snapshot of this trajectory (0 after ljmd_batch_set_state)
+    int64_t snapshots = 0;            // snapshots since configure / reset, over all trajectories
+    std::vector<int64_t> counts;      // [max_lag + 1] origins that contributed to each lag: the same for all replicas
+    uint64_t *d_sums = nullptr;       // [B][2][max_lag + 1][3] signed 192-bit
+    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_tcf_reset
+    double *d_ring = nullptr;         // [slots][6][offsets[B]]: ru and v of the stored origins
+};
+
+}  // namespace ljmdb
+
+struct ljmd_batch {
+    size_t B = 0;
+    size_t total = 0;                 // offsets[B]: elements of one plane
+    int device = 0;
+    std::vector<ljmdb::BatchRep> rep; // [B], replica order
+    std::vector<int64_t> offsets;     // [B + 1]
+    std::vector<ljmdb::BatchGroup> groups;   // by kernel class, ascending
+    bool concurrent = false;          // groups on streams of their own, joined before the records are fetched
+    int mode = LJMD_PRECISION_FP64;   // or LJMD_PRECISION_FP64_REPRODUCIBLE (ljmd_batch_set_precision)
+    bool tail_on = true;
+    bool have_state = false, have_accel = false;
+    bool poisoned = false;            // a launch failed half-way: LJMD_ERR_STATE until ljmd_batch_set_state
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipEvent_t fork = nullptr;
+    ljmdb::BatchReplica *d_table = nullptr;  // [B], the groups' entries one after another
+    double *d_state = nullptr;        // [12][offsets[B]]
+    double *d_rec = nullptr;          // [samples][B][rec_words]: doubles, or int64 words in the reproducible mode
+    size_t rec_cap = 0;               // 8-byte words the record buffer holds (>= B * kExactWords)
+    std::vector<double> h_rec;
+    int32_t *d_range = nullptr;       // [B] reproducible mode: sticky range flags, cleared by ljmd_batch_set_state
+    std::vector<int32_t> h_range;
+    double last_ms = 0.0;             // kernel time of the last ljmd_batch_steps call
+    int32_t last_launches = 0;
+    ljmdb::BatchRdf rdf;
+    ljmdb::BatchTcf tcf;
+    std::string err;
+};
+
+namespace ljmdb __attribute__((visibility("hidden"))) {
+
+using ljmdh::fail;
+
+inline bool reproducible(const ljmd_batch *h) { return h->mode == LJMD_PRECISION_FP64_REPRODUCIBLE; }
+inline double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
+
+// What an entry point requires before it starts, checked in this order after the NULL handle: configured g(r),
+// configured MSD / VACF, a state, valid accelerations, no poison (LJMD_ERR_STATE each); kNeedDevice: the handle's device
+// is then made current (ljmd_batch.cpp)
+enum BatchNeed : unsigned { kNeedRdf = 1, kNeedTcf = 2, kNeedState = 4, kNeedAccel = 8, kNeedSound = 16, kNeedDevice = 32 };
+int enter(ljmd_batch *h, const char *who, unsigned need);
+
+// fails the call as fail() does and poisons the handle: LJMD_ERR_STATE from the guarded calls until ljmd_batch_set_state
+inline int poison(ljmd_batch *h, int code, const char *fmt, ...)
+{
+    h->poisoned = true;
+    va_list ap;
+    va_start(ap, fmt);
+    ljmdh::failv(&h->err, code, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+// `bytes` of device memory in *p, or *p = NULL and "<who>: cannot allocate <bytes> bytes of <what>"
+template <class T>
+int device_alloc(ljmd_batch *h, T **p, size_t bytes, const char *who, const char *what)
+{
+    if (hipMalloc(p, bytes) == hipSuccess) return LJMD_OK;
+    *p = nullptr;
+    return fail(h, LJMD_ERR_ALLOC, "%s: cannot allocate %zu bytes of %s", who, bytes, what);
+}
+
+// grow() sizes host containers; std::bad_alloc becomes "<who>: out of host memory" (h may be NULL)
+template <class F>
+int host_alloc(const ljmd_batch *h, const char *who, F &&grow)
+{
+    try {
+        grow();
+    } catch (const std::bad_alloc &) {
+        return fail(h, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+    }
+    return LJMD_OK;
+}
+
+// An accumulator as the step loop sees it (run_groups, ljmd_batch_steps): a launch ends at the steps every, 2 every, ...
+// of the call, the group's enqueue follows it on the same stream, and ran() does the host's share after the whole call.
+struct BatchAccumulator {
+    int every = 0;                    // steps between two snapshots of ljmd_batch_steps; 0: off, or not taken by it
+    const char *name = nullptr;       // "g(r)": "... is not a multiple of the g(r) interval"
+    const char *tag = nullptr;        // "rdf": ljmd_batch_rdf_configure
+    // the launches of group g on stream s for snapshot k (0-based) of this call; counts them; a failure poisons
+    int (*enqueue)(ljmd_batch *h, const BatchGroup &g, hipStream_t s, int k, int32_t *count, const char *who) = nullptr;
+    void (*ran)(ljmd_batch *h, int snapshots) = nullptr;
+};
+BatchAccumulator rdf_accumulator(const ljmd_batch *h);    // ljmd_batch_rdf.cpp
+BatchAccumulator tcf_accumulator(const ljmd_batch *h);    // ljmd_batch_tcf.cpp
+using BatchAccumulators = std::array<BatchAccumulator, 2>;
+inline BatchAccumulators accumulators(const ljmd_batch *h) { return {rdf_accumulator(h), tcf_accumulator(h)}; }
+
+// one snapshot of the resident state outside ljmd_batch_steps, on the handle's stream (ljmd_batch_*_accumulate)
+int accumulate_now(ljmd_batch *h, const BatchAccumulator &a, const char *who);
+
+// frees what ljmd_batch_*_configure allocated and switches the accumulator off (ljmd_batch_destroy)
+void rdf_release(ljmd_batch *h);
+void tcf_release(ljmd_batch *h);
+
+}  // namespace ljmdb
+#endif

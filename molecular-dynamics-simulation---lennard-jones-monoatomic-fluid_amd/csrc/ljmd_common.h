@@ -83,7 +83,7 @@ SimParams derive_params(int n, double box_length, double dt, double rc);
 void scalars_from_sums(double s12, double s6, double kx, double ky, double kz, double te, double td, double tdd,
                        double *epot, double *ekin, double *d_epot, double *dd_epot);
 
-// The reproducible mode's form (ljmd_records.cpp), shared by the engine and the batch engine: `ordered` holds the exact
+// The reproducible mode's form, shared by the engine (ljmd_records.cpp) and the batch engine: `ordered` holds the exact
 // sums {S12, S6 over the ORDERED pairs, Kx, Ky, Kz}, signed 192-bit integers in units of 2^-64 as three little-endian
 // limbs.  The pair sums are halved and combined as integers, then ONE rounding per scalar, then the tail constants.
 // have_e / have_k false (the record carries no energy / kinetic sums): those scalars are NaN.

@@ -1,61 +1,9 @@
-// ljmd_plan.cpp -- what an engine decides once, when it is created, from (n, n_ranks, precision mode) and the environment:
-// the table of LJMD_* knobs and the launch plan of its three kernel families.  Host arithmetic only: no HIP call, and no
-// getenv outside read_knobs().
+// ljmd_plan.cpp -- what an engine decides once, when it is created, from (n, n_ranks, precision mode) and the table of
+// LJMD_* knobs (read_knobs, ljmd_common.cpp): the launch plan of its three kernel families.  Host arithmetic only: no HIP
+// call and no getenv.
 #include "ljmd_engine.h"
 
 namespace ljmdh {
-
-Knobs read_knobs()
-{
-    auto flag = [](const char *name, bool dflt) { return env_int(name, dflt ? 1 : 0) != 0; };
-    auto is = [](const char *name, const char *value) {
-        const char *v = std::getenv(name);
-        return v && std::strcmp(v, value) == 0;
-    };
-    auto opt_int = [](const char *name) -> std::optional<int> {
-        const char *v = std::getenv(name);
-        if (v && *v) return std::atoi(v);
-        return std::nullopt;
-    };
-    Knobs k;
-    k.sort = flag("LJMD_SORT", k.sort);
-    k.force_generic = flag("LJMD_FORCE_GENERIC", k.force_generic);
-    k.force_collectives = flag("LJMD_FORCE_COLLECTIVES", k.force_collectives);
-    k.fuse = flag("LJMD_FUSE", k.fuse);
-    k.fuse_tail = flag("LJMD_FUSE_TAIL", k.fuse_tail);
-    k.fuse_defer_record = flag("LJMD_FUSE_DEFER_RECORD", k.fuse_defer_record);
-    // measured at n = 262144: chunks of 4 consecutive row groups per XCD -3 % pair-kernel time (19.8 -> 19.1 ms; 2: -1 %,
-    // 8 / 16 / 32: +-0, one contiguous eighth per XCD: +10 %), -1.5 % at n = 131072 and 524288 (profiles/r02_xcd_remap_and_prefetch.txt)
-    k.xcd_remap = std::max(0, env_int("LJMD_N3_XCD_REMAP", k.xcd_remap));
-    k.inject_failure_at_step = env_int("LJMD_INJECT_FAILURE_AT_STEP", k.inject_failure_at_step);
-    k.exchange_alltoall = is("LJMD_FORCE_EXCHANGE", "alltoall");
-    k.resort_every = opt_int("LJMD_RESORT_EVERY");
-    k.n3_row_tiles = env_int("LJMD_N3_ROW_TILES", k.n3_row_tiles);
-    k.n3_wg_waves = env_int("LJMD_N3_WG_WAVES", k.n3_wg_waves);
-    k.slab_budget_gb = std::max(1, env_int("LJMD_SLAB_BUDGET_GB", k.slab_budget_gb));
-    k.n3_both_ties = flag("LJMD_N3_BOTH_TIES", k.n3_both_ties);
-    k.n3_min_n = env_int("LJMD_N3_MIN_N", k.n3_min_n);
-    k.n3 = flag("LJMD_N3", k.n3);
-    k.n3_target_waves = opt_int("LJMD_N3_TARGET_WAVES");
-    k.n3_clusters = flag("LJMD_N3_CLUSTERS", k.n3_clusters);
-    k.n3_pertile = flag("LJMD_N3_PERTILE", k.n3_pertile);
-    k.fp32_far_stream = flag("LJMD_FP32_FAR_STREAM", k.fp32_far_stream);
-    k.fp32_vfar = flag("LJMD_FP32_VFAR", k.fp32_vfar);
-    {
-        const char *rs = std::getenv("LJMD_FP32_SPLIT");
-        if (rs && *rs) k.fp32_split = std::max(0.0, std::atof(rs));
-    }
-    k.overlap_exchange = flag("LJMD_OVERLAP_EXCHANGE", k.overlap_exchange);
-    k.migrate_blocks = is("LJMD_MIGRATE_DEAL", "blocks");
-    {
-        const char *xm = std::getenv("LJMD_MULTI_EXCHANGE");
-        k.multi_exchange = xm ? xm : "";
-    }
-    k.multi_migrate_every = std::max(0, env_int("LJMD_MULTI_MIGRATE_EVERY", k.multi_migrate_every));
-    k.multi_threads = flag("LJMD_MULTI_THREADS", k.multi_threads);
-    k.batch_group_streams = !is("LJMD_BATCH_GROUP_STREAMS", "0");
-    return k;
-}
 
 int plan_engine(const SimParams &sim, int n, int n_ranks, int precision_mode, const Knobs &k, LaunchPlan *out)
 {

@@ -5,7 +5,8 @@
 // communicators of one process (ncclCommInitAll + ncclGroupStart/End), so that AddressSanitizer checks every
 // extent and offset the host code hands to hipMemcpyAsync / ncclAllGather / ncclReduceScatter / ncclSend+Recv --
 // including the single-process multi-GPU path that cannot run on a one-GPU box.  Numbers computed "on the device"
-// are meaningless here (no kernel runs); only the host orchestration is under test.  Never linked into the product.
+// are meaningless here (no kernel runs); only the host orchestration is under test.  Also linked into tests/batch_trace,
+// the host transcript of the batch engine.  Never linked into the product.
 #include <hip/hip_runtime_api.h>
 #include <rccl/rccl.h>
 
