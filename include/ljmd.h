@@ -594,6 +594,40 @@ int ljmd_batch_tcf_read_exact(ljmd_batch_t *h, int64_t *words, int64_t *counts, 
 int ljmd_batch_tcf_reset(ljmd_batch_t *h);
 int ljmd_tcf_from_exact(const int64_t *words, int32_t n, int64_t count, double *out);
 
+/*
+ * Independent initial configurations on the device (ljmd_batch_prepare): per replica b, with n = n_b, L = L_b and k the
+ * integer with 4 k^3 = n, the steps of the reference's initial-configuration program
+ * (scripts/md_initial_config_program.f90:58-121), without a round trip of the state through the host.  seeds[B] and
+ * target_total_energy[B] are required; epot0[B] and ekin0[B] may be NULL.
+ *   a. FCC lattice in the reference's particle order and expressions: cells ix > iy > iz, basis (0,0,0), (0,1/2,1/2),
+ *      (1/2,0,1/2), (1/2,1/2,0); a = L / dble(k), x0 = dble(ix) * a, offsets x0 + 0.5 * a, no fused multiply-add.  ru <- r.
+ *   b. Velocities from the reference's random_uniform as its first call with seed -|seeds[b]| initialises it: 3 n
+ *      draws, particle i takes draws 3 i, 3 i + 1, 3 i + 2 for vx, vy, vz, v = draw - 0.5.  The generator's state is an
+ *      integer m < 4 10^6 and a draw is double(m) * (1.0 / 4.0e6), the rounded reciprocal.  The stream depends on
+ *      | 1618033 - |seed| | mod 4 10^6 alone: seeds s and -s, and seeds s and 3236066 - s, give the same stream.  Equal
+ *      seeds in different replicas are allowed.
+ *   c. Centre of mass per axis: v_cm = R(sum_i Q(v_i)) / dble(n), v_i <- v_i - v_cm, with Q(t) = rint(t 2^64) and R the
+ *      one correctly rounded conversion of the exact integer sum, as in the reproducible mode -- in BOTH precision
+ *      modes, so that the result depends on no summation order.
+ *   d. epot0 = what ljmd_batch_compute_forces returns for this state (the handle's precision mode and tail-correction
+ *      setting), ekin0 = what ljmd_batch_kinetic_energy returns for it; scale = sqrt((target - epot0) / ekin0) in IEEE
+ *      doubles on the host; v <- v * scale on the device, one rounding each.  The accelerations of the force call stay
+ *      valid (the positions did not change).
+ *   e. warmup_steps velocity-Verlet steps as ljmd_batch_steps takes them, nothing sampled and no g(r), MSD or VACF
+ *      snapshot taken whatever `every` is configured to; then ru <- r again, as a production run that read this state
+ *      from rv_init.dat would start.  (ljmd_batch_profile_read then describes the warm-up.)
+ * Afterwards the handle has a state and valid accelerations; the range flags are cleared, a poison is cleared as
+ * ljmd_batch_set_state clears it, the MSD / VACF snapshot numbering restarts at 0 and the accumulators' sums stay.
+ * A replica's result depends on its own (n, L, dt, rc, seed, target) only: not on B, its slot or the other replicas.
+ * LJMD_ERR_INVALID_ARG, the handle unchanged: NULL seeds or target_total_energy; warmup_steps < 0; a seed of INT32_MIN;
+ * a replica whose n is not 4 k^3 ("replica <b>").  LJMD_ERR_INVALID_ARG when target - epot0 <= 0 or ekin0 <= 0 for some
+ * replica (the first such "replica <b>" is named): the handle is then left without a state (LJMD_ERR_STATE from the
+ * guarded calls until ljmd_batch_set_state or another ljmd_batch_prepare) and is not poisoned.  A failed launch poisons
+ * the handle, as elsewhere.
+ */
+int ljmd_batch_prepare(ljmd_batch_t *h, const int32_t *seeds, const double *target_total_energy,
+                       int32_t warmup_steps, double *epot0, double *ekin0);
+
 #ifdef __cplusplus
 }
 #endif

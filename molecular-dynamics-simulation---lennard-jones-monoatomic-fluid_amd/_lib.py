@@ -135,6 +135,7 @@ PROTOTYPES = {
     "ljmd_batch_tcf_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int64_p, c_int64_p]),
     "ljmd_batch_tcf_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]),
     "ljmd_batch_tcf_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_prepare": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
     "ljmd_tcf_from_exact": (C.c_int, [c_int64_p, C.c_int32, C.c_int64, c_double_p]),
 }
 

@@ -28,7 +28,7 @@ module ljmd_c_api
   public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_set_precision, ljmd_batch_profile_read
   public :: ljmd_batch_rdf_configure, ljmd_batch_rdf_accumulate, ljmd_batch_rdf_read, ljmd_batch_rdf_reset
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
-  public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact
+  public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -353,6 +353,16 @@ module ljmd_c_api
 
     ! MSD / VACF on the device (ljmd.h: ljmd_batch_tcf_*); msd, vacf [max_lag + 1, B], counts [max_lag + 1],
     ! words [3, max_lag + 1, 2, B] in Fortran order; c_null_ptr skips an output
+    ! initial configurations on the device: seeds(B) int32 and target_total_energy(B) required; epot0(B), ekin0(B) or
+    ! c_null_ptr
+    function ljmd_batch_prepare(handle, seeds, target_total_energy, warmup_steps, epot0, ekin0) &
+        bind(C, name="ljmd_batch_prepare") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle, seeds, target_total_energy, epot0, ekin0
+      integer(c_int32_t), value :: warmup_steps
+      integer(c_int) :: status
+    end function
+
     function ljmd_batch_tcf_configure(handle, max_lag, origin_stride, every) bind(C, name="ljmd_batch_tcf_configure") &
         result(status)
       import :: c_int, c_int32_t, c_ptr

@@ -27,7 +27,14 @@
 ! averaged as compute_msd_tau_timeorig / compute_vacf_tau_timeorig, scripts/md_one_run_analysis.py:404-489, over the
 ! sampling instants that write an rva.dat record, every LJMD_TCF_ORIGIN_STRIDE-th of them (default 1) an origin;
 ! outputs/run_NNNN/msd_vacf_gpu.dat gets a header line and, per lag with at least one origin, lag, lag * output_interval *
-! dt, the number of origins, MSD and VACF).
+! dt, the number of origins, MSD and VACF),
+! LJMD_SEED_BASE (unset: the rv_init.dat files above are read; s >= 1: NO rv_init.dat is read -- run i is prepared on the
+! device, ljmd_batch_prepare, with seed s + i - 1: the reference's FCC lattice, its generator's velocities, centre of
+! mass removed, scaled to the target_total_energy of the run's own or the shared input file, then that file's
+! warmup_steps Verlet steps, as md_initial_config_gpu prepares one system with the seed 12345; the prepared state is
+! written to outputs/run_NNNN/rv_init_gpu.dat in the rv_init.dat format -- the user's own rv_init.dat files are left
+! alone -- and the production loop follows unchanged.  The runs are then independent trajectories; run i is
+! byte-identical to LJMD_RUNS=1 with LJMD_SEED_BASE = s + i - 1 and that run's parameters).
 ! Batches take n <= LJMD_BATCH_MAX_N.
 !==============================================================================
 program md_simulation_many_gpu
@@ -48,6 +55,9 @@ program md_simulation_many_gpu
   integer(kind=8), allocatable :: off(:)            ! run i's particles: elements off(i) + 1 .. off(i + 1)
   integer(c_int32_t), allocatable :: n_c(:)
   real(c_double), allocatable :: box_c(:), dt_c(:), rc_c(:), time_run(:)
+  integer :: seed_base                              ! LJMD_SEED_BASE, 0: unset
+  integer(c_int32_t), allocatable, target :: seeds_c(:)
+  real(c_double), allocatable, target :: target_run(:)     ! each run's target_total_energy: its own file's or the shared one
   logical :: any_own
   integer(kind=int_kind) :: total_steps, output_interval, warmup_steps, n_snapshots_expected
   real(kind=dp_kind) :: rc_over_L, target_total_energy
@@ -100,7 +110,15 @@ program md_simulation_many_gpu
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) tcf_stride
   if (tcf_stride < 1) stop 'md_simulation_many: LJMD_TCF_ORIGIN_STRIDE must be >= 1.'
 
-  allocate(rparams(n_runs), own_params(n_runs), off(n_runs + 1), time_run(n_runs))
+  seed_base = 0
+  call get_environment_variable('LJMD_SEED_BASE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) then
+    read(env, *) seed_base
+    if (seed_base < 1) stop 'md_simulation_many: LJMD_SEED_BASE must be >= 1.'
+    if (seed_base > huge(1_c_int32_t) - (n_runs - 1)) stop 'md_simulation_many: LJMD_SEED_BASE + LJMD_RUNS - 1 exceeds int32.'
+  end if
+
+  allocate(rparams(n_runs), own_params(n_runs), off(n_runs + 1), time_run(n_runs), target_run(n_runs))
   allocate(s_epot(n_runs), s_ekin(n_runs), s_depot(n_runs), s_ddepot(n_runs))
   allocate(stats(n_runs), iu_rva(n_runs), iu_out(n_runs), run_dir(n_runs))
 
@@ -117,9 +135,11 @@ program md_simulation_many_gpu
   total = off(n_runs + 1)
   allocate(rx(total), ry(total), rz(total), ux(total), uy(total), uz(total), &
            vx(total), vy(total), vz(total), ax(total), ay(total), az(total))
-  do i = 1, n_runs
-    call read_rv_init(i)
-  end do
+  if (seed_base == 0) then
+    do i = 1, n_runs
+      call read_rv_init(i)
+    end do
+  end if
 
   if (any_own) then
     allocate(n_c(n_runs), box_c(n_runs), dt_c(n_runs), rc_c(n_runs))
@@ -141,9 +161,13 @@ program md_simulation_many_gpu
   call ljmd_batch_check(ljmd_batch_set_precision(batch, precision_mode), batch, 'ljmd_batch_set_precision')
   call ljmd_batch_check(ljmd_batch_set_tail_corrections(batch, merge(1_c_int32_t, 0_c_int32_t, use_tail_corrections)), &
                         batch, 'ljmd_batch_set_tail_corrections')
-  ! H2D; the library sets ru <- r (md_simulation_program.f90:229-231)
-  call ljmd_batch_check(ljmd_batch_set_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(vx), c_loc(vy), &
-                                             c_loc(vz)), batch, 'ljmd_batch_set_state')
+  if (seed_base == 0) then
+    ! H2D; the library sets ru <- r (md_simulation_program.f90:229-231)
+    call ljmd_batch_check(ljmd_batch_set_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(vx), c_loc(vy), &
+                                               c_loc(vz)), batch, 'ljmd_batch_set_state')
+  else
+    call prepare_on_device()
+  end if
   if (rdf_bins > 0) call ljmd_batch_check(ljmd_batch_rdf_configure(batch, int(rdf_bins, c_int32_t), c_null_ptr, &
                                                                    0_c_int32_t), batch, 'ljmd_batch_rdf_configure')
   if (tcf_max_lag > 0) call ljmd_batch_check(ljmd_batch_tcf_configure(batch, int(tcf_max_lag, c_int32_t), &
@@ -264,9 +288,11 @@ contains
     inquire(file=trim(filename), exist=own_params(irun))
     if (.not. own_params(irun)) then
       rparams(irun) = params
+      target_run(irun) = target_total_energy
       return
     end if
     call read_simulation_parameters(trim(filename), rparams(irun), ts, oi, ws, rcl, tte)
+    target_run(irun) = tte
     if (ts /= total_steps .or. oi /= output_interval .or. ws /= warmup_steps) then
       write(*, '(a,a,a)') 'md_simulation_many_gpu: ', trim(filename), ': total_steps, output_interval and '// &
         'warmup_steps must equal those of inputs/input_simulation_parameters.txt (all runs step together)'
@@ -321,6 +347,35 @@ contains
     end do
     close(iu_tcf)
   end subroutine write_msd_vacf
+
+  ! LJMD_SEED_BASE: every run's initial configuration on the device (seed_base + i - 1, the run's target_total_energy,
+  ! the shared warmup_steps), then each run's rv_init_gpu.dat: the two records of rv_init.dat
+  subroutine prepare_on_device()
+    integer :: irun, iu_rv, ierr
+    integer(kind=8) :: o0
+    integer(kind=int_kind) :: ni0
+    allocate(seeds_c(n_runs))
+    do irun = 1, n_runs
+      seeds_c(irun) = int(seed_base + irun - 1, c_int32_t)
+    end do
+    call ljmd_batch_check(ljmd_batch_prepare(batch, c_loc(seeds_c), c_loc(target_run), int(warmup_steps, c_int32_t), &
+                                             c_null_ptr, c_null_ptr), batch, 'ljmd_batch_prepare')
+    call ljmd_batch_check(ljmd_batch_get_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_null_ptr, c_null_ptr, &
+                                               c_null_ptr, c_loc(vx), c_loc(vy), c_loc(vz), c_null_ptr, c_null_ptr, &
+                                               c_null_ptr), batch, 'ljmd_batch_get_state')
+    do irun = 1, n_runs
+      open(newunit=iu_rv, file=trim(run_dir(irun)) // '/rv_init_gpu.dat', form='unformatted', status='replace', &
+           action='write', iostat=ierr)
+      if (ierr /= 0) stop 'md_simulation_many: cannot open rv_init_gpu.dat of a run.'
+      o0 = off(irun)
+      ni0 = rparams(irun)%n
+      write(iu_rv) rx(o0 + 1:o0 + ni0), ry(o0 + 1:o0 + ni0), rz(o0 + 1:o0 + ni0)
+      write(iu_rv) vx(o0 + 1:o0 + ni0), vy(o0 + 1:o0 + ni0), vz(o0 + 1:o0 + ni0)
+      close(iu_rv)
+      write(*, '(a,a,a,i0)') 'md_simulation_many_gpu: ', trim(run_dir(irun)), ' prepared on the device with seed ', &
+        seeds_c(irun)
+    end do
+  end subroutine prepare_on_device
 
   ! run i's rv_init.dat: record 1 = rx ry rz, record 2 = vx vy vz (md_initial_config_program.f90:285-286)
   subroutine read_rv_init(irun)

@@ -514,6 +514,38 @@ class BatchEngine:
         self._ck(self._lib.ljmd_batch_profile_read(self._h, C.byref(ms), C.byref(c)))
         return {"kernel_ms": ms.value, "launches": c.value}
 
+    # -- initial configurations on the device -------------------------------
+    def prepare(self, seeds, target_total_energy, warmup_steps: int = 0):
+        """ljmd_batch_prepare: every replica gets the reference's initial configuration on the device -- FCC lattice
+        (n = 4 k^3), velocities from the reference's generator seeded with -|seed|, centre of mass removed, scaled to
+        target_total_energy, warmup_steps Verlet steps, ru <- r -> (epot0, ekin0), each (B,): the energies before the
+        scaling.  seeds (integers within int32) and target_total_energy are scalars or B values.  Seeds s, -s and
+        3236066 - s give the same velocities.  The handle then has a state and valid accelerations."""
+        B = self.n_replicas
+        s = np.asarray(seeds)
+        if s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer):
+            raise TypeError(f"prepare: seeds must be integers, got dtype {s.dtype}")
+        if s.shape not in ((), (B,)):
+            raise ValueError(f"prepare: seeds must be a scalar or have shape ({B},), got {s.shape}")
+        if s.size and (int(s.min()) < -2 ** 31 or int(s.max()) > 2 ** 31 - 1):
+            raise ValueError("prepare: seeds must lie within the int32 range")
+        t = np.asarray(target_total_energy)
+        if t.dtype == np.bool_ or not (np.issubdtype(t.dtype, np.floating) or np.issubdtype(t.dtype, np.integer)):
+            raise TypeError(f"prepare: target_total_energy must be real numbers, got dtype {t.dtype}")
+        if t.shape not in ((), (B,)):
+            raise ValueError(f"prepare: target_total_energy must be a scalar or have shape ({B},), got {t.shape}")
+        if isinstance(warmup_steps, bool) or not isinstance(warmup_steps, (int, np.integer)):
+            raise TypeError(f"prepare: warmup_steps must be an integer, got {warmup_steps!r}")
+        if not -2 ** 31 <= int(warmup_steps) <= 2 ** 31 - 1:
+            raise ValueError("prepare: warmup_steps must lie within the int32 range")
+        s32 = np.ascontiguousarray(np.broadcast_to(s, (B,)), dtype=np.int32)
+        t64 = np.ascontiguousarray(np.broadcast_to(t, (B,)), dtype=np.float64)
+        epot0 = np.empty(B, dtype=np.float64)
+        ekin0 = np.empty(B, dtype=np.float64)
+        self._ck(self._lib.ljmd_batch_prepare(self._h, s32.ctypes.data_as(_lib.c_int32_p), _ptr(t64), int(warmup_steps),
+                                              _ptr(epot0), _ptr(ekin0)))
+        return epot0, ekin0
+
     # -- g(r) on the device ------------------------------------------------
     def rdf_configure(self, nbins: int, rmax=None, every: int = 0) -> None:
         """ljmd_batch_rdf_configure: nbins bins per replica up to rmax (a scalar, B values, or None = 0.5 L of each
