@@ -402,6 +402,46 @@ int ljmd_profile_read_rank(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, do
 int ljmd_profile_read_stats(ljmd_t *h, int32_t rank, double *ms_avg /* [6] */, double *ms_min /* [6] */,
                             double *ms_median /* [6] */, int32_t *launches);
 
+/*
+ * g(r) of the resident system, accumulated where the positions live (ljmd_rdf_*): no snapshot leaves the device.
+ *
+ * Definition.  One snapshot adds to hist[nbins], for the positions resident now -- the wrapped r that ljmd_get_state
+ * would return and ljmd_snapshot_begin would copy -- exactly the integers ljmd_rdf_histogram(n, x, y, z, L, nbins, rmax,
+ * hist) adds for those positions: weight 2 per unordered pair with r < rmax, bin int(r / dr), dr = rmax / nbins, through
+ * the same per-pair arithmetic with no contraction, over all particles (no subsampling).  The counts are integers, so
+ * they depend on nothing else: not on the slot order or re-sort state, the tile walk, the number of ranks, ownership
+ * migration, the precision mode, knobs or streams.
+ * configure: 1 <= nbins <= LJMD_RDF_MAX_BINS, rmax finite and > 0 (values above L/2 are allowed, as in the stateless
+ * call); allocates and zeroes the counts and the snapshot count; calling it again reconfigures and zeroes; nbins == 0
+ * switches the feature off and frees it.  A failed guard returns LJMD_ERR_INVALID_ARG and leaves the earlier
+ * configuration in place; a failed allocation LJMD_ERR_ALLOC with the feature off.  Works with or without a state.
+ * ljmd_set_state, ljmd_set_accel, ljmd_set_unwrapped and ljmd_set_tail_corrections leave configuration and counts alone.
+ * accumulate: one snapshot, stream-ordered on the engine's stream behind everything enqueued so far
+ * (ljmd_enqueue_steps* included), no host wait; the snapshot count goes up by one.  LJMD_ERR_STATE before configure,
+ * without a state, without valid accelerations, on a poisoned handle and between ljmd_step_begin and ljmd_step_finish.
+ * r, ru, v, a, the step records and every later result stay bitwise what they are without the call: it reads the
+ * exchange buffer and writes buffers of its own.
+ * read: waits for the device; hist[nbins] and the snapshot count, either may be NULL; clears nothing.
+ * reset: zeroes both.  read, reset and profile_read return LJMD_ERR_STATE before configure.
+ * profile_read, for the most recent accumulate (zeros before the first): the (row tile, column tile) pairs of 64 x 64
+ * particles its walk evaluated, the pairs it considered (evaluated + skipped because their bounding boxes are provably
+ * farther apart than rmax), and the time of its two launches from HIP events; any pointer may be NULL; waits for the
+ * device.
+ * Ranks.  On a rank engine (ljmd_create with n_ranks > 1) a snapshot adds weight 1 for every ordered pair (i owned by
+ * this rank, j any other particle of the system) and read returns this partial histogram: the partials of the ranks add
+ * up to the definition above.  The rank's exchange buffer must hold everybody's current positions, which is the case
+ * whenever the accelerations are valid and the caller has run the exchanges it is responsible for (after
+ * ljmd_migrate_deal: the position exchange).  On a multi-device handle (ljmd_create_multi) accumulate runs on every
+ * rank, read returns the sum, the snapshot count is the common one; profile_read returns the tile-pair counts summed
+ * over the ranks and the longest of their times.
+ */
+#define LJMD_RDF_MAX_BINS 8192
+int ljmd_rdf_configure(ljmd_t *h, int32_t nbins, double rmax);
+int ljmd_rdf_accumulate(ljmd_t *h);
+int ljmd_rdf_read(ljmd_t *h, uint64_t *hist, int64_t *n_snapshots);
+int ljmd_rdf_reset(ljmd_t *h);
+int ljmd_rdf_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *tile_pairs_total, double *kernel_ms);
+
 /* ---- batch engine: many independent small systems on one device ------------------------------------------------
  *
  * One ljmd_batch_t holds B replicas on one device -- the ensemble runs of the reference's run-many framework

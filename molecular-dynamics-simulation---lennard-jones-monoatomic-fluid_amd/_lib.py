@@ -126,6 +126,11 @@ PROTOTYPES = {
     "ljmd_batch_set_tail_corrections": (C.c_int, [C.c_void_p, C.c_int32]),
     "ljmd_batch_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "ljmd_batch_profile_read": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
+    "ljmd_rdf_configure": (C.c_int, [C.c_void_p, C.c_int32, C.c_double]),
+    "ljmd_rdf_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
+    "ljmd_rdf_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_rdf_profile_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_double_p]),
     "ljmd_batch_rdf_configure": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     "ljmd_batch_rdf_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_batch_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),

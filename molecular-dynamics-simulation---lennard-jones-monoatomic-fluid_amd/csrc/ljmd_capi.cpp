@@ -108,6 +108,7 @@ int ljmd_set_state(ljmd_t *h, const double *rx, const double *ry, const double *
     if (h->multi) return ljmdm::set_state(h, rx, ry, rz, vx, vy, vz);
     h->boxes_valid = false;
     h->drift_prefused = false;
+    h->step_open = false;
     LJMD_HIP(h, hipSetDevice(h->device));
     if (h->poisoned) {
         // a batch of steps failed half-way: drain the stream, forget whatever records were in flight and take the
@@ -479,6 +480,7 @@ int ljmd_step_begin(ljmd_t *h)
     if (!h->have_state || !h->have_accel)
         return fail(h, LJMD_ERR_STATE, "ljmd_step_begin: state/accelerations not initialised");
     LJMD_HIP(h, hipSetDevice(h->device));
+    h->step_open = true;                 // the own block runs ahead of the exchange buffer until ljmd_step_finish
     return enqueue_drift(h, next_events(h));
 }
 
@@ -504,7 +506,9 @@ int ljmd_step_finish(ljmd_t *h)
         const int rc_ = enqueue_pair_forces(h, q);
         if (rc_ != LJMD_OK) return rc_;
     }
-    return enqueue_kick(h, true, q);
+    const int rc_ = enqueue_kick(h, true, q);
+    if (rc_ == LJMD_OK) h->step_open = false;
+    return rc_;
 }
 
 int ljmd_force_buffers(ljmd_t *h, int32_t external, void **fpart, int64_t *fpart_doubles, void **frecv,

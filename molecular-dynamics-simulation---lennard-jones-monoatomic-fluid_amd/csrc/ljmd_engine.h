@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "ljmd_internal.h"
+#include "ljmd_rdf.h"
 
 using namespace ljmdk;
 
@@ -203,6 +204,10 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     std::vector<size_t> mig_level_off;
     double mig_ext[3] = {0, 0, 0};    // extents of a rank's block after the deal (choose the shard's k-d axes)
     int32_t migrations = 0;
+
+    // resident g(r) (ljmd_rdf_*, ljmd_rdf.cpp); a multi-device parent keeps only nbins here, the ranks own the buffers
+    ljmdr::RdfState rdf;
+    bool step_open = false;           // between ljmd_step_begin and ljmd_step_finish (split-phase API)
 
     bool profiling = false;
     std::vector<EventSet> ev_pool;

@@ -27,6 +27,7 @@ module ljmd_c_api
   public :: ljmd_batch_set_unwrapped, ljmd_batch_get_state, ljmd_batch_compute_forces, ljmd_batch_kinetic_energy
   public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_set_precision, ljmd_batch_profile_read
   public :: ljmd_batch_rdf_configure, ljmd_batch_rdf_accumulate, ljmd_batch_rdf_read, ljmd_batch_rdf_reset
+  public :: ljmd_rdf_configure, ljmd_rdf_accumulate, ljmd_rdf_read, ljmd_rdf_reset, ljmd_rdf_profile_read
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_check, ljmd_batch_error_text
@@ -320,6 +321,43 @@ module ljmd_c_api
       type(c_ptr), value :: handle
       real(c_double), intent(out) :: kernel_ms
       integer(c_int32_t), intent(out) :: launches
+      integer(c_int) :: status
+    end function
+
+    ! g(r) of the system resident on an engine handle (ljmd.h: ljmd_rdf_*): hist = c_loc of nbins 64-bit counts
+    function ljmd_rdf_configure(handle, nbins, rmax) bind(C, name="ljmd_rdf_configure") result(status)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: nbins
+      real(c_double), value :: rmax
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rdf_accumulate(handle) bind(C, name="ljmd_rdf_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rdf_read(handle, hist, n_snapshots) bind(C, name="ljmd_rdf_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, hist
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rdf_reset(handle) bind(C, name="ljmd_rdf_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rdf_profile_read(handle, tile_pairs_visited, tile_pairs_total, kernel_ms) &
+        bind(C, name="ljmd_rdf_profile_read") result(status)
+      import :: c_int, c_int64_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: tile_pairs_visited, tile_pairs_total
+      real(c_double), intent(out) :: kernel_ms
       integer(c_int) :: status
     end function
 

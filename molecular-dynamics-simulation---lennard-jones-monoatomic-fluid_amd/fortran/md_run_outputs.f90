@@ -4,14 +4,17 @@
 !   <dir>/md_final_results.txt (appended block)      md_simulation_program.f90:531-560
 ! <obs> = epot, ekin, etot, temp, press.  Used by md_simulation_gpu (samples from the GPU) and
 ! by md_stats_replay (samples from a file; CPU-only test of this module and md_stats).
+!   <dir>/rdf_gpu.dat: the g(r) histogram a GPU driver accumulated on the device (write_rdf_file), shared by
+!   md_simulation_gpu (ljmd_rdf_*) and md_simulation_many_gpu (ljmd_batch_rdf_*).
 !==============================================================================
 module md_run_outputs
+  use, intrinsic :: iso_c_binding, only: c_int64_t
   use define_precision, only: dp_kind, int_kind
   use md_types,         only: sim_params
   use md_stats
   implicit none
   private
-  public :: write_run_statistics
+  public :: write_run_statistics, write_rdf_file
 
 contains
 
@@ -89,6 +92,34 @@ contains
     write(iu, *)
     close(iu)
   end subroutine write_run_statistics
+
+  ! rdf_gpu.dat: per bin its centre, the integer count (2 per unordered pair, summed over the snapshots) and
+  ! g(r) = count / (snapshots N rho shell volume); bin edges k rmax / nbins, the last one rmax itself
+  subroutine write_rdf_file(filename, n, box_length, rmax, nbins, hist, snapshots)
+    character(len=*), intent(in) :: filename
+    integer(kind=int_kind), intent(in) :: n
+    real(kind=dp_kind), intent(in) :: box_length, rmax
+    integer, intent(in) :: nbins
+    integer(c_int64_t), intent(in) :: hist(nbins), snapshots
+    real(kind=dp_kind), parameter :: pi = 3.141592653589793238462643383279502884d0
+    real(kind=dp_kind) :: dr, e0, e1, rho, norm, g
+    integer :: iu_rdf, ierr, kb
+    dr = rmax / dble(nbins)
+    rho = dble(n) / box_length**3
+    open(newunit=iu_rdf, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_rdf_file(): cannot open rdf_gpu.dat.'
+    write(iu_rdf, '(a)') '# r_center   count   g(r)'
+    do kb = 1, nbins
+      e0 = dble(kb - 1) * dr
+      e1 = dble(kb) * dr
+      if (kb == nbins) e1 = rmax
+      norm = dble(snapshots) * dble(n) * rho * ((4.d0 / 3.d0) * pi * (e1**3 - e0**3))
+      g = 0.d0
+      if (norm > 0.d0) g = dble(hist(kb)) / norm
+      write(iu_rdf, '(es24.16e3,2x,i0,2x,es24.16e3)') 0.5d0 * (e0 + e1), hist(kb), g
+    end do
+    close(iu_rdf)
+  end subroutine write_rdf_file
 
   subroutine write_curve(filename, header, errmsg, lag_max, c, cn)
     character(len=*), intent(in) :: filename, header, errmsg

@@ -16,7 +16,11 @@
 ! drives that many devices -- ljmd_create_multi, particles sharded by index range, RCCL all-gather of positions and
 ! reduce-scatter of forces per step inside the library -- e.g. BASELINE config 4 with LJMD_GPUS=8; LJMD_DEVICES, a
 ! comma-separated device list of that length, overrides 0..LJMD_GPUS-1), LJMD_REPRODUCIBLE (default 0; 1: the
-! LJMD_PRECISION_FP64_REPRODUCIBLE mode -- every output file bitwise independent of LJMD_GPUS).
+! LJMD_PRECISION_FP64_REPRODUCIBLE mode -- every output file bitwise independent of LJMD_GPUS), LJMD_RDF_BINS
+! (default 0 = off; > 0: g(r) with that many bins up to LJMD_RDF_RMAX, default half the box, is accumulated on the
+! device -- ljmd_rdf_* -- at every sampling instant that writes an rva.dat record, over all particles, and
+! outputs/one_run/rdf_gpu.dat gets the bin centres, integer counts and g(r), in the format of md_simulation_many_gpu;
+! every other output file is the same with and without it).
 !==============================================================================
 program md_simulation_gpu
   use, intrinsic :: iso_c_binding
@@ -26,7 +30,7 @@ program md_simulation_gpu
   use ljmd_c_api
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push
-  use md_run_outputs,   only: write_run_statistics
+  use md_run_outputs,   only: write_run_statistics, write_rdf_file
   implicit none
 
   type(sim_params) :: params
@@ -46,6 +50,10 @@ program md_simulation_gpu
   type(c_ptr) :: engine
   type(run_statistics) :: stats
   character(len=32) :: env
+  integer :: rdf_bins
+  real(kind=dp_kind) :: rdf_rmax
+  integer(c_int64_t), allocatable, target :: rdf_hist(:)
+  integer(c_int64_t) :: rdf_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -68,6 +76,13 @@ program md_simulation_gpu
   if (ios == 0 .and. len_trim(env) > 0) then
     if (trim(env) /= '0') precision_mode = LJMD_PRECISION_FP64_REPRODUCIBLE
   end if
+  rdf_bins = 0
+  call get_environment_variable('LJMD_RDF_BINS', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rdf_bins
+  if (rdf_bins < 0) stop 'md_simulation: LJMD_RDF_BINS must be >= 0.'
+  rdf_rmax = 0.5d0 * params%box_length
+  call get_environment_variable('LJMD_RDF_RMAX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rdf_rmax
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
@@ -89,6 +104,8 @@ program md_simulation_gpu
   ! H2D; the library sets ru <- r (md_simulation_program.f90:229-231)
   call ljmd_check(ljmd_set_state(engine, c_loc(state%rx), c_loc(state%ry), c_loc(state%rz), &
                                  c_loc(state%vx), c_loc(state%vy), c_loc(state%vz)), engine, 'ljmd_set_state')
+  if (rdf_bins > 0) call ljmd_check(ljmd_rdf_configure(engine, int(rdf_bins, c_int32_t), rdf_rmax), engine, &
+                                    'ljmd_rdf_configure')
   ! t = 0 forces and energies (:236-243)
   call ljmd_check(ljmd_compute_forces(engine, epot, d_epot, dd_epot), engine, 'ljmd_compute_forces')
   call ljmd_check(ljmd_kinetic_energy(engine, ekin), engine, 'ljmd_kinetic_energy')
@@ -130,6 +147,8 @@ program md_simulation_gpu
     etot = epot + ekin
     sample_now = step > warmup_steps .and. mod(step, output_interval) == 0       ! :361
     if (sample_now) call ljmd_check(ljmd_snapshot_begin(engine), engine, 'ljmd_snapshot_begin')
+    ! g(r) of the same instant, on the device, ahead of the next segment in the engine's stream
+    if (sample_now .and. rdf_bins > 0) call ljmd_check(ljmd_rdf_accumulate(engine), engine, 'ljmd_rdf_accumulate')
     count = segment_length(step)
     if (async_io .and. count > 0) call enqueue_segment(count)
     if (sample_now) then
@@ -150,10 +169,16 @@ program md_simulation_gpu
   call system_clock(c1)
   close(iu_out)
   close(iu_rva)
+  if (rdf_bins > 0) then
+    allocate(rdf_hist(rdf_bins))
+    call ljmd_check(ljmd_rdf_read(engine, c_loc(rdf_hist), rdf_snapshots), engine, 'ljmd_rdf_read')
+  end if
   call ljmd_destroy(engine)
 
   if (num_samples <= 0) stop 'md_simulation: no samples were taken (check warmup_steps/output_interval).'
   call write_run_statistics('outputs/one_run', params, total_steps, output_interval, warmup_steps, stats)
+  if (rdf_bins > 0) call write_rdf_file('outputs/one_run/rdf_gpu.dat', params%n, params%box_length, rdf_rmax, rdf_bins, &
+                                        rdf_hist, rdf_snapshots)
   write(*, '(a,i0,a,i0,a,f10.2,a,es11.4,a)') 'md_simulation_gpu: N=', params%n, ' steps=', total_steps, &
     '  ', dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' steps/s  ', &
     0.5d0 * npd * (npd - 1.d0) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' pair-interactions/s'

@@ -45,7 +45,7 @@ program md_simulation_many_gpu
   use ljmd_c_api
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push
-  use md_run_outputs,   only: write_run_statistics
+  use md_run_outputs,   only: write_run_statistics, write_rdf_file
   implicit none
 
   character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
@@ -308,28 +308,11 @@ contains
       ' dt=', rparams(irun)%dt, ' rc=', rparams(irun)%rc
   end subroutine read_run_parameters
 
-  ! run i's rdf_gpu.dat: bin centre, count, g(r) = count / (snapshots N rho shell volume), edges k rmax / nbins
+  ! run i's rdf_gpu.dat (md_run_outputs: write_rdf_file), up to half its box
   subroutine write_rdf(irun)
     integer, intent(in) :: irun
-    real(kind=dp_kind), parameter :: pi = 3.141592653589793238462643383279502884d0
-    real(kind=dp_kind) :: rmax, dr, e0, e1, rho, norm, g
-    integer :: iu_rdf, ierr, kb
-    rmax = 0.5d0 * rparams(irun)%box_length
-    dr = rmax / dble(rdf_bins)
-    rho = dble(rparams(irun)%n) / rparams(irun)%box_length**3
-    open(newunit=iu_rdf, file=trim(run_dir(irun)) // '/rdf_gpu.dat', status='replace', action='write', iostat=ierr)
-    if (ierr /= 0) stop 'md_simulation_many: cannot open rdf_gpu.dat of a run.'
-    write(iu_rdf, '(a)') '# r_center   count   g(r)'
-    do kb = 1, rdf_bins
-      e0 = dble(kb - 1) * dr
-      e1 = dble(kb) * dr
-      if (kb == rdf_bins) e1 = rmax
-      norm = dble(rdf_snapshots) * dble(rparams(irun)%n) * rho * ((4.d0 / 3.d0) * pi * (e1**3 - e0**3))
-      g = 0.d0
-      if (norm > 0.d0) g = dble(rdf_hist(kb, irun)) / norm
-      write(iu_rdf, '(es24.16e3,2x,i0,2x,es24.16e3)') 0.5d0 * (e0 + e1), rdf_hist(kb, irun), g
-    end do
-    close(iu_rdf)
+    call write_rdf_file(trim(run_dir(irun)) // '/rdf_gpu.dat', rparams(irun)%n, rparams(irun)%box_length, &
+                        0.5d0 * rparams(irun)%box_length, rdf_bins, rdf_hist(:, irun), rdf_snapshots)
   end subroutine write_rdf
 
   ! run i's msd_vacf_gpu.dat: per lag with at least one origin, lag, tau = lag * output_interval * dt of the run, the

@@ -342,6 +342,37 @@ class Engine:
         dd_epot without the three mean-field tail constants"""
         self._ck(self._lib.ljmd_set_tail_corrections(self._h, 1 if on else 0))
 
+    # -- g(r) of the resident system (include/ljmd.h: ljmd_rdf_*) ---------------------------
+    def rdf_configure(self, nbins: int, rmax=None) -> None:
+        """ljmd_rdf_configure: nbins bins up to rmax (None = half the box); nbins = 0 switches the feature off.  The
+        counts start at zero."""
+        r = 0.5 * self.params.box_length if rmax is None else float(rmax)
+        self._ck(self._lib.ljmd_rdf_configure(self._h, int(nbins), r))
+        self._rdf_nbins = int(nbins)
+
+    def rdf_accumulate(self) -> None:
+        """adds the histogram of the positions resident now (stream-ordered: no host wait)"""
+        self._ck(self._lib.ljmd_rdf_accumulate(self._h))
+
+    def rdf_read(self):
+        """-> (hist[nbins] uint64: 2 per unordered pair with r < rmax, the number of snapshots accumulated); a rank
+        engine (n_ranks > 1) returns its partial histogram: 1 per ordered pair (own i, any j)"""
+        nbins = getattr(self, "_rdf_nbins", 0)
+        hist = np.zeros(max(nbins, 1), dtype=np.uint64)
+        count = C.c_int64()
+        self._ck(self._lib.ljmd_rdf_read(self._h, hist.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(count)))
+        return hist[:nbins], count.value
+
+    def rdf_reset(self) -> None:
+        self._ck(self._lib.ljmd_rdf_reset(self._h))
+
+    def rdf_profile(self) -> dict:
+        """ljmd_rdf_profile_read for the most recent rdf_accumulate -> {'tile_pairs_visited', 'tile_pairs_total',
+        'kernel_ms'}"""
+        vis, tot, ms = C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self._lib.ljmd_rdf_profile_read(self._h, C.byref(vis), C.byref(tot), C.byref(ms)))
+        return {"tile_pairs_visited": vis.value, "tile_pairs_total": tot.value, "kernel_ms": ms.value}
+
     # -- measurement -----------------------------------------------------------
     def profile_enable(self, on: bool = True) -> None:
         self._ck(self._lib.ljmd_profile_enable(self._h, 1 if on else 0))
