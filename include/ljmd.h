@@ -442,6 +442,55 @@ int ljmd_rdf_read(ljmd_t *h, uint64_t *hist, int64_t *n_snapshots);
 int ljmd_rdf_reset(ljmd_t *h);
 int ljmd_rdf_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *tile_pairs_total, double *kernel_ms);
 
+/*
+ * MSD(tau) and VACF(tau) of the resident system, time-origin averaged where ru and v live (ljmd_tcf_*): no snapshot
+ * leaves the device.  One-rank engines only (ljmd_create with n_ranks = 1).
+ *
+ * Definition.  That of ljmd_batch_tcf_* below with B = 1 -- the terms, Q(t) = RNE(t 2^64), the range rule (a term that
+ * is not finite or has |t| >= 2^40 enters as 0 and sets a sticky range word), signed 192-bit sums S[kind][l] per (kind,
+ * lag), the lag-0 terms of an origin added when the next snapshot arrives, ring slot (s / origin_stride) % slots with
+ * slots = max_lag / origin_stride + 1 <= LJMD_TCF_MAX_ORIGINS, count[l] kept on the host, msd[l] = fixed(S[0][l]) /
+ * ((double)n * (double)count[l]) through ljmd_tcf_from_exact.  What differs:
+ *   Snapshot: the resident ru and v of all n particles, as ljmd_get_state would return them now; numbered s = 0, 1, ...
+ *   from the last configure, reset or ljmd_set_state.
+ *   Identity: a term pairs values of the same particle, i.e. the same index of the arrays given to the last
+ *   ljmd_set_state, whatever slot it occupies now.  The integers therefore depend on the snapshots alone: not on slot
+ *   order, re-sort state or interval, tiling knobs, step form (generic, Newton-3, two-launch fused step), precision mode
+ *   (given the same ru, v) or on how the kernels split the work.
+ * configure: 1 <= max_lag <= LJMD_TCF_MAX_LAG, origin_stride >= 1 (and n <= 2^23); max_lag = 0 switches the feature off and frees
+ * everything; otherwise allocates and zeroes; calling it again reconfigures and zeroes.  A failed guard returns
+ * LJMD_ERR_INVALID_ARG and leaves the earlier configuration in place; a failed allocation LJMD_ERR_ALLOC with the
+ * feature off, the message naming the buffer and its byte count.  Works with or without a state.  The origin ring is
+ * slots x 6 x n_pad x 8 bytes, n_pad = n rounded up to 1024 -- 6.4 GB at n = 262 144 with 512 origins; the size is
+ * computed in size_t.  On a rank engine (n_ranks > 1) or a multi-device handle (ljmd_create_multi) configure returns
+ * LJMD_ERR_INVALID_ARG ("... n_ranks = <G>: ... needs a one-rank engine"), and the other five calls LJMD_ERR_STATE
+ * ("not configured").
+ * accumulate: the resident state is the next snapshot, stream-ordered on the engine's stream behind everything enqueued
+ * so far (ljmd_enqueue_steps* included), no host wait.  Guards and their order are those of ljmd_rdf_accumulate:
+ * LJMD_ERR_STATE before configure, without a state, without valid accelerations, on a poisoned handle and between
+ * ljmd_step_begin and ljmd_step_finish.  It writes only buffers of its own: r, ru, v, a, the step records, the slot
+ * permutation and every later result stay bitwise what they are without the call.
+ * read / read_exact: wait for the device; msd[max_lag + 1], vacf[max_lag + 1] (read) or words[2][max_lag + 1][3]
+ * (read_exact), counts[max_lag + 1], the number of snapshots since configure / reset -- any pointer may be NULL; they
+ * clear nothing.  With the range word set they return LJMD_ERR_RANGE until ljmd_tcf_reset; the handle is not poisoned
+ * and stepping is unaffected.
+ * reset: zeroes the sums, counts, numbering and range word.
+ * profile_read, for the most recent accumulate (zeros before the first): the HIP-event time of its launches and the
+ * number of live origins it visited; either pointer may be NULL; waits for the device.
+ * read, read_exact, reset and profile_read return LJMD_ERR_STATE before configure.
+ * ljmd_set_state starts a new trajectory: the stored origins are dropped and the numbering restarts at 0, the sums and
+ * counts stay, as for the batch.  ljmd_set_unwrapped, ljmd_set_accel, ljmd_set_tail_corrections, ljmd_rdf_* and
+ * ljmd_migrate (a no-op on one rank) leave everything alone.
+ */
+#define LJMD_TCF_MAX_LAG 4096
+#define LJMD_TCF_MAX_ORIGINS 512
+int ljmd_tcf_configure(ljmd_t *h, int32_t max_lag, int32_t origin_stride);
+int ljmd_tcf_accumulate(ljmd_t *h);
+int ljmd_tcf_read(ljmd_t *h, double *msd, double *vacf, int64_t *counts, int64_t *n_snapshots);
+int ljmd_tcf_read_exact(ljmd_t *h, int64_t *words /* [2][max_lag+1][3] */, int64_t *counts, int64_t *n_snapshots);
+int ljmd_tcf_reset(ljmd_t *h);
+int ljmd_tcf_profile_read(ljmd_t *h, double *kernel_ms, int32_t *origins_live);
+
 /* ---- batch engine: many independent small systems on one device ------------------------------------------------
  *
  * One ljmd_batch_t holds B replicas on one device -- the ensemble runs of the reference's run-many framework

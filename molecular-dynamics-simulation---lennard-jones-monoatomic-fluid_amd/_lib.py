@@ -131,6 +131,12 @@ PROTOTYPES = {
     "ljmd_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
     "ljmd_rdf_reset": (C.c_int, [C.c_void_p]),
     "ljmd_rdf_profile_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_double_p]),
+    "ljmd_tcf_configure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "ljmd_tcf_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_tcf_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int64_p, c_int64_p]),
+    "ljmd_tcf_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]),
+    "ljmd_tcf_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_tcf_profile_read": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
     "ljmd_batch_rdf_configure": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     "ljmd_batch_rdf_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_batch_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
@@ -147,6 +153,8 @@ PROTOTYPES = {
 BATCH_MAX_N = 4096
 BATCH_TCF_MAX_LAG = 4096
 BATCH_TCF_MAX_ORIGINS = 512
+TCF_MAX_LAG = 4096
+TCF_MAX_ORIGINS = 512
 
 _lib = None
 

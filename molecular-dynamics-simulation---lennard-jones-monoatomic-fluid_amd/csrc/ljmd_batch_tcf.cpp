@@ -2,8 +2,13 @@
 // ljmd_tcf_from_exact; kernel: ljmd_batch_tcf.hip): configure / accumulate / read / reset, the numbering of the
 // snapshots and the ring of origins, and the entry through which the step loop of ljmd_batch.cpp takes its snapshots.
 #include "ljmd_batch_host.h"
+#include "ljmd_tcf_host.h"
 
 using namespace ljmdb;
+using ljmdh::tcf_count;
+using ljmdh::tcf_quotient;
+using ljmdh::tcf_window;
+using ljmdh::TcfWindow;
 
 static_assert(kBatchTcfMaxLag == LJMD_BATCH_TCF_MAX_LAG && kBatchTcfMaxOrigins == LJMD_BATCH_TCF_MAX_ORIGINS,
               "MSD / VACF limits out of sync with include/ljmd.h");
@@ -14,8 +19,7 @@ namespace {
 // 1 <= s - t0 <= max_lag (BatchTcfArgs); n_live == 0 and store_slot < 0: nothing to launch
 BatchTcfArgs tcf_snapshot(const ljmd_batch *h, int64_t s)
 {
-    const int64_t stride = h->tcf.stride, lo = std::max<int64_t>(0, s - h->tcf.max_lag);
-    const int64_t first = (lo + stride - 1) / stride * stride, last = s >= 1 ? (s - 1) / stride * stride : -1;
+    const TcfWindow w = tcf_window(s, h->tcf.max_lag, h->tcf.stride, h->tcf.slots);
     BatchTcfArgs ta{};
     ta.state = h->d_state;
     ta.ring = h->tcf.d_ring;
@@ -26,12 +30,10 @@ BatchTcfArgs tcf_snapshot(const ljmd_batch *h, int64_t s)
     ta.max_lag = h->tcf.max_lag;
     ta.stride = h->tcf.stride;
     ta.slots = h->tcf.slots;
-    if (last >= first) {
-        ta.n_live = (int)((last - first) / stride) + 1;
-        ta.lag_first = (int)(s - first);
-        ta.slot_first = (int)(first / stride % h->tcf.slots);
-    }
-    ta.store_slot = s % stride == 0 ? (int)(s / stride % h->tcf.slots) : -1;
+    ta.n_live = w.n_live;
+    ta.lag_first = w.lag_first;
+    ta.slot_first = w.slot_first;
+    ta.store_slot = w.store_slot;
     return ta;
 }
 
@@ -54,12 +56,7 @@ int enqueue_tcf(ljmd_batch *h, const BatchGroup &g, hipStream_t s_, int k, int32
 void tcf_ran(ljmd_batch *h, int snapshots)
 {
     for (int k = 0; k < snapshots; ++k) {
-        const BatchTcfArgs l = tcf_snapshot(h, h->tcf.s);
-        for (int e = 0; e < l.n_live; ++e) {
-            const int lag = l.lag_first - e * h->tcf.stride;
-            ++h->tcf.counts[(size_t)lag];
-            if (lag == 1) ++h->tcf.counts[0];
-        }
+        tcf_count(tcf_window(h->tcf.s, h->tcf.max_lag, h->tcf.stride, h->tcf.slots), h->tcf.stride, h->tcf.counts.data());
         ++h->tcf.s;
         ++h->tcf.snapshots;
     }
@@ -170,8 +167,7 @@ int ljmd_tcf_from_exact(const int64_t *words, int32_t n, int64_t count, double *
     if (!words || !out) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_tcf_from_exact: NULL argument");
     if (n < 1 || count < 0) return fail(nullptr, LJMD_ERR_INVALID_ARG, "ljmd_tcf_from_exact: n must be >= 1, count >= 0");
     const uint64_t x[3] = {(uint64_t)words[0], (uint64_t)words[1], (uint64_t)words[2]};
-    // one rounding of the integer, one division (n count < 2^53: the product is exact)
-    *out = count == 0 ? 0.0 : ljmdk::fixed_to_double(x) / ((double)n * (double)count);
+    *out = tcf_quotient(x, n, count);
     return LJMD_OK;
 }
 

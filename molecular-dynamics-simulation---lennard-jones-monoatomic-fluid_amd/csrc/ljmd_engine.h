@@ -19,6 +19,7 @@
 
 #include "ljmd_internal.h"
 #include "ljmd_rdf.h"
+#include "ljmd_tcf.h"
 
 using namespace ljmdk;
 
@@ -207,6 +208,8 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
 
     // resident g(r) (ljmd_rdf_*, ljmd_rdf.cpp); a multi-device parent keeps only nbins here, the ranks own the buffers
     ljmdr::RdfState rdf;
+    // resident MSD / VACF (ljmd_tcf_*, ljmd_tcf.cpp): one-rank engines only
+    ljmdt::TcfState tcf;
     bool step_open = false;           // between ljmd_step_begin and ljmd_step_finish (split-phase API)
 
     bool profiling = false;

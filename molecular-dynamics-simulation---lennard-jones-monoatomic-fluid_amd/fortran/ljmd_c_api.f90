@@ -28,6 +28,7 @@ module ljmd_c_api
   public :: ljmd_batch_steps, ljmd_batch_set_tail_corrections, ljmd_batch_set_precision, ljmd_batch_profile_read
   public :: ljmd_batch_rdf_configure, ljmd_batch_rdf_accumulate, ljmd_batch_rdf_read, ljmd_batch_rdf_reset
   public :: ljmd_rdf_configure, ljmd_rdf_accumulate, ljmd_rdf_read, ljmd_rdf_reset, ljmd_rdf_profile_read
+  public :: ljmd_tcf_configure, ljmd_tcf_accumulate, ljmd_tcf_read, ljmd_tcf_read_exact, ljmd_tcf_reset, ljmd_tcf_profile_read
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_check, ljmd_batch_error_text
@@ -37,6 +38,8 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_PRECISION_FP64_REPRODUCIBLE = 2   ! exact fixed-point sums (ljmd.h)
   integer(c_int32_t), parameter, public :: LJMD_MAX_PENDING_STEPS = 4096
   integer(c_int32_t), parameter, public :: LJMD_BATCH_MAX_N = 4096
+  integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_LAG = 4096
+  integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_ORIGINS = 512
 
   interface
     function ljmd_compute_lj_potential_energy(n, box_length, rc, rx, ry, rz, ax, ay, az, &
@@ -358,6 +361,49 @@ module ljmd_c_api
       type(c_ptr), value :: handle
       integer(c_int64_t), intent(out) :: tile_pairs_visited, tile_pairs_total
       real(c_double), intent(out) :: kernel_ms
+      integer(c_int) :: status
+    end function
+
+    ! MSD / VACF of the system resident on a one-rank engine handle (ljmd.h: ljmd_tcf_*); msd, vacf, counts = c_loc of
+    ! max_lag + 1 values, words [3, max_lag + 1, 2] in Fortran order; c_null_ptr skips an output
+    function ljmd_tcf_configure(handle, max_lag, origin_stride) bind(C, name="ljmd_tcf_configure") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_lag, origin_stride
+      integer(c_int) :: status
+    end function
+
+    function ljmd_tcf_accumulate(handle) bind(C, name="ljmd_tcf_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_tcf_read(handle, msd, vacf, counts, n_snapshots) bind(C, name="ljmd_tcf_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, msd, vacf, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_tcf_read_exact(handle, words, counts, n_snapshots) bind(C, name="ljmd_tcf_read_exact") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_tcf_reset(handle) bind(C, name="ljmd_tcf_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_tcf_profile_read(handle, kernel_ms, origins_live) bind(C, name="ljmd_tcf_profile_read") result(status)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      real(c_double), intent(out) :: kernel_ms
+      integer(c_int32_t), intent(out) :: origins_live
       integer(c_int) :: status
     end function
 

@@ -6,6 +6,8 @@
 ! by md_stats_replay (samples from a file; CPU-only test of this module and md_stats).
 !   <dir>/rdf_gpu.dat: the g(r) histogram a GPU driver accumulated on the device (write_rdf_file), shared by
 !   md_simulation_gpu (ljmd_rdf_*) and md_simulation_many_gpu (ljmd_batch_rdf_*).
+!   <dir>/msd_vacf_gpu.dat: MSD(tau) and VACF(tau) accumulated on the device (write_msd_vacf_file), shared by
+!   md_simulation_gpu (ljmd_tcf_*) and md_simulation_many_gpu (ljmd_batch_tcf_*).
 !==============================================================================
 module md_run_outputs
   use, intrinsic :: iso_c_binding, only: c_int64_t
@@ -14,7 +16,7 @@ module md_run_outputs
   use md_stats
   implicit none
   private
-  public :: write_run_statistics, write_rdf_file
+  public :: write_run_statistics, write_rdf_file, write_msd_vacf_file
 
 contains
 
@@ -120,6 +122,27 @@ contains
     end do
     close(iu_rdf)
   end subroutine write_rdf_file
+
+  ! msd_vacf_gpu.dat: per lag with at least one origin, lag, tau = lag * output_interval * dt, the origins, MSD and VACF
+  ! (ljmd_tcf_read / one run's column of ljmd_batch_tcf_read)
+  subroutine write_msd_vacf_file(filename, max_lag, output_interval, dt, counts, msd, vacf)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: max_lag
+    integer(kind=int_kind), intent(in) :: output_interval
+    real(kind=dp_kind), intent(in) :: dt
+    integer(c_int64_t), intent(in) :: counts(0:max_lag)
+    real(kind=dp_kind), intent(in) :: msd(0:max_lag), vacf(0:max_lag)
+    integer :: iu_tcf, ierr, lag
+    open(newunit=iu_tcf, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_msd_vacf_file(): cannot open msd_vacf_gpu.dat.'
+    write(iu_tcf, '(a)') '# lag   tau   origins   MSD   VACF'
+    do lag = 0, max_lag
+      if (counts(lag) <= 0) cycle
+      write(iu_tcf, '(i0,2x,es24.16e3,2x,i0,2(2x,es24.16e3))') lag, dble(lag) * dble(output_interval) * dt, &
+        counts(lag), msd(lag), vacf(lag)
+    end do
+    close(iu_tcf)
+  end subroutine write_msd_vacf_file
 
   subroutine write_curve(filename, header, errmsg, lag_max, c, cn)
     character(len=*), intent(in) :: filename, header, errmsg

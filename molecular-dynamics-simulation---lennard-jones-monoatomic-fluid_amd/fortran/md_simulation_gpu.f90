@@ -20,6 +20,11 @@
 ! (default 0 = off; > 0: g(r) with that many bins up to LJMD_RDF_RMAX, default half the box, is accumulated on the
 ! device -- ljmd_rdf_* -- at every sampling instant that writes an rva.dat record, over all particles, and
 ! outputs/one_run/rdf_gpu.dat gets the bin centres, integer counts and g(r), in the format of md_simulation_many_gpu;
+! every other output file is the same with and without it), LJMD_TCF_MAX_LAG (default 0 = off; > 0: MSD(tau) and
+! VACF(tau) of the resident system on the device -- ljmd_tcf_*, time-origin averaged over the same sampling instants,
+! every LJMD_TCF_ORIGIN_STRIDE-th of them (default 1) an origin -- and outputs/one_run/msd_vacf_gpu.dat gets, per lag
+! with at least one origin, lag, lag * output_interval * dt, the number of origins, MSD and VACF, in the format of
+! md_simulation_many_gpu; one-rank engines only: with LJMD_GPUS > 1 the program stops before an engine is created;
 ! every other output file is the same with and without it).
 !==============================================================================
 program md_simulation_gpu
@@ -30,7 +35,7 @@ program md_simulation_gpu
   use ljmd_c_api
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push
-  use md_run_outputs,   only: write_run_statistics, write_rdf_file
+  use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file
   implicit none
 
   type(sim_params) :: params
@@ -54,6 +59,10 @@ program md_simulation_gpu
   real(kind=dp_kind) :: rdf_rmax
   integer(c_int64_t), allocatable, target :: rdf_hist(:)
   integer(c_int64_t) :: rdf_snapshots
+  integer :: tcf_max_lag, tcf_stride
+  real(c_double), allocatable, target :: tcf_msd(:), tcf_vacf(:)           ! [tcf_max_lag + 1]
+  integer(c_int64_t), allocatable, target :: tcf_counts(:)
+  integer(c_int64_t) :: tcf_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -83,9 +92,19 @@ program md_simulation_gpu
   rdf_rmax = 0.5d0 * params%box_length
   call get_environment_variable('LJMD_RDF_RMAX', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) rdf_rmax
+  tcf_max_lag = 0
+  call get_environment_variable('LJMD_TCF_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) tcf_max_lag
+  if (tcf_max_lag < 0) stop 'md_simulation: LJMD_TCF_MAX_LAG must be >= 0.'
+  tcf_stride = 1
+  call get_environment_variable('LJMD_TCF_ORIGIN_STRIDE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) tcf_stride
+  if (tcf_stride < 1) stop 'md_simulation: LJMD_TCF_ORIGIN_STRIDE must be >= 1.'
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
+  if (n_gpus > 1 .and. tcf_max_lag > 0) &
+    error stop 'md_simulation: LJMD_TCF_MAX_LAG needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1) then
     allocate(device_list(n_gpus))
     device_list = [(int(k - 1, c_int32_t), k = 1, n_gpus)]
@@ -106,6 +125,8 @@ program md_simulation_gpu
                                  c_loc(state%vx), c_loc(state%vy), c_loc(state%vz)), engine, 'ljmd_set_state')
   if (rdf_bins > 0) call ljmd_check(ljmd_rdf_configure(engine, int(rdf_bins, c_int32_t), rdf_rmax), engine, &
                                     'ljmd_rdf_configure')
+  if (tcf_max_lag > 0) call ljmd_check(ljmd_tcf_configure(engine, int(tcf_max_lag, c_int32_t), int(tcf_stride, c_int32_t)), &
+                                       engine, 'ljmd_tcf_configure')
   ! t = 0 forces and energies (:236-243)
   call ljmd_check(ljmd_compute_forces(engine, epot, d_epot, dd_epot), engine, 'ljmd_compute_forces')
   call ljmd_check(ljmd_kinetic_energy(engine, ekin), engine, 'ljmd_kinetic_energy')
@@ -149,6 +170,7 @@ program md_simulation_gpu
     if (sample_now) call ljmd_check(ljmd_snapshot_begin(engine), engine, 'ljmd_snapshot_begin')
     ! g(r) of the same instant, on the device, ahead of the next segment in the engine's stream
     if (sample_now .and. rdf_bins > 0) call ljmd_check(ljmd_rdf_accumulate(engine), engine, 'ljmd_rdf_accumulate')
+    if (sample_now .and. tcf_max_lag > 0) call ljmd_check(ljmd_tcf_accumulate(engine), engine, 'ljmd_tcf_accumulate')
     count = segment_length(step)
     if (async_io .and. count > 0) call enqueue_segment(count)
     if (sample_now) then
@@ -173,12 +195,19 @@ program md_simulation_gpu
     allocate(rdf_hist(rdf_bins))
     call ljmd_check(ljmd_rdf_read(engine, c_loc(rdf_hist), rdf_snapshots), engine, 'ljmd_rdf_read')
   end if
+  if (tcf_max_lag > 0) then
+    allocate(tcf_msd(0:tcf_max_lag), tcf_vacf(0:tcf_max_lag), tcf_counts(0:tcf_max_lag))
+    call ljmd_check(ljmd_tcf_read(engine, c_loc(tcf_msd), c_loc(tcf_vacf), c_loc(tcf_counts), tcf_snapshots), engine, &
+                    'ljmd_tcf_read')
+  end if
   call ljmd_destroy(engine)
 
   if (num_samples <= 0) stop 'md_simulation: no samples were taken (check warmup_steps/output_interval).'
   call write_run_statistics('outputs/one_run', params, total_steps, output_interval, warmup_steps, stats)
   if (rdf_bins > 0) call write_rdf_file('outputs/one_run/rdf_gpu.dat', params%n, params%box_length, rdf_rmax, rdf_bins, &
                                         rdf_hist, rdf_snapshots)
+  if (tcf_max_lag > 0) call write_msd_vacf_file('outputs/one_run/msd_vacf_gpu.dat', tcf_max_lag, output_interval, params%dt, &
+                                                tcf_counts, tcf_msd, tcf_vacf)
   write(*, '(a,i0,a,i0,a,f10.2,a,es11.4,a)') 'md_simulation_gpu: N=', params%n, ' steps=', total_steps, &
     '  ', dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' steps/s  ', &
     0.5d0 * npd * (npd - 1.d0) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' pair-interactions/s'

@@ -45,7 +45,7 @@ program md_simulation_many_gpu
   use ljmd_c_api
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push
-  use md_run_outputs,   only: write_run_statistics, write_rdf_file
+  use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file
   implicit none
 
   character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
@@ -263,7 +263,8 @@ program md_simulation_many_gpu
   end if
   if (tcf_max_lag > 0) then
     do i = 1, n_runs
-      call write_msd_vacf(i)
+      call write_msd_vacf_file(trim(run_dir(i)) // '/msd_vacf_gpu.dat', tcf_max_lag, output_interval, rparams(i)%dt, &
+                               tcf_counts, tcf_msd(:, i), tcf_vacf(:, i))
     end do
   end if
   if (any_own) then
@@ -314,22 +315,6 @@ contains
     call write_rdf_file(trim(run_dir(irun)) // '/rdf_gpu.dat', rparams(irun)%n, rparams(irun)%box_length, &
                         0.5d0 * rparams(irun)%box_length, rdf_bins, rdf_hist(:, irun), rdf_snapshots)
   end subroutine write_rdf
-
-  ! run i's msd_vacf_gpu.dat: per lag with at least one origin, lag, tau = lag * output_interval * dt of the run, the
-  ! origins, MSD and VACF (ljmd_batch_tcf_read)
-  subroutine write_msd_vacf(irun)
-    integer, intent(in) :: irun
-    integer :: iu_tcf, ierr, lag
-    open(newunit=iu_tcf, file=trim(run_dir(irun)) // '/msd_vacf_gpu.dat', status='replace', action='write', iostat=ierr)
-    if (ierr /= 0) stop 'md_simulation_many: cannot open msd_vacf_gpu.dat of a run.'
-    write(iu_tcf, '(a)') '# lag   tau   origins   MSD   VACF'
-    do lag = 0, tcf_max_lag
-      if (tcf_counts(lag) <= 0) cycle
-      write(iu_tcf, '(i0,2x,es24.16e3,2x,i0,2(2x,es24.16e3))') lag, dble(lag) * dble(output_interval) * rparams(irun)%dt, &
-        tcf_counts(lag), tcf_msd(lag, irun), tcf_vacf(lag, irun)
-    end do
-    close(iu_tcf)
-  end subroutine write_msd_vacf
 
   ! LJMD_SEED_BASE: every run's initial configuration on the device (seed_base + i - 1, the run's target_total_energy,
   ! the shared warmup_steps), then each run's rv_init_gpu.dat: the two records of rv_init.dat

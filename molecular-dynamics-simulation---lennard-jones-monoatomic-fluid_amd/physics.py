@@ -373,6 +373,65 @@ class Engine:
         self._ck(self._lib.ljmd_rdf_profile_read(self._h, C.byref(vis), C.byref(tot), C.byref(ms)))
         return {"tile_pairs_visited": vis.value, "tile_pairs_total": tot.value, "kernel_ms": ms.value}
 
+    # -- MSD / VACF of the resident system (include/ljmd.h: ljmd_tcf_*) --------------------
+    def tcf_configure(self, max_lag: int, origin_stride: int = 1) -> None:
+        """ljmd_tcf_configure: time-origin averaged MSD(tau) and VACF(tau) up to lag max_lag (in snapshots), every
+        origin_stride-th snapshot an origin; max_lag = 0 switches the feature off.  Zeroes the sums.  One-rank engines
+        only."""
+        for name, val in (("max_lag", max_lag), ("origin_stride", origin_stride)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise TypeError(f"tcf_configure: {name} must be an integer, got {val!r}")
+        self._ck(self._lib.ljmd_tcf_configure(self._h, int(max_lag), int(origin_stride)))
+        self._tcf_max_lag = int(max_lag)
+
+    def tcf_accumulate(self) -> None:
+        """takes the resident ru and v as the next snapshot (stream-ordered: no host wait)"""
+        self._ck(self._lib.ljmd_tcf_accumulate(self._h))
+
+    def _tcf_rows(self, who: str) -> int:
+        max_lag = getattr(self, "_tcf_max_lag", 0)
+        if max_lag < 1:
+            raise ValueError(f"{who}: call tcf_configure with max_lag >= 1 first")
+        return max_lag + 1
+
+    def tcf_read(self):
+        """-> (msd[max_lag + 1], vacf[max_lag + 1], counts[max_lag + 1] int64, n_snapshots); nothing is cleared"""
+        rows = self._tcf_rows("tcf_read")
+        msd = np.empty(rows, dtype=np.float64)
+        vacf = np.empty(rows, dtype=np.float64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_tcf_read(self._h, msd.ctypes.data_as(c_double_p), vacf.ctypes.data_as(c_double_p),
+                                         counts.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        return msd, vacf, counts, snaps.value
+
+    def tcf_read_exact(self, raw: bool = False):
+        """-> (sums, counts, n_snapshots): the exact integer sums of Q(term) = RNE(term 2^64), sums[kind, lag] with kind
+        0 = MSD, 1 = VACF, as Python ints in an object array -- or, raw=True, the library's int64 words
+        [2, max_lag + 1, 3] (three little-endian limbs of a signed 192-bit integer)"""
+        rows = self._tcf_rows("tcf_read_exact")
+        words = np.empty((2, rows, 3), dtype=np.int64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_tcf_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p),
+                                               counts.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        if raw:
+            return words, counts, snaps.value
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:2], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums, counts, snaps.value
+
+    def tcf_reset(self) -> None:
+        self._ck(self._lib.ljmd_tcf_reset(self._h))
+
+    def tcf_profile(self) -> dict:
+        """ljmd_tcf_profile_read for the most recent tcf_accumulate -> {'kernel_ms', 'origins_live'}"""
+        ms, live = C.c_double(), C.c_int32()
+        self._ck(self._lib.ljmd_tcf_profile_read(self._h, C.byref(ms), C.byref(live)))
+        return {"kernel_ms": ms.value, "origins_live": live.value}
+
     # -- measurement -----------------------------------------------------------
     def profile_enable(self, on: bool = True) -> None:
         self._ck(self._lib.ljmd_profile_enable(self._h, 1 if on else 0))
