@@ -113,6 +113,8 @@ struct Knobs {
     std::optional<int> n3_target_waves;     // LJMD_N3_TARGET_WAVES: work items the pair kernel aims at (unset: by system size)
     bool n3_clusters = true;                // LJMD_N3_CLUSTERS: cluster passes (4-tile row groups, one wave per workgroup)
     bool n3_pertile = true;                 // LJMD_N3_PERTILE: per-tile periodic images in the geometry pre-pass
+    std::optional<int> reduce_split;        // LJMD_REDUCE_SPLIT: slices of the pair kernel run in a second launch beside the slab
+                                            // reduction's first phase (0 = one launch; unset: by system size)
     bool fp32_far_stream = true;            // LJMD_FP32_FAR_STREAM: the fp32 far pass on a stream of its own
     bool fp32_vfar = true;                  // LJMD_FP32_VFAR: the very-far form of the fp32 kernel
     double fp32_split = 5.0;                // LJMD_FP32_SPLIT: boxes closer than this stay fp64

@@ -88,6 +88,7 @@ N3Args n3_args(ljmd_t *h)
     a.by_group = h->plan.j_by_group;
     a.dchunk = h->plan.dchunk;
     a.uchunk = h->plan.uchunk;
+    a.by0 = 0;
     a.xcd_remap = 0;
     a.inline_class = (h->plan.fuse_tail && h->plan.rt <= 2 && h->plan.wg_waves == 1) ? 1 : 0;
     a.both_ties = h->plan.both_ties ? 1 : 0;
@@ -140,6 +141,9 @@ ReduceArgs reduce_args(ljmd_t *h, int nslab, bool n3)
     a.CS = h->plan.CS;
     a.CS2 = h->plan.CS2;
     a.RT = h->plan.rt;
+    a.partial = h->d_red_part;
+    a.c_split = h->plan.split_s1;
+    a.j_split = h->plan.split_j1;
     return a;
 }
 
@@ -280,6 +284,7 @@ int enqueue_pair_forces(ljmd_t *h, EventSet *q)
     }
     int nslab, n_wg;
     bool n3 = false;
+    bool split = false;             // the slab reduction's first phase is already enqueued: the second one is left
     if (fast) {
         GeometryArgs ga = geometry_args(h);
         if (!h->plan.use_n3) ga.mask_far = nullptr;
@@ -303,7 +308,23 @@ int enqueue_pair_forces(ljmd_t *h, EventSet *q)
             // mixed precision: the two pair kernels write disjoint slabs and partials -- the far pass (the long one) goes to
             // its own stream first and the near pass, mostly descriptor look-ups with a few passes between them, runs beside it
             const bool far_beside = h->mode == LJMD_PRECISION_FP32_FORCE && h->far_stream != nullptr;
-            if (far_beside) {
+            split = h->plan.split_s1 > 0 && h->side_stream != nullptr;
+            if (split) {
+                // Two launches over disjoint slices (LaunchPlan::split_s1).  The second needs nothing of the first and goes to
+                // the side stream, whose priority is the lowest: its workgroups fill the first launch's drain, and the first
+                // phase of the slab reduction -- HBM-bound, over what the first launch completed -- runs beside it.  The
+                // streams join before the second phase.
+                const int s1 = h->plan.split_s1;
+                LJMD_HIP(h, hipEventRecord(h->ev_side_go, h->stream));
+                LJMD_HIP(h, hipStreamWaitEvent(h->side_stream, h->ev_side_go, 0));
+                LJMD_HIP(h, launch_pair_n3(na, dim3(grid.x, s1), h->plan.wg_waves, h->stream));
+                N3Args nb = na;
+                nb.by0 = s1;
+                LJMD_HIP(h, launch_pair_n3(nb, dim3(grid.x, grid.y - s1), h->plan.wg_waves, h->side_stream));
+                LJMD_HIP(h, launch_reduce_forces_split(reduce_args(h, h->plan.nslab_n, true), 1, h->stream));
+                LJMD_HIP(h, hipEventRecord(h->ev_side_done, h->side_stream));
+                LJMD_HIP(h, hipStreamWaitEvent(h->stream, h->ev_side_done, 0));
+            } else if (far_beside) {
                 LJMD_HIP(h, hipEventRecord(h->ev_far_go, h->stream));
                 LJMD_HIP(h, hipStreamWaitEvent(h->far_stream, h->ev_far_go, 0));
             } else {
@@ -356,6 +377,8 @@ int enqueue_pair_forces(ljmd_t *h, EventSet *q)
     if (h->reduce_deferred) {            // the tail launch of enqueue_kick reduces, kicks and folds the record in one kernel
         h->deferred_nslab = nslab;
         h->deferred_n3 = n3;
+    } else if (split) {
+        LJMD_HIP(h, launch_reduce_forces_split(reduce_args(h, nslab, n3), 2, h->stream));
     } else {
         LJMD_HIP(h, launch_reduce_forces(reduce_args(h, nslab, n3), needs_force_exchange(h), h->stream));
     }

@@ -36,6 +36,8 @@ constexpr int kN3MidTargetItems = 32768;   // work items aimed at below that on 
 constexpr int kBothTiesMaxGroups = 128; // row groups up to which the tie d = NG / 2 is worked from both sides
 constexpr int kFuseTailMaxRowTiles = 2; // tiles per row group up to which small systems take the two-launch step ...
 constexpr int kFuseTailMaxN = 20000;    // ... and their largest particle count (n = 24 576: the in-kernel pass descriptors cost the pair kernel more than the launches save)
+constexpr int kReduceSplitMinN = 131072;   // one rank, fp64: from here the slab reduction runs in two phases (LaunchPlan::split_s1) ...
+constexpr int kReduceSplitShare = 8;       // ... with 1 / this of the pair kernel's slices in the second launch (profiles/reduce_split_sweep.txt)
 constexpr int kMaxProfiledLaunches = 4096;
 constexpr int kEventsPerLaunch = 9;
 
@@ -71,6 +73,10 @@ struct LaunchPlan {
     // LJMD_FUSE_TAIL (default on): small single-rank systems run a step as TWO launches -- the pair kernel with its pass
     // descriptors worked out in-kernel, and tile_tail_kernel (slab reduction + kick + step record + the NEXT step's K1)
     bool fuse_tail = false;
+    // LJMD_REDUCE_SPLIT: the pair kernel runs the slices [0, split_s1) and [split_s1, nslab_n) in two launches, and the slab
+    // reduction sums what the first one completed -- those row-side slices and the blocks j < split_j1 of every column tile --
+    // beside the second (enqueue_pair_forces).  0 = one launch, one-phase reduction
+    int split_s1 = 0, split_j1 = 0;
     int nslab_max = 1, n_wg_max = 0;  // slices of d_slab, workgroup partials of d_wg_part: the largest of the kernel families
     int n_ke = 0;
 };
@@ -160,6 +166,11 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     size_t wg_part_stride = 0;        // doubles per wg_part buffer
     double *d_slab_j = nullptr;
     unsigned char *d_flag_j = nullptr;
+    // two-phase slab reduction (LaunchPlan::split_s1): the four waves' partial sums per tile, the stream of lowest priority
+    // that carries the pair kernel's second launch, and the two events that fence it against the engine's stream
+    double *d_red_part = nullptr;     // [TB][4][3][64]
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_side_go = nullptr, ev_side_done = nullptr;
     // mixed precision (mode = LJMD_PRECISION_FP32_FORCE): far tile pairs in fp32
     uint64_t *d_mask_far = nullptr;
     double *d_slab_j2 = nullptr;

@@ -74,6 +74,8 @@ struct N3Args {
     int CS, by_group;       // slab_j layout (above)
     int RT;                 // tiles per row group: 4 for large systems, 1 or 2 to give small ones enough work items
     int dchunk;             // fp32 far kernel: offsets d per grid.y slice
+    int by0;                // pair_n3_kernel: slice of this launch's blockIdx.y == 0.  0 unless the step runs the slices in two
+                            // launches (LaunchPlan::split_s1): the work item of a slice does not depend on which launch runs it
     int uchunk;             // pair_n3_kernel: UNITS per grid.y slice.  Unit u of a row group = e * RT + l: offset e, column tile l of
                             // the group there (one pass); = dchunk * RT unless the system is cut finer
     int energy;             // 0: forces only -- the energy sums are not accumulated and the workgroup partials are NaN
@@ -114,6 +116,10 @@ struct ReduceArgs {
     int nslab, P, G, rank, TB;
     int CS, CS2;            // blocks per column tile of slab_j / slab_j2 (N3Args::slab_j)
     int RT;                 // tiles per Newton-3 row group of this engine (1, 2 or 4)
+    // two-phase form (reduce_forces_split_kernel; one rank): phase 1 sums the row-side slices c < c_split and the blocks
+    // j < j_split of every column tile and leaves the four waves' partial sums in `partial`; phase 2 continues from them
+    double *partial;        // [TB][4][3][64], or NULL
+    int c_split, j_split;
 };
 
 struct FinalizeArgs {
@@ -268,6 +274,7 @@ hipError_t launch_pair_n3(const N3Args &a, dim3 grid, int wg_waves, hipStream_t 
 hipError_t launch_pair_n3_f32(const N3Args &a, dim3 grid, hipStream_t s);
 hipError_t launch_drift_kick(const IntegrateArgs &a, int phase /* 0 all, 1 positions, 2 velocities */, hipStream_t s);
 hipError_t launch_reduce_forces(const ReduceArgs &a, bool all_blocks, hipStream_t s);
+hipError_t launch_reduce_forces_split(const ReduceArgs &a, int phase /* 1 or 2 */, hipStream_t s);
 hipError_t launch_kick(const IntegrateArgs &a, bool kick, hipStream_t s);
 // kick + finalize in one launch: the last block to finish folds the partials (needs a.ticket, f.n_wg <= kDirectFoldMax)
 hipError_t launch_kick_finalize(const IntegrateArgs &a, const FinalizeArgs &f, bool kick, hipStream_t s);

@@ -1064,6 +1064,7 @@ __global__ __launch_bounds__(kTile * W, MIN_WAVES) void pair_n3_kernel(N3Args a)
         by = slot / per;
         bx = ((s / C) * 8u + xcd) * C + s % C;
     }
+    by += (unsigned)a.by0;                          // the slice: this launch runs the slices by0 .. by0 + gridDim.y - 1
 #ifdef LJMD_WAVE_TRACE
     const unsigned long long tr0 = trace_now();
     unsigned long long tr1 = tr0;
@@ -1729,6 +1730,93 @@ __global__ __launch_bounds__(kBlock) void reduce_forces_kernel(ReduceArgs a)
 #pragma unroll
             for (int w = 1; w < kWavesPerBlock; ++w) t += part[w][ax][lane];
             a.fpart[(size_t)(gridDim.y == 1 ? 0 : g) * 3 * a.P + (size_t)ax * a.P + i] = t;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// K3a in two phases (one rank, one wave per pair workgroup, blocks numbered by offset: LaunchPlan::split_s1).  The pair kernel
+// runs its slices in two launches; the first completes the row-side slices c < c_split and, of every column tile, the
+// blocks j < j_split.  PHASE 1 runs beside the second launch: wave q sums the slices c < c_split, c = q, q + 4, ...
+// ascending, then the flagged blocks j < j_split, j = q, q + 4, ... ascending, and stores its partial sum.  PHASE 2 runs behind
+// both launches: wave q reloads its partial, adds the slices c >= c_split and then the blocks j >= j_split in the same
+// strided ascending order, and the four partials are combined as reduce_forces_kernel does.  The order depends on
+// (c_split, j_split, nslab, CS) only.  grid = (P / 64).
+// ---------------------------------------------------------------------------
+template <int PHASE>
+__global__ __launch_bounds__(kBlock) void reduce_forces_split_kernel(ReduceArgs a)
+{
+    __shared__ double part[kWavesPerBlock][3][kTile];
+    const int lane = threadIdx.x & 63, q = threadIdx.x >> 6;
+    const int i = blockIdx.x * kTile + lane;                    // slot; blockIdx.x = the column tile
+    double *mine = a.partial + ((size_t)blockIdx.x * kWavesPerBlock + q) * (3 * kTile) + lane;
+    double s[3] = {0.0, 0.0, 0.0};
+    if constexpr (PHASE == 2) {
+        s[0] = mine[0];
+        s[1] = mine[kTile];
+        s[2] = mine[2 * kTile];
+    }
+    const int c_lo = PHASE == 1 ? 0 : a.c_split, c_hi = PHASE == 1 ? a.c_split : a.nslab;
+    for (int c = c_lo + ((q - c_lo) & (kWavesPerBlock - 1)); c < c_hi; c += kWavesPerBlock) {   // first c >= c_lo with c % 4 == q
+        const double *sl = a.slab + (size_t)c * 3 * a.P + i;
+        s[0] += sl[0];
+        s[1] += sl[a.P];
+        s[2] += sl[2 * (size_t)a.P];
+    }
+    {
+        // as add_blocks of reduce_forces_kernel, over the blocks [j_lo, j_hi) only: a flag outside the range may be one the
+        // pair kernel's second launch is writing at this moment -- it is read with its 64 neighbours and masked out
+        constexpr int U = 4;
+        const int j_lo = PHASE == 1 ? 0 : a.j_split, j_hi = PHASE == 1 ? a.j_split : a.CS;
+        const int qs = __builtin_amdgcn_readfirstlane(q);
+        const size_t base = (size_t)blockIdx.x * a.CS;
+        const int j_first = j_lo & ~(kTile - 1);
+        unsigned f = j_first + lane < j_hi ? a.flag_j[base + j_first + lane] : 0u;
+        for (int j0 = j_first; j0 < j_hi; j0 += kTile) {
+            unsigned long long m = __ballot(f != 0u && j0 + lane >= j_lo) & (0x1111111111111111ull << qs);
+            const int jn = j0 + kTile + lane;
+            const unsigned fn = jn < j_hi ? a.flag_j[base + jn] : 0u;
+            while (m) {
+                double v[U][3];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    v[u][0] = v[u][1] = v[u][2] = 0.0;
+                    if (m) {
+                        const int j = j0 + __builtin_ctzll(m);
+                        m &= m - 1;
+                        const double *b = a.slab_j + (base + j) * (3 * kTile) + lane;
+                        v[u][0] = b[0];
+                        v[u][1] = b[kTile];
+                        v[u][2] = b[2 * kTile];
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    s[0] += v[u][0];
+                    s[1] += v[u][1];
+                    s[2] += v[u][2];
+                }
+            }
+            f = fn;
+        }
+    }
+    if constexpr (PHASE == 1) {
+        mine[0] = s[0];
+        mine[kTile] = s[1];
+        mine[2 * kTile] = s[2];
+    } else {
+        part[q][0][lane] = s[0];
+        part[q][1][lane] = s[1];
+        part[q][2][lane] = s[2];
+        __syncthreads();
+        if (q == 0) {
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                double t = part[0][ax][lane];
+#pragma unroll
+                for (int w = 1; w < kWavesPerBlock; ++w) t += part[w][ax][lane];
+                a.fpart[(size_t)ax * a.P + i] = t;
+            }
         }
     }
 }
@@ -2408,6 +2496,16 @@ hipError_t launch_reduce_forces(const ReduceArgs &a, bool all_blocks, hipStream_
         hipLaunchKernelGGL(reduce_forces_kernel<true>, grid, dim3(kBlock), 0, s, a);
     else
         hipLaunchKernelGGL(reduce_forces_kernel<false>, grid, dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_reduce_forces_split(const ReduceArgs &a, int phase, hipStream_t s)
+{
+    const dim3 grid(a.P / kTile);
+    if (phase == 1)
+        hipLaunchKernelGGL(reduce_forces_split_kernel<1>, grid, dim3(kBlock), 0, s, a);
+    else
+        hipLaunchKernelGGL(reduce_forces_split_kernel<2>, grid, dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

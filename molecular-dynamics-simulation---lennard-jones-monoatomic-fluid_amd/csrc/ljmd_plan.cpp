@@ -5,6 +5,16 @@
 
 namespace ljmdh {
 
+namespace {
+// smallest m > 0 with m * uchunk a multiple of rt
+int rt_align(int uchunk, int rt)
+{
+    int m = 1;
+    while ((m * uchunk) % rt != 0) ++m;
+    return m;
+}
+}  // namespace
+
 int plan_engine(const SimParams &sim, int n, int n_ranks, int precision_mode, const Knobs &k, LaunchPlan *out)
 {
     LaunchPlan p;
@@ -134,6 +144,20 @@ int plan_engine(const SimParams &sim, int n, int n_ranks, int precision_mode, co
     // two launches per step for small single-rank systems (tile_tail_kernel; ljmd_engine.h: fuse_tail)
     p.fuse_tail = k.fuse && k.fuse_tail && n_ranks == 1 && n <= kFuseTailMaxN && p.rc_allows_fast &&
                   precision_mode == LJMD_PRECISION_FP64 && (!p.use_n3 || (p.rt <= kFuseTailMaxRowTiles && p.wg_waves == 1));
+    // the pair kernel's slices in two launches, most of the slab reduction beside the second (LaunchPlan::split_s1): one rank,
+    // fp64, 4-tile row groups, one wave per workgroup, blocks numbered by offset.  The first launch must end on a whole offset
+    // -- split_s1 * uchunk a multiple of rt -- so that it completes the blocks j < split_j1 of every column tile.
+    if (n_ranks == 1 && precision_mode == LJMD_PRECISION_FP64 && p.use_n3 && p.rc_allows_fast && !p.fuse_tail &&
+        p.rt == kRowTiles && p.wg_waves == 1 && !p.j_by_group && !k.force_collectives) {
+        const int S = p.nslab_n;
+        const int m = rt_align(p.uchunk, p.rt);                               // slices per whole number of offsets
+        const int deferred = k.reduce_split.value_or(n >= kReduceSplitMinN ? (S + kReduceSplitShare - 1) / kReduceSplitShare : 0);
+        if (deferred >= 1 && m < S) {
+            const int s1 = std::max(m, (std::max(0, S - deferred) / m) * m);
+            p.split_s1 = s1;
+            p.split_j1 = s1 * p.uchunk / p.rt;
+        }
+    }
     const bool mixed = precision_mode == LJMD_PRECISION_FP32_FORCE;
     if (mixed && (!p.use_n3 || n < kMixedMinN))
         // the fp32 far kernel works on 4-tile row groups and only pays where most pairs are far pairs

@@ -30,6 +30,14 @@ int allocate_engine(ljmd_t *h)
             LJMD_HIP(h, hipMalloc(&h->d_desc2, (size_t)h->plan.NGo * h->plan.T * 8 * sizeof(float)));
         LJMD_HIP(h, hipMalloc(&h->d_pos_tc, P3 * h->G));
     }
+    if (h->plan.split_s1 > 0) {
+        LJMD_HIP(h, hipMalloc(&h->d_red_part, (size_t)h->plan.TB * kWavesPerBlock * 3 * kTile * sizeof(double)));
+        int least = 0, greatest = 0;       // numerically: least = the lowest priority
+        LJMD_HIP(h, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        LJMD_HIP(h, hipStreamCreateWithPriority(&h->side_stream, hipStreamNonBlocking, least));
+        LJMD_HIP(h, hipEventCreateWithFlags(&h->ev_side_go, hipEventDisableTiming));
+        LJMD_HIP(h, hipEventCreateWithFlags(&h->ev_side_done, hipEventDisableTiming));
+    }
     if (mixed && h->knobs.fp32_far_stream) {
         LJMD_HIP(h, hipStreamCreateWithFlags(&h->far_stream, hipStreamNonBlocking));
         LJMD_HIP(h, hipEventCreateWithFlags(&h->ev_far_go, hipEventDisableTiming));
@@ -103,6 +111,12 @@ void release(ljmd_t *h)
         (void)hipStreamSynchronize(h->far_stream);
         (void)hipStreamDestroy(h->far_stream);
     }
+    if (h->side_stream) {
+        (void)hipStreamSynchronize(h->side_stream);
+        (void)hipStreamDestroy(h->side_stream);
+    }
+    if (h->ev_side_go) (void)hipEventDestroy(h->ev_side_go);
+    if (h->ev_side_done) (void)hipEventDestroy(h->ev_side_done);
     if (h->ev_far_go) (void)hipEventDestroy(h->ev_far_go);
     if (h->ev_far_done) (void)hipEventDestroy(h->ev_far_done);
     if (h->ev_pos_ready) (void)hipEventDestroy(h->ev_pos_ready);
@@ -113,7 +127,7 @@ void release(ljmd_t *h)
                    h->d_ring_pos, h->d_bbox, h->d_mask, h->d_idx, h->d_idx2,
                    h->d_perm, h->d_perm2, h->d_tmp3, h->d_cub, h->d_slab_j, h->d_flag_j, h->d_fpart, h->d_frecv, h->d_fall,
                    h->d_kd_offsets, h->d_kd_keys, h->d_kd_keys2, h->d_mask_far, h->d_slab_j2, h->d_flag_j2, h->d_fold, h->d_ticket,
-                   h->d_desc, h->d_desc_far, h->d_desc2, h->d_ke_tile, h->d_pos_tc, h->d_gid0, h->d_mig, h->d_mig_idx, h->d_mig_idx2, h->d_mig_keys,
+                   h->d_desc, h->d_desc_far, h->d_desc2, h->d_red_part, h->d_ke_tile, h->d_pos_tc, h->d_gid0, h->d_mig, h->d_mig_idx, h->d_mig_idx2, h->d_mig_keys,
                    h->d_mig_keys2, h->d_mig_offsets, h->d_mig_cub, h->d_fslab, h->d_fflag, h->d_fblk, h->d_frec};
     for (void *p : dev) (void)hipFree(p);
     if (h->h_stage) (void)hipHostFree(h->h_stage);
