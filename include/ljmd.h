@@ -491,6 +491,67 @@ int ljmd_tcf_read_exact(ljmd_t *h, int64_t *words /* [2][max_lag+1][3] */, int64
 int ljmd_tcf_reset(ljmd_t *h);
 int ljmd_tcf_profile_read(ljmd_t *h, double *kernel_ms, int32_t *origins_live);
 
+/*
+ * Pressure tensor of the resident system, one snapshot per call, recorded where r and v live (ljmd_stress_*): no
+ * snapshot leaves the device.  One-rank engines, rank engines and multi-device handles; n <= 2^23.
+ *
+ * Definition.  Components c in the order xx, yy, zz, xy, xz, yz.  One snapshot is 12 signed 192-bit integers, K[6]
+ * then S[6], each three int64 limbs, least significant first (the layout of ljmd_tcf_read_exact).
+ *   Kinetic part: for every particle the terms vx*vx, vy*vy, vz*vz, vx*vy, vx*vz, vy*vz of the resident velocities, each
+ *   entering K[c] as Q(t) = RNE(t 2^64).
+ *   Virial part, over the ORDERED pairs i != j of the wrapped positions resident now, the arithmetic of the
+ *   reproducible mode's pair kernel, unfused, left to right:
+ *     d0 = x_i - x_j ; d = d0 - L * round(d0 * invL) (half away from zero) per axis ; r2 = dx*dx + dy*dy + dz*dz ;
+ *     if r2 < rc2 (strict): u = 1.0 / r2 ; u3 = u*u*u ; u6 = u3*u3 ; mdu = 2.0*u6 - u3 ; fx = mdu*dx*u, fy, fz likewise;
+ *     terms fx*dx, fy*dy, fz*dz, fx*dy, fx*dz, fy*dz, each entering S[c] as Q(t).
+ *   Under i <-> j every d and f changes sign exactly, so an unordered pair may be evaluated once and added twice: the
+ *   integer is the same.
+ *   Range: a pair is out of range when any of fx, fy, fz, u6 or of its six products is not finite or has |t| >= 2^40;
+ *   all six of its terms then enter as 0 and a sticky word is set.  The same holds for a particle's six velocity
+ *   products.  An arithmetic flag: nothing wraps, nothing faults.
+ *   Doubles: p[c] = (R(K[c]) + 12.0 * R(S[c])) / V with V = (L*L)*L and R(x) = RNE(x) 2^-64, ONE rounding of the integer
+ *   -- the host-only ljmd_stress_from_exact(words[12][3], L, out[6]).  No tail correction: ljmd_set_tail_corrections
+ *   does not apply, and the isotropic tail term is the caller's to add to the diagonal.  12 (S_xx + S_yy + S_zz) is
+ *   -(d_epot without tail) up to per-term rounding; K_xx + K_yy + K_zz is 2 ekin.
+ * The integers depend on the particle set alone: not on slot order, re-sorts, tiling, ranks, ownership migration,
+ * precision mode or knobs.
+ * configure: 1 <= max_snapshots <= LJMD_STRESS_MAX_SNAPSHOTS and n <= 2^23; allocates and zeroes the series on the
+ * device (288 bytes per snapshot); calling it again reconfigures and zeroes; 0 switches the feature off and frees it.
+ * A failed guard returns LJMD_ERR_INVALID_ARG and leaves the earlier configuration in place; a failed allocation
+ * LJMD_ERR_ALLOC with the feature off.  Works with or without a state.  ljmd_set_state, the other setters, ljmd_rdf_*,
+ * ljmd_tcf_* and ljmd_migrate leave configuration and series alone.
+ * accumulate: appends one snapshot, stream-ordered on the engine's stream behind everything enqueued so far
+ * (ljmd_enqueue_steps* included), no host wait.  Guards and their order are those of ljmd_rdf_accumulate:
+ * LJMD_ERR_STATE before configure, without a state, without valid accelerations, on a poisoned handle and between
+ * ljmd_step_begin and ljmd_step_finish; then LJMD_ERR_STATE when the series is full, before anything is launched.  It
+ * reads the exchange buffer and the velocities and writes only buffers of its own: r, ru, v, a, the step records and
+ * every later result stay bitwise what they are without the call.
+ * read_exact / read: wait for the device; words[n][12][3] (read_exact) or p[n][6] (read) for the n snapshots taken
+ * since configure / reset, and n -- any pointer may be NULL; they clear nothing.  While the sticky word is set they
+ * return LJMD_ERR_RANGE, until ljmd_stress_reset; the handle is not poisoned and stepping is unaffected.
+ * reset: empties the series and clears the sticky word.
+ * profile_read, for the most recent accumulate (zeros before the first): the (row tile, column tile) pairs of 64 x 64
+ * particles its walk evaluated, the pairs it considered (evaluated + skipped because their bounding boxes are provably
+ * farther apart than rc), and the time of its launches from HIP events; any pointer may be NULL; waits for the device.
+ * read_exact, read, reset and profile_read return LJMD_ERR_STATE before configure.
+ * Ranks.  On a rank engine (ljmd_create with n_ranks > 1) a snapshot sums the ordered pairs (i owned by this rank, j
+ * any other particle of the system) and the velocity products of the own particles, and read_exact returns this
+ * partial: the partials of the ranks add up, as integers, to the definition above.  read is refused there
+ * (LJMD_ERR_STATE: add the words, then ljmd_stress_from_exact).  The rank's exchange buffer must hold everybody's
+ * current positions, which is the case whenever the accelerations are valid and the caller has run the exchanges it
+ * is responsible for (after ljmd_migrate_deal: the position exchange).  On a multi-device handle (ljmd_create_multi)
+ * accumulate runs on every rank, read_exact / read add the ranks' words in 192 bits on the host, profile_read returns
+ * the tile-pair counts summed over the ranks and the longest of their times.
+ */
+#define LJMD_STRESS_MAX_SNAPSHOTS 262144
+int ljmd_stress_configure(ljmd_t *h, int32_t max_snapshots);
+int ljmd_stress_accumulate(ljmd_t *h);
+int ljmd_stress_read_exact(ljmd_t *h, int64_t *words /* [n][12][3] */, int64_t *n_snapshots);
+int ljmd_stress_read(ljmd_t *h, double *p /* [n][6] */, int64_t *n_snapshots);
+int ljmd_stress_reset(ljmd_t *h);
+int ljmd_stress_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *tile_pairs_total, double *kernel_ms);
+int ljmd_stress_from_exact(const int64_t *words /* [12][3] */, double box_length, double *out6);
+
 /* ---- batch engine: many independent small systems on one device ------------------------------------------------
  *
  * One ljmd_batch_t holds B replicas on one device -- the ensemble runs of the reference's run-many framework

@@ -137,6 +137,13 @@ PROTOTYPES = {
     "ljmd_tcf_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]),
     "ljmd_tcf_reset": (C.c_int, [C.c_void_p]),
     "ljmd_tcf_profile_read": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
+    "ljmd_stress_configure": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ljmd_stress_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_stress_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ljmd_stress_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
+    "ljmd_stress_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_stress_profile_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_double_p]),
+    "ljmd_stress_from_exact": (C.c_int, [c_int64_p, C.c_double, c_double_p]),
     "ljmd_batch_rdf_configure": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     "ljmd_batch_rdf_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_batch_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
@@ -155,6 +162,7 @@ BATCH_TCF_MAX_LAG = 4096
 BATCH_TCF_MAX_ORIGINS = 512
 TCF_MAX_LAG = 4096
 TCF_MAX_ORIGINS = 512
+STRESS_MAX_SNAPSHOTS = 262144
 
 _lib = None
 

@@ -126,3 +126,27 @@ def compute_vacf_tau_timeorig(vx, vy, vz, max_lag=None, origin_stride: int = 1) 
                        + vz[t0:t0 + lag + 1, :] * vz[t0, :][None, :], axis=1)
 
     return _time_origin_average((vx,), max_lag, origin_stride, term)
+
+
+def stress_acf(p, max_lag=None, origin_stride: int = 1):
+    """p [n_snap, 6]: a pressure-tensor series in the order xx, yy, zz, xy, xz, yz (Engine.stress_read) -> (shear,
+    normal): two autocorrelation functions of max_lag + 1 lags, each a mean over three components.  shear: the
+    time-origin average of sigma_xy, sigma_xz, sigma_yz; normal: the same of (sigma_xx - sigma_yy) / 2,
+    (sigma_yy - sigma_zz) / 2, (sigma_zz - sigma_xx) / 2.  Formula, origin convention and counts are those of
+    compute_vacf_tau_timeorig with the three components as the velocity of one particle."""
+    p = np.asarray(p, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 6:
+        raise ValueError(f"stress_acf: p must have shape (n_snap, 6), got {p.shape}")
+    xx, yy, zz, xy, xz, yz = (p[:, c][:, None] for c in range(6))
+    shear = compute_vacf_tau_timeorig(xy, xz, yz, max_lag, origin_stride) / 3.0
+    normal = compute_vacf_tau_timeorig(0.5 * (xx - yy), 0.5 * (yy - zz), 0.5 * (zz - xx), max_lag, origin_stride) / 3.0
+    return shear, normal
+
+
+def viscosity_green_kubo(acf, dt_sample: float, V: float, T: float) -> np.ndarray:
+    """Green-Kubo running shear viscosity eta(tau) = V / T * integral_0^tau acf, the integral by the trapezoid rule on the
+    sampling grid (eta[0] = 0); reduced units (k_B = 1)."""
+    acf = np.asarray(acf, dtype=np.float64)
+    run = np.zeros_like(acf)
+    run[1:] = np.cumsum(0.5 * (acf[1:] + acf[:-1]) * dt_sample)
+    return (V / T) * run

@@ -19,6 +19,7 @@
 
 #include "ljmd_internal.h"
 #include "ljmd_rdf.h"
+#include "ljmd_stress.h"
 #include "ljmd_tcf.h"
 
 using namespace ljmdk;
@@ -221,6 +222,9 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     ljmdr::RdfState rdf;
     // resident MSD / VACF (ljmd_tcf_*, ljmd_tcf.cpp): one-rank engines only
     ljmdt::TcfState tcf;
+    // resident pressure tensor (ljmd_stress_*, ljmd_stress.cpp); a multi-device parent keeps only max_snapshots and the
+    // snapshot count here.  Freed where a handle is destroyed (ljmd_capi.cpp, ljmd_multi.cpp), not by release()
+    ljmds::StressState stress;
     bool step_open = false;           // between ljmd_step_begin and ljmd_step_finish (split-phase API)
 
     bool profiling = false;

@@ -1,0 +1,103 @@
+// ljmd_stress.h -- pressure tensor of the system resident on the single / sharded engine (include/ljmd.h:
+// ljmd_stress_*): argument blocks of the three kernels of ljmd_stress.hip and the host core of ljmd_stress.cpp.
+//
+// The layout is the engine's (ljmd_internal.h): exchange buffer pos[G][3][P], velocities v[3][P] of the own block,
+// 64-slot tiles, TB tiles per rank block, T = G TB tiles, NaN positions and zero velocities on the padding slots.
+// The walk, its grid and the tile boxes it skips by are those of the resident g(r) (ljmd_rdf.h).
+#ifndef LJMD_STRESS_H
+#define LJMD_STRESS_H
+
+#include "ljmd_rdf.h"
+
+namespace ljmds {
+
+using ljmdr::kRdfBoxStride;
+using ljmdr::kRdfWaves;
+
+constexpr int kStressComponents = 6;            // xx, yy, zz, xy, xz, yz
+constexpr int kStressWords = 2 * kStressComponents * 3;    // int64 words of one snapshot: K[6][3], then S[6][3]
+constexpr int kStressMaxSnapshots = 262144;     // LJMD_STRESS_MAX_SNAPSHOTS
+constexpr int kStressMaxN = 1 << 23;            // kFixedMaxN: a lane adds fewer than 2^23 terms below 2^104
+constexpr int kStressKinThreads = 256;          // threads of a kinetic workgroup ...
+constexpr int kStressKinPerThread = 8;          // ... and slots per thread
+constexpr int kStressKinBlock = kStressKinThreads * kStressKinPerThread;
+constexpr int kStressFoldWaves = 13;            // one wave per row of the fold: K[6], S[6], the tile-pair counts
+
+// the walk of rdf_pairs_kernel (ljmd_rdf.h: RdfPairArgs), grid = (ceil(TB / kRdfWaves), ceil(U / chunk))
+struct StressPairArgs {
+    const double *pos;              // exchange buffer [G][3][P]
+    const double *bbox;             // [T][kRdfBoxStride] from launch_rdf_boxes
+    uint64_t *part;                 // [workgroups][6][3] sums of Q(term) of the workgroup; workgroup = y grid.x + x
+    unsigned long long *pcount;     // [workgroups][2] tile pairs evaluated / considered
+    unsigned *pflag;                // [workgroups] 1 = a pair of the workgroup was out of range
+    int P, G, rank, TB, T;
+    int U, chunk;
+    int skip;                       // 0: every tile pair is evaluated (positions not known to be compact)
+    double L, invL, rc2;
+    double rc2_skin;                // rc^2 (1 + 1e-10): a tile pair is skipped only when its bound exceeds this
+};
+
+struct StressKineticArgs {
+    const double *v;                // [3][P] of the own block
+    uint64_t *kpart;                // [blocks][6][3]
+    unsigned *kflag;                // [blocks]
+    int P, blocks;
+};
+
+struct StressFoldArgs {
+    const uint64_t *part;
+    const unsigned long long *pcount;
+    const unsigned *pflag;
+    const uint64_t *kpart;
+    const unsigned *kflag;
+    int workgroups, blocks;
+    uint64_t *row;                  // [kStressWords] of the series: this launch is its only writer
+    unsigned long long *count;      // [2] tile pairs of this accumulate
+    int32_t *range;                 // sticky
+};
+
+hipError_t launch_stress_pairs(const StressPairArgs &a, dim3 grid, hipStream_t s);
+hipError_t launch_stress_kinetic(const StressKineticArgs &a, hipStream_t s);
+hipError_t launch_stress_fold(const StressFoldArgs &a, hipStream_t s);
+
+// ---- host core (ljmd_stress.cpp): knows nothing of struct ljmd ----
+
+struct StressView {
+    int n = 0, P = 0, TB = 0, T = 0, G = 1, rank = 0;
+    double L = 0, invL = 0, rc2 = 0;
+    const double *pos = nullptr;    // exchange buffer
+    const double *v = nullptr;      // [3][P]
+    hipStream_t stream = nullptr;
+    bool compact = false;           // coordinate spread < 2.4 L
+};
+
+struct StressState {
+    int max_snapshots = 0;          // 0 = not configured
+    int workgroups = 0, blocks = 0; // rows of part / kpart
+    uint64_t *d_series = nullptr;   // [max_snapshots][kStressWords]
+    uint64_t *d_part = nullptr, *d_kpart = nullptr;
+    unsigned long long *d_pcount = nullptr, *d_count = nullptr;
+    unsigned *d_pflag = nullptr, *d_kflag = nullptr;
+    int32_t *d_range = nullptr;
+    double *d_bbox = nullptr;       // [T][kRdfBoxStride]
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the launches of the most recent accumulate
+    bool timed = false;
+    int64_t snapshots = 0;
+};
+
+// All return an LJMD_* code and leave a message in *err (and in the thread's last error).  `who` = the public name.
+int stress_configure(StressState *st, std::string *err, const char *who, const StressView &v, int32_t max_snapshots);
+int stress_accumulate(StressState *st, std::string *err, const char *who, const StressView &v);
+// words [snapshots][kStressWords], either pointer may be NULL; LJMD_ERR_RANGE while the sticky word is set
+int stress_fetch(StressState *st, std::string *err, const char *who, const StressView &v, int64_t *words, int64_t *n_snapshots);
+int stress_read(StressState *st, std::string *err, const char *who, const StressView &v, double *p, int64_t *n_snapshots);
+int stress_reset(StressState *st, std::string *err, const char *who, const StressView &v);
+int stress_profile_read(StressState *st, std::string *err, const char *who, const StressView &v, int64_t *visited,
+                        int64_t *total, double *kernel_ms);
+// frees everything after what may still use it; the state is "not configured" afterwards
+void stress_release(StressState *st, hipStream_t stream);
+// p[c] = (R(K[c]) + 12 R(S[c])) / ((L L) L) of one snapshot's words
+void stress_doubles(const int64_t *words, double L, double *out6);
+
+}  // namespace ljmds
+#endif

@@ -29,6 +29,8 @@ module ljmd_c_api
   public :: ljmd_batch_rdf_configure, ljmd_batch_rdf_accumulate, ljmd_batch_rdf_read, ljmd_batch_rdf_reset
   public :: ljmd_rdf_configure, ljmd_rdf_accumulate, ljmd_rdf_read, ljmd_rdf_reset, ljmd_rdf_profile_read
   public :: ljmd_tcf_configure, ljmd_tcf_accumulate, ljmd_tcf_read, ljmd_tcf_read_exact, ljmd_tcf_reset, ljmd_tcf_profile_read
+  public :: ljmd_stress_configure, ljmd_stress_accumulate, ljmd_stress_read, ljmd_stress_read_exact, ljmd_stress_reset
+  public :: ljmd_stress_profile_read, ljmd_stress_from_exact, ljmd_time_origin_average
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_check, ljmd_batch_error_text
@@ -40,6 +42,7 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_BATCH_MAX_N = 4096
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_LAG = 4096
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_ORIGINS = 512
+  integer(c_int32_t), parameter, public :: LJMD_STRESS_MAX_SNAPSHOTS = 262144
 
   interface
     function ljmd_compute_lj_potential_energy(n, box_length, rc, rx, ry, rz, ax, ay, az, &
@@ -404,6 +407,68 @@ module ljmd_c_api
       type(c_ptr), value :: handle
       real(c_double), intent(out) :: kernel_ms
       integer(c_int32_t), intent(out) :: origins_live
+      integer(c_int) :: status
+    end function
+
+    ! pressure tensor of the system resident on an engine handle (ljmd.h: ljmd_stress_*); p = c_loc of [6, n_snapshots]
+    ! doubles, words = c_loc of [3, 12, n_snapshots] 64-bit words in Fortran order; c_null_ptr skips an output
+    function ljmd_stress_configure(handle, max_snapshots) bind(C, name="ljmd_stress_configure") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_stress_accumulate(handle) bind(C, name="ljmd_stress_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_stress_read(handle, p, n_snapshots) bind(C, name="ljmd_stress_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, p
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_stress_read_exact(handle, words, n_snapshots) bind(C, name="ljmd_stress_read_exact") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_stress_reset(handle) bind(C, name="ljmd_stress_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_stress_profile_read(handle, tile_pairs_visited, tile_pairs_total, kernel_ms) &
+        bind(C, name="ljmd_stress_profile_read") result(status)
+      import :: c_int, c_int64_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: tile_pairs_visited, tile_pairs_total
+      real(c_double), intent(out) :: kernel_ms
+      integer(c_int) :: status
+    end function
+
+    ! host only: words = c_loc of the [3, 12] words of one snapshot, out6 = c_loc of 6 doubles
+    function ljmd_stress_from_exact(words, box_length, out6) bind(C, name="ljmd_stress_from_exact") result(status)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: words, out6
+      real(c_double), value :: box_length
+      integer(c_int) :: status
+    end function
+
+    ! time-origin averages of a host trajectory (ljmd.h): x, y, z = c_loc of [n, n_snap] doubles, out = c_loc of
+    ! min(max_lag, n_snap - 1) + 1 doubles; kind 0 = MSD, 1 = VACF
+    function ljmd_time_origin_average(kind, n_snap, n, x, y, z, max_lag, origin_stride, out) &
+        bind(C, name="ljmd_time_origin_average") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      integer(c_int32_t), value :: kind, n_snap, n, max_lag, origin_stride
+      type(c_ptr), value :: x, y, z, out
       integer(c_int) :: status
     end function
 

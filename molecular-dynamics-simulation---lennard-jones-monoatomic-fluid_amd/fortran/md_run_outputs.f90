@@ -8,6 +8,8 @@
 !   md_simulation_gpu (ljmd_rdf_*) and md_simulation_many_gpu (ljmd_batch_rdf_*).
 !   <dir>/msd_vacf_gpu.dat: MSD(tau) and VACF(tau) accumulated on the device (write_msd_vacf_file), shared by
 !   md_simulation_gpu (ljmd_tcf_*) and md_simulation_many_gpu (ljmd_batch_tcf_*).
+!   <dir>/pressure_tensor_gpu.dat, <dir>/stress_acf_gpu.dat: the pressure tensor md_simulation_gpu recorded on the device
+!   (ljmd_stress_*) and its Green-Kubo autocorrelations (write_pressure_tensor_file, write_stress_acf_file).
 !==============================================================================
 module md_run_outputs
   use, intrinsic :: iso_c_binding, only: c_int64_t
@@ -16,7 +18,7 @@ module md_run_outputs
   use md_stats
   implicit none
   private
-  public :: write_run_statistics, write_rdf_file, write_msd_vacf_file
+  public :: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, write_stress_acf_file
 
 contains
 
@@ -143,6 +145,50 @@ contains
     end do
     close(iu_tcf)
   end subroutine write_msd_vacf_file
+
+  ! pressure_tensor_gpu.dat: per sampling instant its time and p_xx, p_yy, p_zz, p_xy, p_xz, p_yz (ljmd_stress_read: no
+  ! tail correction); times(k) is the time of snapshot k
+  subroutine write_pressure_tensor_file(filename, n_snapshots, times, p)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: n_snapshots
+    real(kind=dp_kind), intent(in) :: times(n_snapshots), p(6, n_snapshots)
+    integer :: iu_p, ierr, k
+    open(newunit=iu_p, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_pressure_tensor_file(): cannot open pressure_tensor_gpu.dat.'
+    write(iu_p, '(a)') '# time   p_xx   p_yy   p_zz   p_xy   p_xz   p_yz'
+    do k = 1, n_snapshots
+      write(iu_p, '(es24.16e3,6(2x,es24.16e3))') times(k), p(:, k)
+    end do
+    close(iu_p)
+  end subroutine write_pressure_tensor_file
+
+  ! stress_acf_gpu.dat: per lag, lag, tau = lag * output_interval * dt, the shear and the normal-difference
+  ! autocorrelation (each a mean over three components) and the running Green-Kubo viscosity of each,
+  ! eta(tau) = V / T * trapezoid integral of the ACF up to tau, with the run's mean temperature
+  subroutine write_stress_acf_file(filename, max_lag, output_interval, dt, volume, temperature, shear, normal)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: max_lag
+    integer(kind=int_kind), intent(in) :: output_interval
+    real(kind=dp_kind), intent(in) :: dt, volume, temperature
+    real(kind=dp_kind), intent(in) :: shear(0:max_lag), normal(0:max_lag)
+    real(kind=dp_kind) :: h, eta_s, eta_n
+    integer :: iu_a, ierr, lag
+    open(newunit=iu_a, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_stress_acf_file(): cannot open stress_acf_gpu.dat.'
+    write(iu_a, '(a)') '# lag   tau   ACF_shear   ACF_normal   eta_shear   eta_normal'
+    h = dble(output_interval) * dt
+    eta_s = 0.d0
+    eta_n = 0.d0
+    do lag = 0, max_lag
+      if (lag > 0) then
+        eta_s = eta_s + 0.5d0 * (shear(lag) + shear(lag - 1)) * h
+        eta_n = eta_n + 0.5d0 * (normal(lag) + normal(lag - 1)) * h
+      end if
+      write(iu_a, '(i0,5(2x,es24.16e3))') lag, dble(lag) * h, shear(lag), normal(lag), &
+        (volume / temperature) * eta_s, (volume / temperature) * eta_n
+    end do
+    close(iu_a)
+  end subroutine write_stress_acf_file
 
   subroutine write_curve(filename, header, errmsg, lag_max, c, cn)
     character(len=*), intent(in) :: filename, header, errmsg

@@ -25,7 +25,14 @@
 ! every LJMD_TCF_ORIGIN_STRIDE-th of them (default 1) an origin -- and outputs/one_run/msd_vacf_gpu.dat gets, per lag
 ! with at least one origin, lag, lag * output_interval * dt, the number of origins, MSD and VACF, in the format of
 ! md_simulation_many_gpu; one-rank engines only: with LJMD_GPUS > 1 the program stops before an engine is created;
-! every other output file is the same with and without it).
+! every other output file is the same with and without it), LJMD_STRESS (default 0 = off; 1: the pressure tensor of
+! the resident system is recorded on the device -- ljmd_stress_* -- at the same sampling instants, with any LJMD_GPUS,
+! and outputs/one_run/pressure_tensor_gpu.dat gets the time and p_xx, p_yy, p_zz, p_xy, p_xz, p_yz of every instant,
+! without tail correction; with LJMD_STRESS_MAX_LAG > 0 outputs/one_run/stress_acf_gpu.dat also gets, per lag up to that
+! many sampling instants, lag, tau, the time-origin averaged shear and normal-difference autocorrelations --
+! ljmd_time_origin_average on the series as the velocity of one particle, each divided by its three components -- and the
+! running Green-Kubo viscosities V / <T> times their trapezoid integrals; every other output file is the same with and
+! without it).
 !==============================================================================
 program md_simulation_gpu
   use, intrinsic :: iso_c_binding
@@ -34,8 +41,9 @@ program md_simulation_gpu
   use read_input_files, only: read_simulation_parameters
   use ljmd_c_api
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
-  use md_stats,         only: run_statistics, stats_begin, stats_push
-  use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file
+  use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
+  use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
+                              write_stress_acf_file
   implicit none
 
   type(sim_params) :: params
@@ -63,6 +71,12 @@ program md_simulation_gpu
   real(c_double), allocatable, target :: tcf_msd(:), tcf_vacf(:)           ! [tcf_max_lag + 1]
   integer(c_int64_t), allocatable, target :: tcf_counts(:)
   integer(c_int64_t) :: tcf_snapshots
+  logical :: stress_on
+  integer :: stress_max_lag, stress_lags
+  real(c_double), allocatable, target :: stress_p(:, :), stress_times(:)   ! [6, snapshots], [snapshots]
+  real(c_double), allocatable, target :: stress_c(:, :), stress_shear(:), stress_normal(:)
+  integer(c_int64_t) :: stress_snapshots
+  real(kind=dp_kind) :: mean_temp, std_temp
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -100,6 +114,13 @@ program md_simulation_gpu
   call get_environment_variable('LJMD_TCF_ORIGIN_STRIDE', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) tcf_stride
   if (tcf_stride < 1) stop 'md_simulation: LJMD_TCF_ORIGIN_STRIDE must be >= 1.'
+  stress_on = .false.
+  call get_environment_variable('LJMD_STRESS', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) stress_on = trim(env) /= '0'
+  stress_max_lag = 0
+  call get_environment_variable('LJMD_STRESS_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) stress_max_lag
+  if (stress_max_lag < 0) stop 'md_simulation: LJMD_STRESS_MAX_LAG must be >= 0.'
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
@@ -127,6 +148,13 @@ program md_simulation_gpu
                                     'ljmd_rdf_configure')
   if (tcf_max_lag > 0) call ljmd_check(ljmd_tcf_configure(engine, int(tcf_max_lag, c_int32_t), int(tcf_stride, c_int32_t)), &
                                        engine, 'ljmd_tcf_configure')
+  if (stress_on) then
+    n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
+    if (n_snapshots_expected < 1) stop 'md_simulation: LJMD_STRESS needs at least one sampling instant.'
+    if (n_snapshots_expected > LJMD_STRESS_MAX_SNAPSHOTS) stop 'md_simulation: more sampling instants than LJMD_STRESS_MAX_SNAPSHOTS.'
+    call ljmd_check(ljmd_stress_configure(engine, int(n_snapshots_expected, c_int32_t)), engine, 'ljmd_stress_configure')
+    allocate(stress_times(n_snapshots_expected))
+  end if
   ! t = 0 forces and energies (:236-243)
   call ljmd_check(ljmd_compute_forces(engine, epot, d_epot, dd_epot), engine, 'ljmd_compute_forces')
   call ljmd_check(ljmd_kinetic_energy(engine, ekin), engine, 'ljmd_kinetic_energy')
@@ -171,6 +199,10 @@ program md_simulation_gpu
     ! g(r) of the same instant, on the device, ahead of the next segment in the engine's stream
     if (sample_now .and. rdf_bins > 0) call ljmd_check(ljmd_rdf_accumulate(engine), engine, 'ljmd_rdf_accumulate')
     if (sample_now .and. tcf_max_lag > 0) call ljmd_check(ljmd_tcf_accumulate(engine), engine, 'ljmd_tcf_accumulate')
+    if (sample_now .and. stress_on) then
+      call ljmd_check(ljmd_stress_accumulate(engine), engine, 'ljmd_stress_accumulate')
+      stress_times(num_samples + 1) = time
+    end if
     count = segment_length(step)
     if (async_io .and. count > 0) call enqueue_segment(count)
     if (sample_now) then
@@ -200,6 +232,11 @@ program md_simulation_gpu
     call ljmd_check(ljmd_tcf_read(engine, c_loc(tcf_msd), c_loc(tcf_vacf), c_loc(tcf_counts), tcf_snapshots), engine, &
                     'ljmd_tcf_read')
   end if
+  if (stress_on) then
+    allocate(stress_p(6, max(num_samples, 1)))
+    call ljmd_check(ljmd_stress_read(engine, c_loc(stress_p), stress_snapshots), engine, 'ljmd_stress_read')
+    if (stress_snapshots /= num_samples) stop 'md_simulation: the pressure tensor series and the samples disagree.'
+  end if
   call ljmd_destroy(engine)
 
   if (num_samples <= 0) stop 'md_simulation: no samples were taken (check warmup_steps/output_interval).'
@@ -208,6 +245,32 @@ program md_simulation_gpu
                                         rdf_hist, rdf_snapshots)
   if (tcf_max_lag > 0) call write_msd_vacf_file('outputs/one_run/msd_vacf_gpu.dat', tcf_max_lag, output_interval, params%dt, &
                                                 tcf_counts, tcf_msd, tcf_vacf)
+  if (stress_on) then
+    call write_pressure_tensor_file('outputs/one_run/pressure_tensor_gpu.dat', int(num_samples), stress_times, stress_p)
+    if (stress_max_lag > 0 .and. num_samples >= 2) then
+      ! the three shear components, then the three normal differences, as the velocity of one particle: [1, snapshots] each
+      allocate(stress_c(num_samples, 6))
+      stress_c(:, 1) = stress_p(4, 1:num_samples)
+      stress_c(:, 2) = stress_p(5, 1:num_samples)
+      stress_c(:, 3) = stress_p(6, 1:num_samples)
+      stress_c(:, 4) = 0.5d0 * (stress_p(1, 1:num_samples) - stress_p(2, 1:num_samples))
+      stress_c(:, 5) = 0.5d0 * (stress_p(2, 1:num_samples) - stress_p(3, 1:num_samples))
+      stress_c(:, 6) = 0.5d0 * (stress_p(3, 1:num_samples) - stress_p(1, 1:num_samples))
+      stress_lags = min(stress_max_lag, int(num_samples) - 1)
+      allocate(stress_shear(0:stress_lags), stress_normal(0:stress_lags))
+      call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(num_samples, c_int32_t), 1_c_int32_t, c_loc(stress_c(1, 1)), &
+                                               c_loc(stress_c(1, 2)), c_loc(stress_c(1, 3)), int(stress_lags, c_int32_t), &
+                                               1_c_int32_t, c_loc(stress_shear)), c_null_ptr, 'ljmd_time_origin_average')
+      call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(num_samples, c_int32_t), 1_c_int32_t, c_loc(stress_c(1, 4)), &
+                                               c_loc(stress_c(1, 5)), c_loc(stress_c(1, 6)), int(stress_lags, c_int32_t), &
+                                               1_c_int32_t, c_loc(stress_normal)), c_null_ptr, 'ljmd_time_origin_average')
+      stress_shear = stress_shear / 3.d0
+      stress_normal = stress_normal / 3.d0
+      call stats_mean_std(stats, Q_T, mean_temp, std_temp)
+      call write_stress_acf_file('outputs/one_run/stress_acf_gpu.dat', stress_lags, output_interval, params%dt, params%volume, &
+                                 mean_temp, stress_shear, stress_normal)
+    end if
+  end if
   write(*, '(a,i0,a,i0,a,f10.2,a,es11.4,a)') 'md_simulation_gpu: N=', params%n, ' steps=', total_steps, &
     '  ', dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' steps/s  ', &
     0.5d0 * npd * (npd - 1.d0) * dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' pair-interactions/s'

@@ -432,6 +432,59 @@ class Engine:
         self._ck(self._lib.ljmd_tcf_profile_read(self._h, C.byref(ms), C.byref(live)))
         return {"kernel_ms": ms.value, "origins_live": live.value}
 
+    # -- pressure tensor of the resident system (include/ljmd.h: ljmd_stress_*) ---------------
+    def stress_configure(self, max_snapshots: int) -> None:
+        """ljmd_stress_configure: room for max_snapshots snapshots of the pressure tensor on the device; 0 switches the
+        feature off.  The series starts empty."""
+        if isinstance(max_snapshots, bool) or not isinstance(max_snapshots, (int, np.integer)):
+            raise TypeError(f"stress_configure: max_snapshots must be an integer, got {max_snapshots!r}")
+        self._ck(self._lib.ljmd_stress_configure(self._h, int(max_snapshots)))
+        self._stress_max = int(max_snapshots)
+
+    def stress_accumulate(self) -> None:
+        """appends the pressure tensor of the state resident now to the series (stream-ordered: no host wait)"""
+        self._ck(self._lib.ljmd_stress_accumulate(self._h))
+
+    def _stress_count(self) -> int:
+        """snapshots in the series (ljmd_stress_read_exact without a buffer); raises as the reads do"""
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_stress_read_exact(self._h, None, C.byref(snaps)))
+        return snaps.value
+
+    def stress_read(self) -> np.ndarray:
+        """-> p[n_snapshots, 6]: xx, yy, zz, xy, xz, yz of (sum v v + 12 sum f d) / V per snapshot, without tail
+        correction; nothing is cleared.  Refused on a rank engine (n_ranks > 1), which holds a partial sum."""
+        p = np.empty((max(self._stress_count(), 1), 6), dtype=np.float64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_stress_read(self._h, p.ctypes.data_as(c_double_p), C.byref(snaps)))
+        return p[:snaps.value].copy()
+
+    def stress_read_exact(self, raw: bool = False):
+        """-> sums[n_snapshots, 12]: the exact integer sums of Q(term) = RNE(term 2^64), K[6] then S[6], as Python ints
+        in an object array -- or, raw=True, the library's int64 words [n_snapshots, 12, 3] (three little-endian limbs
+        of a signed 192-bit integer).  A rank engine returns its partial."""
+        words = np.empty((max(self._stress_count(), 1), 12, 3), dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_stress_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        words = words[:snaps.value].copy()
+        if raw:
+            return words
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:2], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums
+
+    def stress_reset(self) -> None:
+        self._ck(self._lib.ljmd_stress_reset(self._h))
+
+    def stress_profile(self) -> dict:
+        """ljmd_stress_profile_read for the most recent stress_accumulate -> {'tile_pairs_visited',
+        'tile_pairs_total', 'kernel_ms'}"""
+        vis, tot, ms = C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self._lib.ljmd_stress_profile_read(self._h, C.byref(vis), C.byref(tot), C.byref(ms)))
+        return {"tile_pairs_visited": vis.value, "tile_pairs_total": tot.value, "kernel_ms": ms.value}
+
     # -- measurement -----------------------------------------------------------
     def profile_enable(self, on: bool = True) -> None:
         self._ck(self._lib.ljmd_profile_enable(self._h, 1 if on else 0))
