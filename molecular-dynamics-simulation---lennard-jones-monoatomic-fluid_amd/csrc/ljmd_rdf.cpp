@@ -39,7 +39,7 @@ int not_configured(std::string *err, const char *who)
 
 }  // namespace
 
-RdfWalk rdf_plan_walk(int TB, int T, int G)
+RdfWalk rdf_plan_walk(int TB, int T, int G, std::optional<int> walk_chunk)
 {
     RdfWalk w;
     w.weight = G == 1 ? 2 : 1;
@@ -47,6 +47,7 @@ RdfWalk rdf_plan_walk(int TB, int T, int G)
     w.row_blocks = (TB + kRdfWaves - 1) / kRdfWaves;
     const int want = std::max(1, std::min(w.U, (kRdfTargetWorkgroups + w.row_blocks - 1) / w.row_blocks));
     w.chunk = std::min((w.U + want - 1) / want, kRdfMaxChunk);
+    if (walk_chunk) w.chunk = std::max(1, std::min(*walk_chunk, std::min(w.U, kRdfMaxChunk)));
     w.slices = (w.U + w.chunk - 1) / w.chunk;
     return w;
 }
@@ -103,7 +104,7 @@ int rdf_configure(RdfState *st, std::string *err, const char *who, const RdfView
 int rdf_accumulate(RdfState *st, std::string *err, const char *who, const RdfView &v)
 {
     if (st->nbins == 0) return not_configured(err, who);
-    const RdfWalk w = rdf_plan_walk(v.TB, v.T, v.G);
+    const RdfWalk w = rdf_plan_walk(v.TB, v.T, v.G, v.walk_chunk);
     // a 32-bit LDS bin cannot overflow: rdf_plan_walk caps the slice; checked, not assumed
     if (rdf_lds_bound(w.chunk, w.weight) > 0xffffffffull)
         return rfail(err, LJMD_ERR_RANGE, "%s: a slice of %d column tiles could overflow a 32-bit histogram bin", who, w.chunk);
@@ -191,6 +192,7 @@ RdfView view_of(const ljmd_t *h)
     v.pos = h->d_pos;
     v.stream = h->stream;
     v.compact = h->positions_compact;
+    v.walk_chunk = h->knobs.walk_chunk;
     return v;
 }
 

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <optional>
 #include <string>
 
 namespace ljmdr {
@@ -76,6 +77,24 @@ __host__ __device__ inline double rdf_tile_gap2(const double *bi, const double *
     return gx * gx + gy * gy + gz * gz;
 }
 
+// The two decisions of the walk, the same for the box test of a lane and for the evaluation after the ballot, in
+// rdf_pairs_kernel and stress_pairs_kernel (tests/rdf_host enumerates them on the host).
+// column tile of row tile I at step u (I < T; u <= T / 2 unordered, u < T ordered: one wrap at most)
+__host__ __device__ inline int rdf_walk_column(int I, int u, int T, bool unordered)
+{
+    int J = unordered ? I + u : u;
+    if (J >= T) J -= T;
+    return J;
+}
+
+// whether row tile I takes step u of a slice that ends at u1: the tie step u = T / 2 of an even T of the unordered walk
+// belongs to the rows I < T / 2 only
+__host__ __device__ inline bool rdf_walk_takes(int I, int u, int u1, int T, bool unordered)
+{
+    const int half = (unordered && (T & 1) == 0) ? T / 2 : -1;
+    return u < u1 && !(u == half && I >= half);
+}
+
 hipError_t launch_rdf_boxes(const RdfBoxArgs &a, hipStream_t s);
 hipError_t launch_rdf_pairs(const RdfPairArgs &a, dim3 grid, hipStream_t s);
 
@@ -88,6 +107,7 @@ struct RdfView {
     const double *pos = nullptr;    // exchange buffer
     hipStream_t stream = nullptr;
     bool compact = false;           // coordinate spread < 2.4 L
+    std::optional<int> walk_chunk;  // LJMD_WALK_CHUNK as the handle read it (Knobs::walk_chunk)
 };
 
 struct RdfState {
@@ -105,7 +125,8 @@ struct RdfState {
 struct RdfWalk {
     int U = 0, chunk = 0, slices = 0, row_blocks = 0, weight = 0;
 };
-RdfWalk rdf_plan_walk(int TB, int T, int G);
+// walk_chunk unset: steps per slice by kRdfTargetWorkgroups; set: that many, clamped to [1, min(U, kRdfMaxChunk)] (tests)
+RdfWalk rdf_plan_walk(int TB, int T, int G, std::optional<int> walk_chunk = std::nullopt);
 
 // All return an LJMD_* code and leave a message in *err (and in the thread's last error).  `who` = the public name.
 int rdf_configure(RdfState *st, std::string *err, const char *who, const RdfView &v, int32_t nbins, double rmax);

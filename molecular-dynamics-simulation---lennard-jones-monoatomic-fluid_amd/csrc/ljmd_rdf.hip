@@ -114,15 +114,13 @@ __global__ __launch_bounds__(kRdfWaves * kTile) void rdf_pairs_kernel(RdfPairArg
         const double *bi = a.bbox + (size_t)I * kRdfBoxStride;
         const bool unordered = a.G == 1;
         const unsigned weight = unordered ? 2u : 1u;
-        const int half = (unordered && (a.T & 1) == 0) ? a.T / 2 : -1;      // the tie step of an even T
         const int u0 = blockIdx.y * a.chunk, u1 = min(u0 + a.chunk, a.U);
         unsigned visited = 0, considered = 0;
         for (int ub = u0; ub < u1; ub += 64) {
             // lane = step ub + lane: its column tile, whether the walk takes it from this row, whether the boxes keep it
             const int u = ub + lane;
-            int J = unordered ? I + u : u;
-            if (J >= a.T) J -= a.T;                             // (I < T, u <= T / 2: one wrap at most)
-            const bool valid = u < u1 && !(u == half && I >= half);
+            const int J = rdf_walk_column(I, u, a.T, unordered);
+            const bool valid = rdf_walk_takes(I, u, u1, a.T, unordered);
             bool keep = valid;
             if (valid && a.skip && J != I) keep = !(rdf_tile_gap2(bi, a.bbox + (size_t)J * kRdfBoxStride, a.L) > a.rmax2_skin);
             uint64_t m = __ballot(keep);
@@ -131,9 +129,7 @@ __global__ __launch_bounds__(kRdfWaves * kTile) void rdf_pairs_kernel(RdfPairArg
             while (m) {
                 const int b = __builtin_ctzll(m);
                 m &= m - 1;
-                int Jb = unordered ? I + ub + b : ub + b;
-                if (Jb >= a.T) Jb -= a.T;
-                Jb = __builtin_amdgcn_readfirstlane(Jb);
+                const int Jb = __builtin_amdgcn_readfirstlane(rdf_walk_column(I, ub + b, a.T, unordered));
                 const int gj = unordered ? 0 : Jb / a.TB;
                 const double *bx = a.pos + (size_t)gj * 3 * a.P + (size_t)(Jb - gj * a.TB) * kTile;
                 if (Jb != I)

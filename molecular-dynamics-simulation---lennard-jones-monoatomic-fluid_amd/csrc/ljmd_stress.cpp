@@ -73,7 +73,7 @@ int stress_configure(StressState *st, std::string *err, const char *who, const S
         return sfail(err, LJMD_ERR_INVALID_ARG, "%s: n = %d outside 1..%d", who, v.n, kStressMaxN);
     stress_release(st, v.stream);
     if (max_snapshots == 0) return LJMD_OK;
-    const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(v.TB, v.T, v.G);
+    const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(v.TB, v.T, v.G, v.walk_chunk);
     const int workgroups = w.row_blocks * w.slices;
     const int blocks = (v.P + kStressKinBlock - 1) / kStressKinBlock;
     const size_t row = (size_t)kStressComponents * 3 * sizeof(uint64_t);
@@ -121,7 +121,7 @@ int stress_accumulate(StressState *st, std::string *err, const char *who, const 
     if (st->snapshots >= st->max_snapshots)
         return sfail(err, LJMD_ERR_STATE, "%s: the series is full (%d snapshots; read it, then ljmd_stress_reset)", who,
                      st->max_snapshots);
-    const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(v.TB, v.T, v.G);
+    const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(v.TB, v.T, v.G, v.walk_chunk);
     const int blocks = (v.P + kStressKinBlock - 1) / kStressKinBlock;
     if (w.row_blocks * w.slices != st->workgroups || blocks != st->blocks || !v.pos || !v.v)
         return sfail(err, LJMD_ERR_STATE, "%s: the engine is not the one the pressure tensor was configured for", who);
@@ -263,6 +263,7 @@ StressView view_of(const ljmd_t *h)
     v.v = h->d_v;
     v.stream = h->stream;
     v.compact = h->positions_compact;
+    v.walk_chunk = h->knobs.walk_chunk;
     return v;
 }
 

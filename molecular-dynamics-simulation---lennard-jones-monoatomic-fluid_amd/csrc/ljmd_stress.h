@@ -69,6 +69,7 @@ struct StressView {
     const double *v = nullptr;      // [3][P]
     hipStream_t stream = nullptr;
     bool compact = false;           // coordinate spread < 2.4 L
+    std::optional<int> walk_chunk;  // LJMD_WALK_CHUNK as the handle read it (Knobs::walk_chunk)
 };
 
 struct StressState {

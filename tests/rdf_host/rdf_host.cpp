@@ -3,16 +3,21 @@
 // its own definitions of the two launchers, which check what they are given and add known numbers where the kernels
 // would add counts.  The program checks itself -- every guard with its return code and message, the sequences around
 // configure / accumulate / read / reset, the bound that keeps a 32-bit LDS bin from overflowing for n up to 2^23, and
-// the tile-pair bound of ljmd_rdf.h against brute force -- prints one line per check that fails and "rdf_host: ok" when
+// the tile-pair bound of ljmd_rdf.h against brute force, and the walk itself: the loop structure of rdf_pairs_kernel /
+// stress_pairs_kernel (slices, blocks of 64 steps, lanes, rdf_walk_column and rdf_walk_takes) replayed for a grid of
+// shapes and LJMD_WALK_CHUNK values, every tile pair counted -- prints one line per check that fails and "rdf_host: ok" when
 // none did.  tests/test_rdf_host.py runs it under ASan and UBSan.  (The fake hipMalloc cannot fail, so the
 // LJMD_ERR_ALLOC branch of configure is not reached here.)
 #include "ljmd.h"
+#include "ljmd_common.h"
 #include "ljmd_rdf.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <random>
 #include <string>
 #include <vector>
@@ -181,7 +186,7 @@ void overflow_bound()
         for (int G : Gs) {
             if (n % G) continue;
             const int S = n / G, P = (S + 255) / 256 * 256, TB = P / 64, T = G * TB;
-            const RdfWalk w = rdf_plan_walk(TB, T, G);
+            const RdfWalk w = rdf_plan_walk(TB, T, G, std::nullopt);
             const bool ok = w.weight == (G == 1 ? 2 : 1) && w.U == (G == 1 ? T / 2 + 1 : T) && w.chunk >= 1 &&
                             w.chunk <= kRdfMaxChunk && (long long)w.slices * w.chunk >= w.U &&
                             (long long)(w.slices - 1) * w.chunk < w.U && w.row_blocks * kRdfWaves >= TB &&
@@ -191,6 +196,140 @@ void overflow_bound()
         }
     check(rdf_lds_bound(kRdfMaxChunk, 2) == (1ull << 31), "the largest slice adds 2^31 at most");
     check(rdf_lds_bound(2 * kRdfMaxChunk, 2) > 0xffffffffull, "twice the largest slice would not fit");
+}
+
+// ---- the walk, enumerated ----
+// What the replay saw, so that none of the paths it is there for is vacuous.
+struct WalkSeen {
+    bool second_block = false;      // a slice longer than 64 steps
+    bool partial_block = false;     // a last block with fewer than 64 steps, after a full one
+    bool full_last_block = false;   // u1 == ub + 64 exactly
+    bool tie_later_block = false;   // the tie step of an even T in a block other than a slice's first, taken and dropped
+    bool tie_dropped_later = false;
+    bool wrap_later_block = false;  // J wrapped at T in a block other than the first
+    bool own_tile_later = false;    // the own tile of the ordered walk in a block other than the first
+    bool odd_T = false;
+} g_seen;
+
+// One launch of the pair kernels for `rank`, as they walk: grid (row_blocks, slices), kRdfWaves waves per workgroup, each
+// taking its slice 64 steps at a time, one lane per step; every lane's box test kept (skip off), then the set bits
+// walked.  count[I T + J] += 1 per evaluated tile pair; -> the `considered` popcounts.
+long long replay_walk(int TB, int T, int G, int rank, const RdfWalk &w, std::vector<unsigned char> &count)
+{
+    const bool unordered = G == 1;
+    long long considered = 0;
+    for (int by = 0; by < w.slices; ++by)
+        for (int bx = 0; bx < w.row_blocks; ++bx)
+            for (int wave = 0; wave < kRdfWaves; ++wave) {
+                const int Il = bx * kRdfWaves + wave;
+                if (Il >= TB) continue;
+                const int I = rank * TB + Il;
+                const int u0 = by * w.chunk, u1 = std::min(u0 + w.chunk, w.U);
+                check(u0 < u1, "walk: no slice is empty");
+                for (int ub = u0; ub < u1; ub += 64) {
+                    uint64_t m = 0;
+                    int Jlane[64];
+                    for (int lane = 0; lane < 64; ++lane) {
+                        const int u = ub + lane;
+                        Jlane[lane] = rdf_walk_column(I, u, T, unordered);
+                        if (!rdf_walk_takes(I, u, u1, T, unordered)) {
+                            if (u < u1 && ub > u0) g_seen.tie_dropped_later = true;
+                            continue;
+                        }
+                        check(Jlane[lane] >= 0 && Jlane[lane] < T && u < w.U, "walk: a valid lane names a tile of the system");
+                        m |= 1ull << lane;
+                    }
+                    considered += __builtin_popcountll(m);
+                    if (ub > u0) g_seen.second_block = true;
+                    if (ub > u0 && u1 - ub < 64) g_seen.partial_block = true;
+                    if (u1 - ub == 64) g_seen.full_last_block = true;
+                    while (m) {
+                        const int b = __builtin_ctzll(m);
+                        m &= m - 1;
+                        const int Jb = rdf_walk_column(I, ub + b, T, unordered);
+                        check(Jb == Jlane[b], "walk: the evaluated tile is the tested one");
+                        if (Jb < 0 || Jb >= T) continue;
+                        unsigned char &c = count[(size_t)I * T + Jb];
+                        if (c < 255) ++c;
+                        if (ub > u0) {
+                            if (unordered && (T & 1) == 0 && ub + b == T / 2) g_seen.tie_later_block = true;
+                            if (unordered && I + ub + b >= T) g_seen.wrap_later_block = true;
+                            if (!unordered && Jb == I) g_seen.own_tile_later = true;
+                        }
+                    }
+                }
+            }
+    return considered;
+}
+
+void walk_enumeration()
+{
+    const int TBs[] = {1, 4, 5, 33, 36, 64, 65, 132, 260};
+    const int Gs[] = {1, 2, 3, 4, 8};
+    for (int TB : TBs)
+        for (int G : Gs) {
+            const int T = G * TB, U = G == 1 ? T / 2 + 1 : T;
+            if (T & 1) g_seen.odd_T = true;
+            const int chunks[] = {1, 2, 63, 64, 65, U - 1, U, U + 7};
+            for (int chunk : chunks) {
+                const RdfWalk w = rdf_plan_walk(TB, T, G, chunk);
+                const bool plan_ok = w.U == U && w.chunk == std::max(1, std::min(chunk, std::min(U, kRdfMaxChunk))) &&
+                                     w.slices == (U + w.chunk - 1) / w.chunk && w.row_blocks == (TB + kRdfWaves - 1) / kRdfWaves &&
+                                     w.weight == (G == 1 ? 2 : 1);
+                if (!plan_ok) std::printf("TB %d G %d asked %d: U %d chunk %d slices %d\n", TB, G, chunk, w.U, w.chunk, w.slices);
+                check(plan_ok, "walk: the plan under an override");
+                // rows I of the array are written by the rank that owns them and by no other
+                std::vector<unsigned char> all((size_t)T * T, 0);
+                bool ok = true;
+                long long considered = 0;
+                for (int rank = 0; rank < G; ++rank) {
+                    const long long con = replay_walk(TB, T, G, rank, w, all);
+                    considered += con;
+                    if (G > 1) ok = ok && con == (long long)TB * T;      // own rows x every column
+                }
+                if (G == 1) {
+                    // every unordered tile pair from one side only, every diagonal tile once
+                    for (int I = 0; I < T; ++I) {
+                        ok = ok && all[(size_t)I * T + I] == 1;
+                        for (int J = I + 1; J < T; ++J) ok = ok && all[(size_t)I * T + J] + all[(size_t)J * T + I] == 1;
+                    }
+                    ok = ok && considered == ((T & 1) ? (long long)T * (T / 2 + 1) : (long long)T * (T / 2) + T / 2);
+                } else {
+                    // every rank every ordered tile pair of its rows once; together all T x T
+                    ok = ok && std::count(all.begin(), all.end(), (unsigned char)1) == (long long)T * T;
+                    ok = ok && considered == (long long)T * T;
+                }
+                if (!ok) std::printf("TB %d G %d chunk %d (asked %d): considered %lld\n", TB, G, w.chunk, chunk, considered);
+                check(ok, "walk: every tile pair exactly once, `considered` the closed form");
+            }
+        }
+    check(g_seen.second_block && g_seen.partial_block && g_seen.full_last_block && g_seen.tie_later_block &&
+              g_seen.tie_dropped_later && g_seen.wrap_later_block && g_seen.own_tile_later && g_seen.odd_T,
+          "walk: the grid reached every path it is there for");
+    // unset and out-of-range requests
+    const RdfWalk plain = rdf_plan_walk(132, 132, 1, std::nullopt);
+    check(plain.chunk == 1 && plain.slices == 67, "walk: unset, T = 132 is one step per slice");
+    check(rdf_plan_walk(132, 132, 1, 0).chunk == 1 && rdf_plan_walk(132, 132, 1, -5).chunk == 1 &&
+              rdf_plan_walk(132, 132, 1, 1000).chunk == 67 && rdf_plan_walk(132, 132, 1, 1000).slices == 1,
+          "walk: a request is clamped to [1, U]");
+    // from the environment to the launch: read_knobs -> (the handle's Knobs) -> RdfView -> the grid of rdf_accumulate
+    setenv("LJMD_WALK_CHUNK", "65", 1);
+    const std::optional<int> knob = ljmdh::read_knobs().walk_chunk;
+    unsetenv("LJMD_WALK_CHUNK");
+    check(knob && *knob == 65 && !ljmdh::read_knobs().walk_chunk, "walk: read_knobs reads LJMD_WALK_CHUNK, unset is unset");
+    std::vector<double> pos;
+    RdfView v = view_for(8200, 1, 0, pos);
+    v.walk_chunk = knob;
+    RdfState st;
+    std::string err;
+    check(rdf_configure(&st, &err, "k", v, 16, 2.0) == LJMD_OK && rdf_accumulate(&st, &err, "k", v) == LJMD_OK &&
+              g_last.chunk == 65 && g_last.U == 67 && g_grid.y == 2 && g_grid.x == 33, "walk: accumulate launches the overridden plan");
+    v.walk_chunk = std::nullopt;
+    check(rdf_accumulate(&st, &err, "k", v) == LJMD_OK && g_last.chunk == 1 && g_grid.y == 67, "walk: unset, the plan of before");
+    rdf_release(&st, nullptr);
+    const int bigT = 4 * kRdfMaxChunk;
+    check(rdf_plan_walk(bigT, bigT, 1, 1 << 30).chunk == kRdfMaxChunk, "walk: a request is clamped to kRdfMaxChunk");
+    check(rdf_lds_bound(rdf_plan_walk(bigT, bigT, 1, 1 << 30).chunk, 2) <= 0xffffffffull, "walk: a clamped request keeps the LDS bound");
 }
 
 // ---- the tile-pair bound against brute force ----
@@ -311,6 +450,7 @@ int main()
     setenv("FAKEHIP_DEVICES", "1", 1);
     guards_and_sequences();
     overflow_bound();
+    walk_enumeration();
     gap_bound_property();
     if (g_failures == 0) std::printf("rdf_host: ok\n");
     return g_failures == 0 ? 0 : 1;

@@ -4,17 +4,20 @@
 // are given and carry out on the host what the kernels mean: the tile boxes, the walk with its skipping, tie rule and
 // doubling, the per-workgroup partials, the kinetic partials and the fold.  The program checks itself -- every guard with
 // its return code and message, the sequences around configure / accumulate / read / reset, a full series, NULL outputs,
-// release, and the returned words against a brute-force sum over the ordered pairs in particle order -- prints one line
+// release, the returned words against a brute-force sum over the ordered pairs in particle order, and the plan under a
+// grid of LJMD_WALK_CHUNK values (slices, workgroups and partial rows) -- prints one line
 // per check that fails and "stress_host: ok" when none did.  tests/test_stress_host.py runs it under ASan and UBSan.
 // (The fake hipMalloc cannot fail, so the LJMD_ERR_ALLOC branch of configure is not reached here.)
 #include "ljmd.h"
 #include "ljmd_internal.h"
 #include "ljmd_stress.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <optional>
 #include <random>
 #include <string>
 #include <vector>
@@ -29,6 +32,8 @@ int g_failures = 0;
 int g_boxes = 0, g_pairs = 0, g_kinetic = 0, g_fold = 0;
 int g_fail_pairs = 0;                      // 1: the next pair launch returns hipErrorLaunchFailure
 StressPairArgs g_last{};
+dim3 g_grid;
+bool g_plan_only = false;                  // the pair launch checks its grid and writes zero rows: no pair is evaluated
 
 void check(bool ok, const char *what)
 {
@@ -120,6 +125,16 @@ hipError_t launch_stress_pairs(const StressPairArgs &a, dim3 grid, hipStream_t)
           "pair launch: the slices cover the walk, none is empty");
     check((long long)grid.x * kRdfWaves >= a.TB && (long long)(grid.x - 1) * kRdfWaves < a.TB, "pair launch: row blocks");
     check(a.rc2_skin > a.rc2 && a.rc2_skin < a.rc2 * (1.0 + 1e-9), "pair launch: rc^2 < skip bound");
+    g_grid = grid;
+    if (g_plan_only) {                                       // every workgroup's rows exist (ASan) and are written
+        for (size_t wg = 0; wg < (size_t)grid.x * grid.y; ++wg) {
+            std::memset(a.part + wg * 18, 0, 18 * sizeof(uint64_t));
+            a.pcount[2 * wg] = 1;
+            a.pcount[2 * wg + 1] = 2;
+            a.pflag[wg] = 0u;
+        }
+        return hipSuccess;
+    }
     const bool unordered = a.G == 1;
     const int half = (unordered && (a.T & 1) == 0) ? a.T / 2 : -1;
     for (unsigned by = 0; by < grid.y; ++by)
@@ -412,6 +427,53 @@ void walks_against_brute_force()
     }
 }
 
+// LJMD_WALK_CHUNK: configure sizes the partial rows from the plan accumulate launches from, for every override of the grid
+// tests/rdf_host enumerates; the launcher's own checks (the slices cover the walk, none is empty) run on each
+void plans_under_an_override()
+{
+    const int TBs[] = {1, 4, 5, 33, 36, 64, 65, 132, 260};
+    const int Gs[] = {1, 2, 3, 4, 8};
+    g_plan_only = true;
+    for (int TB : TBs)
+        for (int G : Gs) {
+            const int T = G * TB, U = G == 1 ? T / 2 + 1 : T, P = TB * 64;
+            const std::vector<double> pos((size_t)G * 3 * P, NAN), vel((size_t)3 * P, 0.0);
+            const int asked[] = {1, 2, 63, 64, 65, U - 1, U, U + 7};
+            for (int chunk : asked) {
+                StressView v;
+                v.n = T * 64; v.P = P; v.TB = TB; v.T = T; v.G = G; v.rank = G - 1;
+                v.L = 10.0; v.invL = 0.1; v.rc2 = 6.25;
+                v.pos = pos.data();
+                v.v = vel.data();
+                v.compact = true;
+                v.walk_chunk = chunk;
+                const int want_chunk = std::max(1, std::min(chunk, U));
+                const int slices = (U + want_chunk - 1) / want_chunk, row_blocks = (TB + kRdfWaves - 1) / kRdfWaves;
+                StressState st;
+                std::string err;
+                int64_t vis = -1, tot = -1;
+                check(stress_configure(&st, &err, "o", v, 1) == LJMD_OK && st.workgroups == row_blocks * slices,
+                      "override: configure sizes the partial rows from the overridden plan");
+                check(stress_accumulate(&st, &err, "o", v) == LJMD_OK && g_last.chunk == want_chunk && g_last.U == U &&
+                          (int)g_grid.x == row_blocks && (int)g_grid.y == slices && (int)(g_grid.x * g_grid.y) == st.workgroups,
+                      "override: accumulate launches the plan configure sized for");
+                check(stress_profile_read(&st, &err, "o", v, &vis, &tot, nullptr) == LJMD_OK && vis == st.workgroups &&
+                          tot == 2 * (int64_t)st.workgroups, "override: the fold reads one row per workgroup");
+                // a view with another value of the knob is another plan: refused, unless the grid happens to be the same
+                StressView other = v;
+                other.walk_chunk = std::nullopt;
+                const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(TB, T, G, std::nullopt);
+                StressState st2;
+                check(stress_configure(&st2, &err, "o", other, 2) == LJMD_OK, "override: configure without the knob");
+                check((stress_accumulate(&st2, &err, "o", v) == LJMD_OK) == (w.row_blocks * w.slices == st.workgroups),
+                      "override: a view whose plan needs other partial rows is refused");
+                stress_release(&st, nullptr);
+                stress_release(&st2, nullptr);
+            }
+        }
+    g_plan_only = false;
+}
+
 // rank engines: own rows x all columns; the partials add up to the one-rank words as integers
 void rank_partials()
 {
@@ -480,6 +542,7 @@ int main()
     guards_and_sequences();
     walks_against_brute_force();
     rank_partials();
+    plans_under_an_override();
     range_flag();
     if (g_failures == 0) std::printf("stress_host: ok\n");
     return g_failures == 0 ? 0 : 1;
