@@ -153,6 +153,11 @@ PROTOTYPES = {
     "ljmd_batch_tcf_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int64_p, c_int64_p]),
     "ljmd_batch_tcf_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]),
     "ljmd_batch_tcf_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_stress_configure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "ljmd_batch_stress_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_stress_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ljmd_batch_stress_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
+    "ljmd_batch_stress_reset": (C.c_int, [C.c_void_p]),
     "ljmd_batch_prepare": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
     "ljmd_tcf_from_exact": (C.c_int, [c_int64_p, C.c_int32, C.c_int64, c_double_p]),
 }
@@ -163,6 +168,7 @@ BATCH_TCF_MAX_ORIGINS = 512
 TCF_MAX_LAG = 4096
 TCF_MAX_ORIGINS = 512
 STRESS_MAX_SNAPSHOTS = 262144
+BATCH_STRESS_MAX_SNAPSHOTS = 262144
 
 _lib = None
 

@@ -3,7 +3,8 @@
 // with one workgroup per replica.  Handle lifecycle, guards, device state, launch planning per kernel class, the step
 // loop and the combination of the per-replica step records, in the fp64 mode and in the reproducible mode (exact integer
 // records, a sticky range flag per replica: ljmd_batch_fixed.hip).  The accumulators the step loop serves are
-// ljmd_batch_rdf.cpp (g(r)) and ljmd_batch_tcf.cpp (MSD / VACF); ljmd_batch_host.h is what the three files share.
+// ljmd_batch_rdf.cpp (g(r)), ljmd_batch_tcf.cpp (MSD / VACF) and, through the handle alone, ljmd_stress_batch.cpp (the
+// pressure tensor); ljmd_batch_host.h is what these files share.
 #include "ljmd_batch_host.h"
 
 using namespace ljmdb;
@@ -14,6 +15,7 @@ int ljmdb::enter(ljmd_batch *h, const char *who, unsigned need)
     auto state = [&](const char *what) { return fail(h, LJMD_ERR_STATE, "%s: %s", who, what); };
     if ((need & kNeedRdf) && h->rdf.nbins == 0) return state("call ljmd_batch_rdf_configure first");
     if ((need & kNeedTcf) && h->tcf.max_lag == 0) return state("call ljmd_batch_tcf_configure first");
+    if ((need & kNeedStress) && h->stress.max_snapshots == 0) return state("call ljmd_batch_stress_configure first");
     if ((need & kNeedState) && !h->have_state) return state("no state has been set");
     if ((need & kNeedAccel) && !h->have_accel)
         return state("no valid accelerations; call ljmd_batch_compute_forces or ljmd_batch_set_accel first");
@@ -378,6 +380,7 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
     if (h->d_range) (void)hipFree(h->d_range);
     rdf_release(h);
     tcf_release(h);
+    if (h->stress.release) h->stress.release(h);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -525,6 +528,8 @@ int ljmd_batch_steps(ljmd_batch_t *h, int32_t nsteps, int32_t sample_every, doub
         if (x.every > 0 && nsteps % x.every != 0)
             return fail(h, LJMD_ERR_INVALID_ARG, "%s: nsteps %d is not a multiple of the %s interval %d "
                                                   "(ljmd_batch_%s_configure: every)", who, nsteps, x.name, x.every, x.tag);
+    for (const BatchAccumulator &x : acc)
+        if (x.every > 0 && x.room) LJMD_TRY(x.room(h, nsteps / x.every, who));
     if (nsteps == 0) return LJMD_OK;
     LJMD_HIP(h, hipSetDevice(h->device));
     const size_t samples = sampling ? (size_t)(nsteps / sample_every) : 0;

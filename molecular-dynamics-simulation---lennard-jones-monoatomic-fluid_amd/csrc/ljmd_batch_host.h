@@ -1,6 +1,7 @@
 // ljmd_batch_host.h -- what the host files of the batch engine share (ljmd_batch.cpp: lifecycle, planning, step loop;
-// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF): the handle, the entry guard, the poison and allocation
-// helpers, and the form in which the step loop sees an accumulator.  Host code only; the kernels' side is ljmd_batch.h.
+// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF; ljmd_stress_batch.cpp: pressure tensor): the handle, the
+// entry guard, the poison and allocation helpers, and the form in which the step loop sees an accumulator.  Host code
+// only; the kernels' side is ljmd_batch.h.
 #ifndef LJMD_BATCH_HOST_H
 #define LJMD_BATCH_HOST_H
 
@@ -15,6 +16,8 @@
 #include <cstring>
 #include <new>
 #include <vector>
+
+struct ljmd_batch;
 
 namespace ljmdb __attribute__((visibility("hidden"))) {   // host-only: no symbol of libljmd.so
 
@@ -54,6 +57,31 @@ struct BatchTcf {
     double *d_ring = nullptr;         // [slots][6][offsets[B]]: ru and v of the stored origins
 };
 
+// An accumulator as the step loop sees it (run_groups, ljmd_batch_steps): a launch ends at the steps every, 2 every, ...
+// of the call, the group's enqueue follows it on the same stream, and ran() does the host's share after the whole call.
+struct BatchAccumulator {
+    int every = 0;                    // steps between two snapshots of ljmd_batch_steps; 0: off, or not taken by it
+    const char *name = nullptr;       // "g(r)": "... is not a multiple of the g(r) interval"
+    const char *tag = nullptr;        // "rdf": ljmd_batch_rdf_configure
+    // the launches of group g on stream s for snapshot k (0-based) of this call; counts them; a failure poisons
+    int (*enqueue)(ljmd_batch *h, const BatchGroup &g, hipStream_t s, int k, int32_t *count, const char *who) = nullptr;
+    void (*ran)(ljmd_batch *h, int snapshots) = nullptr;
+    // NULL, or whether the `snapshots` of a call fit: LJMD_OK, or LJMD_ERR_STATE before anything is launched
+    int (*room)(ljmd_batch *h, int snapshots, const char *who) = nullptr;
+};
+
+// pressure tensor series (ljmd_stress_batch.cpp): off while max_snapshots == 0, and every is 0 then.  That file is not
+// linked into every program that links ljmd_batch.cpp (tests/batch_trace), so the handle carries its entry into the
+// step loop and its release: ljmd_batch_stress_configure fills both, and default-constructed means nothing is called
+struct BatchStress {
+    int32_t max_snapshots = 0, every = 0;
+    int64_t count = 0;                // snapshots in the series
+    uint64_t *d_words = nullptr;      // [max_snapshots][B][12][3] signed 192-bit
+    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_stress_reset
+    BatchAccumulator acc;
+    void (*release)(ljmd_batch *h) = nullptr;
+};
+
 }  // namespace ljmdb
 
 struct ljmd_batch {
@@ -82,6 +110,7 @@ struct ljmd_batch {
     int32_t last_launches = 0;
     ljmdb::BatchRdf rdf;
     ljmdb::BatchTcf tcf;
+    ljmdb::BatchStress stress;
     std::string err;
 };
 
@@ -93,9 +122,10 @@ inline bool reproducible(const ljmd_batch *h) { return h->mode == LJMD_PRECISION
 inline double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
 
 // What an entry point requires before it starts, checked in this order after the NULL handle: configured g(r),
-// configured MSD / VACF, a state, valid accelerations, no poison (LJMD_ERR_STATE each); kNeedDevice: the handle's device
-// is then made current (ljmd_batch.cpp)
-enum BatchNeed : unsigned { kNeedRdf = 1, kNeedTcf = 2, kNeedState = 4, kNeedAccel = 8, kNeedSound = 16, kNeedDevice = 32 };
+// configured MSD / VACF, configured pressure tensor, a state, valid accelerations, no poison (LJMD_ERR_STATE each);
+// kNeedDevice: the handle's device is then made current (ljmd_batch.cpp)
+enum BatchNeed : unsigned { kNeedRdf = 1, kNeedTcf = 2, kNeedState = 4, kNeedAccel = 8, kNeedSound = 16, kNeedDevice = 32,
+                         kNeedStress = 64 };
 int enter(ljmd_batch *h, const char *who, unsigned need);
 
 // fails the call as fail() does and poisons the handle: LJMD_ERR_STATE from the guarded calls until ljmd_batch_set_state
@@ -130,20 +160,15 @@ int host_alloc(const ljmd_batch *h, const char *who, F &&grow)
     return LJMD_OK;
 }
 
-// An accumulator as the step loop sees it (run_groups, ljmd_batch_steps): a launch ends at the steps every, 2 every, ...
-// of the call, the group's enqueue follows it on the same stream, and ran() does the host's share after the whole call.
-struct BatchAccumulator {
-    int every = 0;                    // steps between two snapshots of ljmd_batch_steps; 0: off, or not taken by it
-    const char *name = nullptr;       // "g(r)": "... is not a multiple of the g(r) interval"
-    const char *tag = nullptr;        // "rdf": ljmd_batch_rdf_configure
-    // the launches of group g on stream s for snapshot k (0-based) of this call; counts them; a failure poisons
-    int (*enqueue)(ljmd_batch *h, const BatchGroup &g, hipStream_t s, int k, int32_t *count, const char *who) = nullptr;
-    void (*ran)(ljmd_batch *h, int snapshots) = nullptr;
-};
 BatchAccumulator rdf_accumulator(const ljmd_batch *h);    // ljmd_batch_rdf.cpp
 BatchAccumulator tcf_accumulator(const ljmd_batch *h);    // ljmd_batch_tcf.cpp
-using BatchAccumulators = std::array<BatchAccumulator, 2>;
-inline BatchAccumulators accumulators(const ljmd_batch *h) { return {rdf_accumulator(h), tcf_accumulator(h)}; }
+using BatchAccumulators = std::array<BatchAccumulator, 3>;
+inline BatchAccumulators accumulators(const ljmd_batch *h)
+{
+    BatchAccumulator stress = h->stress.acc;
+    stress.every = h->stress.every;
+    return {rdf_accumulator(h), tcf_accumulator(h), stress};
+}
 
 // one snapshot of the resident state outside ljmd_batch_steps, on the handle's stream (ljmd_batch_*_accumulate)
 int accumulate_now(ljmd_batch *h, const BatchAccumulator &a, const char *who);

@@ -178,17 +178,6 @@ int stress_fetch(StressState *st, std::string *err, const char *who, const Stres
     return LJMD_OK;
 }
 
-void stress_doubles(const int64_t *words, double L, double *out6)
-{
-    const double V = (L * L) * L;
-    for (int c = 0; c < kStressComponents; ++c) {
-        const int64_t *k = words + 3 * c, *s = words + 3 * (kStressComponents + c);
-        const uint64_t kw[3] = {(uint64_t)k[0], (uint64_t)k[1], (uint64_t)k[2]};
-        const uint64_t sw[3] = {(uint64_t)s[0], (uint64_t)s[1], (uint64_t)s[2]};
-        out6[c] = (ljmdk::fixed_to_double(kw) + 12.0 * ljmdk::fixed_to_double(sw)) / V;
-    }
-}
-
 int stress_read(StressState *st, std::string *err, const char *who, const StressView &v, double *p, int64_t *n_snapshots)
 {
     if (st->max_snapshots == 0) return not_configured(err, who);

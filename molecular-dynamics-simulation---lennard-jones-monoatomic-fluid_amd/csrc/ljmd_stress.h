@@ -7,6 +7,7 @@
 #ifndef LJMD_STRESS_H
 #define LJMD_STRESS_H
 
+#include "ljmd_internal.h"
 #include "ljmd_rdf.h"
 
 namespace ljmds {
@@ -97,8 +98,17 @@ int stress_profile_read(StressState *st, std::string *err, const char *who, cons
                         int64_t *total, double *kernel_ms);
 // frees everything after what may still use it; the state is "not configured" afterwards
 void stress_release(StressState *st, hipStream_t stream);
-// p[c] = (R(K[c]) + 12 R(S[c])) / ((L L) L) of one snapshot's words
-void stress_doubles(const int64_t *words, double L, double *out6);
+// p[c] = (R(K[c]) + 12 R(S[c])) / ((L L) L) of one snapshot's words (inline: the batch engine's read uses it too)
+inline void stress_doubles(const int64_t *words, double L, double *out6)
+{
+    const double V = (L * L) * L;
+    for (int c = 0; c < kStressComponents; ++c) {
+        const int64_t *k = words + 3 * c, *s = words + 3 * (kStressComponents + c);
+        const uint64_t kw[3] = {(uint64_t)k[0], (uint64_t)k[1], (uint64_t)k[2]};
+        const uint64_t sw[3] = {(uint64_t)s[0], (uint64_t)s[1], (uint64_t)s[2]};
+        out6[c] = (ljmdk::fixed_to_double(kw) + 12.0 * ljmdk::fixed_to_double(sw)) / V;
+    }
+}
 
 }  // namespace ljmds
 #endif

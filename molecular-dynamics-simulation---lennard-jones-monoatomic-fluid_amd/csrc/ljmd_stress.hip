@@ -2,7 +2,8 @@
 // sums of f_a d_b over the pairs within the cutoff and of v_a v_b over the particles, where the state lives, in the
 // engine's tile order.
 //
-// Per pair pair_fixed's arithmetic (ljmd_internal.h), unfused and left to right (-ffp-contract=off, csrc/Makefile):
+// Per pair pair_fixed's arithmetic (ljmd_internal.h), unfused and left to right (-ffp-contract=off, csrc/Makefile) -- the
+// one copy of it, with add_six and wave_sum192, is ljmd_stress_arith.h, shared with the batch engine's kernel:
 //   d0 = x_i - x_j ; d = d0 - L * round(d0 * invL)              (half away from zero)
 //   r2 = dx*dx + dy*dy + dz*dz ; if r2 < rc2:
 //   u = 1.0 / r2 ; u3 = u*u*u ; u6 = u3*u3 ; mdu = 2.0*u6 - u3 ; fx = mdu*dx*u (fy, fz likewise)
@@ -24,41 +25,23 @@
 #include "ljmd_stress.h"
 
 #include "ljmd_internal.h"
+#include "ljmd_stress_arith.h"
 
 namespace ljmds {
 namespace {
 
+static_assert(kStressComponents == ljmdk::kStressTerms, "the shared arithmetic adds six terms");
+
 using ljmdk::add192;
-using ljmdk::fixed_add;
-using ljmdk::fixed_out_of_range;
+using ljmdk::add_six;
 using ljmdk::from128;
 using ljmdk::kTile;
+using ljmdk::stress_image;
+using ljmdk::stress_terms;
+using ljmdk::wave_sum192;
 using ljmdr::rdf_tile_gap2;
 using ljmdr::rdf_walk_column;
 using ljmdr::rdf_walk_takes;
-
-// sum over the wave of one signed 192-bit integer per lane; valid in lane 0
-__device__ __forceinline__ void wave_sum192(uint64_t (&q)[3])
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        uint64_t o[3];
-#pragma unroll
-        for (int w = 0; w < 3; ++w) o[w] = __shfl_down(q[w], off, 64);
-        add192(q, o);
-    }
-}
-
-// acc[c] += Q(t[c]) for the six terms -- or six zeros, and the flag, when `oob` or one of the terms is out of range
-__device__ __forceinline__ void add_six(__int128 (&acc)[kStressComponents], const double (&t)[kStressComponents], bool oob,
-                                        bool &bad)
-{
-#pragma unroll
-    for (int c = 0; c < kStressComponents; ++c) oob = oob || fixed_out_of_range(t[c]);
-    bad = bad || oob;
-#pragma unroll
-    for (int c = 0; c < kStressComponents; ++c) fixed_add(acc[c], oob ? 0.0 : t[c]);
-}
 
 // the 64 x 64 pairs of one (row tile, column tile).  MODE 0: all of them; 1: column slot > row slot (the diagonal tile of
 // the unordered walk); 2: column slot != row slot (the own tile of the ordered walk)
@@ -74,22 +57,16 @@ __device__ __forceinline__ void tile_pairs(const StressPairArgs &a, const double
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
             const double dx0 = xi - xj[k], dy0 = yi - yj[k], dz0 = zi - zj[k];
-            const double dx = dx0 - a.L * __builtin_round(dx0 * a.invL);
-            const double dy = dy0 - a.L * __builtin_round(dy0 * a.invL);
-            const double dz = dz0 - a.L * __builtin_round(dz0 * a.invL);
+            const double dx = stress_image(dx0, a.L, a.invL);
+            const double dy = stress_image(dy0, a.L, a.invL);
+            const double dz = stress_image(dz0, a.L, a.invL);
             const double r2 = dx * dx + dy * dy + dz * dz;
             bool in = r2 < a.rc2;                                   // NaN (padding) never passes
             if (MODE == 1) in = in && (j0 + k > lane);
             if (MODE == 2) in = in && (j0 + k != lane);
             if (in) {
-                const double u = 1.0 / r2;
-                const double u3 = u * u * u;
-                const double u6 = u3 * u3;
-                const double mdu = 2.0 * u6 - u3;
-                const double fx = mdu * dx * u, fy = mdu * dy * u, fz = mdu * dz * u;
-                const double t[kStressComponents] = {fx * dx, fy * dy, fz * dz, fx * dy, fx * dz, fy * dz};
-                const bool oob = fixed_out_of_range(fx) || fixed_out_of_range(fy) || fixed_out_of_range(fz) ||
-                                 fixed_out_of_range(u6);
+                double t[kStressComponents];
+                const bool oob = stress_terms(dx, dy, dz, r2, t);
                 add_six(acc, t, oob, bad);
             }
         }

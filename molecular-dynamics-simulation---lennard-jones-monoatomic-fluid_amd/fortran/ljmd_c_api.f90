@@ -33,6 +33,8 @@ module ljmd_c_api
   public :: ljmd_stress_profile_read, ljmd_stress_from_exact, ljmd_time_origin_average
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
+  public :: ljmd_batch_stress_configure, ljmd_batch_stress_accumulate, ljmd_batch_stress_read, ljmd_batch_stress_read_exact
+  public :: ljmd_batch_stress_reset
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -43,6 +45,7 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_LAG = 4096
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_ORIGINS = 512
   integer(c_int32_t), parameter, public :: LJMD_STRESS_MAX_SNAPSHOTS = 262144
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_STRESS_MAX_SNAPSHOTS = 262144
 
   interface
     function ljmd_compute_lj_potential_energy(n, box_length, rc, rx, ry, rz, ax, ay, az, &
@@ -543,6 +546,43 @@ module ljmd_c_api
     end function
 
     function ljmd_batch_tcf_reset(handle) bind(C, name="ljmd_batch_tcf_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    ! pressure tensor of every replica of a batch handle (ljmd.h: ljmd_batch_stress_*); p = c_loc of [6, B, n_snapshots]
+    ! doubles, words = c_loc of [3, 12, B, n_snapshots] 64-bit words in Fortran order; c_null_ptr skips an output
+    function ljmd_batch_stress_configure(handle, max_snapshots, every) bind(C, name="ljmd_batch_stress_configure") &
+        result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_snapshots, every
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_stress_accumulate(handle) bind(C, name="ljmd_batch_stress_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_stress_read(handle, p, n_snapshots) bind(C, name="ljmd_batch_stress_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, p
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_stress_read_exact(handle, words, n_snapshots) bind(C, name="ljmd_batch_stress_read_exact") &
+        result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_stress_reset(handle) bind(C, name="ljmd_batch_stress_reset") result(status)
       import :: c_int, c_ptr
       type(c_ptr), value :: handle
       integer(c_int) :: status

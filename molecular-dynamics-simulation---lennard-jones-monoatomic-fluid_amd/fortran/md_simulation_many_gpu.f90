@@ -28,6 +28,11 @@
 ! sampling instants that write an rva.dat record, every LJMD_TCF_ORIGIN_STRIDE-th of them (default 1) an origin;
 ! outputs/run_NNNN/msd_vacf_gpu.dat gets a header line and, per lag with at least one origin, lag, lag * output_interval *
 ! dt, the number of origins, MSD and VACF),
+! LJMD_STRESS (default 0 = off; 1: the pressure tensor of every run is recorded on the device, ljmd_batch_stress_*, at
+! every sampling instant that writes an rva.dat record; outputs/run_NNNN/pressure_tensor_gpu.dat gets per instant its time
+! and p_xx, p_yy, p_zz, p_xy, p_xz, p_yz without tail correction, and with LJMD_STRESS_MAX_LAG > 0
+! outputs/run_NNNN/stress_acf_gpu.dat the shear and normal-difference autocorrelations and running Green-Kubo
+! viscosities of the run -- the files and formats of md_simulation_gpu; every other file stays byte-identical),
 ! LJMD_SEED_BASE (unset: the rv_init.dat files above are read; s >= 1: NO rv_init.dat is read -- run i is prepared on the
 ! device, ljmd_batch_prepare, with seed s + i - 1: the reference's FCC lattice, its generator's velocities, centre of
 ! mass removed, scaled to the target_total_energy of the run's own or the shared input file, then that file's
@@ -44,8 +49,9 @@ program md_simulation_many_gpu
   use read_input_files, only: read_simulation_parameters
   use ljmd_c_api
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
-  use md_stats,         only: run_statistics, stats_begin, stats_push
-  use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file
+  use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
+  use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
+                              write_stress_acf_file
   implicit none
 
   character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
@@ -81,6 +87,11 @@ program md_simulation_many_gpu
   real(c_double), allocatable, target :: tcf_msd(:, :), tcf_vacf(:, :)     ! [tcf_max_lag + 1, n_runs]
   integer(c_int64_t), allocatable, target :: tcf_counts(:)
   integer(c_int64_t) :: tcf_snapshots
+  logical :: stress_on
+  integer :: stress_max_lag
+  real(c_double), allocatable, target :: stress_p(:, :, :)      ! [6, n_runs, snapshots]
+  real(c_double), allocatable :: stress_times(:, :)             ! [snapshots, n_runs]
+  integer(c_int64_t) :: stress_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -109,6 +120,13 @@ program md_simulation_many_gpu
   call get_environment_variable('LJMD_TCF_ORIGIN_STRIDE', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) tcf_stride
   if (tcf_stride < 1) stop 'md_simulation_many: LJMD_TCF_ORIGIN_STRIDE must be >= 1.'
+  stress_on = .false.
+  call get_environment_variable('LJMD_STRESS', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) stress_on = trim(env) /= '0'
+  stress_max_lag = 0
+  call get_environment_variable('LJMD_STRESS_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) stress_max_lag
+  if (stress_max_lag < 0) stop 'md_simulation_many: LJMD_STRESS_MAX_LAG must be >= 0.'
 
   seed_base = 0
   call get_environment_variable('LJMD_SEED_BASE', env, status=ios)
@@ -181,6 +199,15 @@ program md_simulation_many_gpu
 
   n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
   if (n_snapshots_expected < 0) n_snapshots_expected = 0
+  if (stress_on) then
+    ! one snapshot per sampling instant that writes an rva.dat record, taken by hand as g(r) and MSD / VACF are
+    if (n_snapshots_expected < 1) stop 'md_simulation_many: LJMD_STRESS needs at least one sampling instant.'
+    if (n_snapshots_expected > LJMD_BATCH_STRESS_MAX_SNAPSHOTS) &
+      stop 'md_simulation_many: more sampling instants than LJMD_BATCH_STRESS_MAX_SNAPSHOTS.'
+    call ljmd_batch_check(ljmd_batch_stress_configure(batch, int(n_snapshots_expected, c_int32_t), 0_c_int32_t), batch, &
+                          'ljmd_batch_stress_configure')
+    allocate(stress_times(n_snapshots_expected, n_runs))
+  end if
   do i = 1, n_runs
     open(newunit=iu_rva(i), file=trim(run_dir(i)) // '/rva.dat', form='unformatted', status='replace', &
          action='write', iostat=ios)
@@ -211,6 +238,10 @@ program md_simulation_many_gpu
     num_samples = num_samples + 1
     if (rdf_bins > 0) call ljmd_batch_check(ljmd_batch_rdf_accumulate(batch), batch, 'ljmd_batch_rdf_accumulate')
     if (tcf_max_lag > 0) call ljmd_batch_check(ljmd_batch_tcf_accumulate(batch), batch, 'ljmd_batch_tcf_accumulate')
+    if (stress_on) then
+      call ljmd_batch_check(ljmd_batch_stress_accumulate(batch), batch, 'ljmd_batch_stress_accumulate')
+      stress_times(num_samples, :) = time_run
+    end if
     call ljmd_batch_check(ljmd_batch_get_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(ux), c_loc(uy), &
                                                c_loc(uz), c_loc(vx), c_loc(vy), c_loc(vz), c_loc(ax), c_loc(ay), &
                                                c_loc(az)), batch, 'ljmd_batch_get_state')
@@ -240,6 +271,11 @@ program md_simulation_many_gpu
     call ljmd_batch_check(ljmd_batch_tcf_read(batch, c_loc(tcf_msd), c_loc(tcf_vacf), c_loc(tcf_counts), &
                                               tcf_snapshots), batch, 'ljmd_batch_tcf_read')
   end if
+  if (stress_on) then
+    allocate(stress_p(6, n_runs, max(num_samples, 1)))
+    call ljmd_batch_check(ljmd_batch_stress_read(batch, c_loc(stress_p), stress_snapshots), batch, 'ljmd_batch_stress_read')
+    if (stress_snapshots /= num_samples) stop 'md_simulation_many: the pressure tensor series and the samples disagree.'
+  end if
   call ljmd_batch_destroy(batch)
   do i = 1, n_runs
     close(iu_out(i))
@@ -265,6 +301,11 @@ program md_simulation_many_gpu
     do i = 1, n_runs
       call write_msd_vacf_file(trim(run_dir(i)) // '/msd_vacf_gpu.dat', tcf_max_lag, output_interval, rparams(i)%dt, &
                                tcf_counts, tcf_msd(:, i), tcf_vacf(:, i))
+    end do
+  end if
+  if (stress_on) then
+    do i = 1, n_runs
+      call write_stress(i)
     end do
   end if
   if (any_own) then
@@ -315,6 +356,41 @@ contains
     call write_rdf_file(trim(run_dir(irun)) // '/rdf_gpu.dat', rparams(irun)%n, rparams(irun)%box_length, &
                         0.5d0 * rparams(irun)%box_length, rdf_bins, rdf_hist(:, irun), rdf_snapshots)
   end subroutine write_rdf
+
+  ! run i's pressure_tensor_gpu.dat and, with LJMD_STRESS_MAX_LAG > 0, stress_acf_gpu.dat: what md_simulation_gpu writes
+  ! for one run (md_run_outputs: write_pressure_tensor_file, write_stress_acf_file), from the run's rows of the series
+  subroutine write_stress(irun)
+    integer, intent(in) :: irun
+    real(c_double), allocatable, target :: p(:, :), c(:, :), shear(:), normal(:)
+    real(kind=dp_kind) :: mean_temp, std_temp
+    integer :: ns, lags
+    ns = int(num_samples)
+    allocate(p(6, ns))
+    p = stress_p(:, irun, 1:ns)
+    call write_pressure_tensor_file(trim(run_dir(irun)) // '/pressure_tensor_gpu.dat', ns, stress_times(1:ns, irun), p)
+    if (stress_max_lag <= 0 .or. ns < 2) return
+    ! the three shear components, then the three normal differences, as the velocity of one particle: [1, snapshots] each
+    allocate(c(ns, 6))
+    c(:, 1) = p(4, :)
+    c(:, 2) = p(5, :)
+    c(:, 3) = p(6, :)
+    c(:, 4) = 0.5d0 * (p(1, :) - p(2, :))
+    c(:, 5) = 0.5d0 * (p(2, :) - p(3, :))
+    c(:, 6) = 0.5d0 * (p(3, :) - p(1, :))
+    lags = min(stress_max_lag, ns - 1)
+    allocate(shear(0:lags), normal(0:lags))
+    call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(ns, c_int32_t), 1_c_int32_t, c_loc(c(1, 1)), c_loc(c(1, 2)), &
+                                             c_loc(c(1, 3)), int(lags, c_int32_t), 1_c_int32_t, c_loc(shear)), c_null_ptr, &
+                    'ljmd_time_origin_average')
+    call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(ns, c_int32_t), 1_c_int32_t, c_loc(c(1, 4)), c_loc(c(1, 5)), &
+                                             c_loc(c(1, 6)), int(lags, c_int32_t), 1_c_int32_t, c_loc(normal)), c_null_ptr, &
+                    'ljmd_time_origin_average')
+    shear = shear / 3.d0
+    normal = normal / 3.d0
+    call stats_mean_std(stats(irun), Q_T, mean_temp, std_temp)
+    call write_stress_acf_file(trim(run_dir(irun)) // '/stress_acf_gpu.dat', lags, output_interval, rparams(irun)%dt, &
+                               rparams(irun)%volume, mean_temp, shear, normal)
+  end subroutine write_stress
 
   ! LJMD_SEED_BASE: every run's initial configuration on the device (seed_base + i - 1, the run's target_total_energy,
   ! the shared warmup_steps), then each run's rv_init_gpu.dat: the two records of rv_init.dat

@@ -771,6 +771,58 @@ class BatchEngine:
     def tcf_reset(self) -> None:
         self._ck(self._lib.ljmd_batch_tcf_reset(self._h))
 
+    # -- pressure tensor on the device (include/ljmd.h: ljmd_batch_stress_*) ----
+    def stress_configure(self, max_snapshots: int, every: int = 0) -> None:
+        """ljmd_batch_stress_configure: room for max_snapshots snapshots of every replica's pressure tensor on the device;
+        every > 0: steps() appends the state after steps every, 2 every, ... by itself.  max_snapshots = 0 switches the
+        feature off.  The series starts empty."""
+        for name, val in (("max_snapshots", max_snapshots), ("every", every)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise TypeError(f"stress_configure: {name} must be an integer, got {val!r}")
+            if not -2 ** 31 <= int(val) <= 2 ** 31 - 1:
+                raise ValueError(f"stress_configure: {name} must lie within the int32 range")
+        self._ck(self._lib.ljmd_batch_stress_configure(self._h, int(max_snapshots), int(every)))
+        self._stress_max = int(max_snapshots)
+
+    def stress_accumulate(self) -> None:
+        """appends the pressure tensor of every replica's resident state to the series (no host wait)"""
+        self._ck(self._lib.ljmd_batch_stress_accumulate(self._h))
+
+    def _stress_rows(self, who: str) -> int:
+        """snapshots in the series (ljmd_batch_stress_read_exact without a buffer); raises as the reads do"""
+        if getattr(self, "_stress_max", 0) < 1:
+            raise ValueError(f"{who}: call stress_configure with max_snapshots >= 1 first")
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_stress_read_exact(self._h, None, C.byref(snaps)))
+        return snaps.value
+
+    def stress_read(self) -> np.ndarray:
+        """-> p[n_snapshots, B, 6]: xx, yy, zz, xy, xz, yz of (sum v v + 12 sum f d) / V_b per snapshot and replica,
+        without tail correction; nothing is cleared"""
+        p = np.empty((max(self._stress_rows("stress_read"), 1), self.n_replicas, 6), dtype=np.float64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_stress_read(self._h, _ptr(p), C.byref(snaps)))
+        return p[:snaps.value].copy()
+
+    def stress_read_exact(self, raw: bool = False):
+        """-> sums[n_snapshots, B, 12]: the exact integer sums of Q(term) = RNE(term 2^64), K[6] then S[6], as Python
+        ints in an object array -- or, raw=True, the library's int64 words [n_snapshots, B, 12, 3] (three little-endian
+        limbs of a signed 192-bit integer)"""
+        words = np.empty((max(self._stress_rows("stress_read_exact"), 1), self.n_replicas, 12, 3), dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_stress_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        words = words[:snaps.value].copy()
+        if raw:
+            return words
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:3], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums
+
+    def stress_reset(self) -> None:
+        self._ck(self._lib.ljmd_batch_stress_reset(self._h))
+
     @staticmethod
     def per_replica(params_list, device: int = 0,
                     precision_mode: int = _lib.PRECISION_FP64) -> "PerReplicaBatchEngine":
