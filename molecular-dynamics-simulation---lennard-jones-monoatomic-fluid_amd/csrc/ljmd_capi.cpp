@@ -147,9 +147,19 @@ int ljmd_set_state(ljmd_t *h, const double *rx, const double *ry, const double *
             }
             for (size_t i = S; i < P; ++i) dst[i] = NAN;
         }
+    // Fast-path precondition (a): the tile-pair test (axis_gap, uniform_image) and the pair kernels take coordinate
+    // differences |d| < 2.5 L.  Kernels that read the coordinates as given (gather, fixed-point, g(r) and stress walks)
+    // have that for a span < 2.4 L: positions_compact.  The Newton-3 kernels read them framed per row group
+    // (tile_boxes_kernel: every particle in the image nearest to the first particle of its group, so up to L / 2 beyond
+    // either end of the span where a group is wider than L / 2, as groups of raw input can be), and differences of framed
+    // coordinates reach span + L.  From a span of 1.4 L on (positions_wide) the frame is therefore taken from the wrapped
+    // coordinates, which keeps the framed copy inside [-L / 2, 3 L / 2] whatever the input.
     h->positions_compact = finite;
-    for (int ax = 0; ax < 3; ++ax)
+    h->positions_wide = false;
+    for (int ax = 0; ax < 3; ++ax) {
         if (!(hi[ax] - lo[ax] < 2.4 * h->L)) h->positions_compact = false;
+        if (!(hi[ax] - lo[ax] < 1.4 * h->L)) h->positions_wide = true;
+    }
     {   // k-d split axes: halve the longest remaining extent of the OWN shard at every level, so that a
         // slab- or column-shaped shard (multi-GPU index ranges) still ends in near-cubic tiles
         double ext[3];

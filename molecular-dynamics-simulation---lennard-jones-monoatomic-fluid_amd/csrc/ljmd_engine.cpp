@@ -41,6 +41,7 @@ GeometryArgs geometry_args(ljmd_t *h)
     a.pos = h->d_pos;
     a.bbox = h->d_bbox;
     a.pos_tc = h->plan.use_n3 ? h->d_pos_tc : nullptr;
+    a.wrap_first = h->positions_wide ? 1 : 0;
     a.invL = h->invL;
     a.mask = h->d_mask;
     a.P = h->plan.P;
@@ -522,6 +523,7 @@ int enqueue_drift_positions(ljmd_t *h, EventSet *q, bool *split)
     *split = !resort_now;
     LJMD_HIP(h, launch_drift_kick(integrate_args(h), resort_now ? 0 : 1, h->stream));
     h->positions_compact = true;  // freshly wrapped into [0, L]
+    h->positions_wide = false;
     if (h->plan.sort_enabled && fast_path_ok(h) && ++h->steps_since_sort >= h->plan.resort_every) {
         if (*split) {             // (positions that only became compact with this wrap: finish K1 before permuting)
             LJMD_HIP(h, launch_drift_kick(integrate_args(h), 2, h->stream));
@@ -574,6 +576,7 @@ int enqueue_drift(ljmd_t *h, EventSet *q)
         h->drift_prefused = false;
         h->boxes_valid = !resort_now && fast_path_ok(h);
         h->positions_compact = true;
+        h->positions_wide = false;
         if (h->plan.sort_enabled && fast_path_ok(h) && ++h->steps_since_sort >= h->plan.resort_every) return resort(h, false);
         return LJMD_OK;
     }
@@ -589,6 +592,7 @@ int enqueue_drift(ljmd_t *h, EventSet *q)
     }
     LJMD_HIP(h, launch_drift_kick(ia, 0, h->stream));
     h->positions_compact = true;  // freshly wrapped into [0, L]
+    h->positions_wide = false;
     if (h->plan.sort_enabled && fast_path_ok(h) && ++h->steps_since_sort >= h->plan.resort_every)
         return resort(h, false);  // a(t) is dead after the drift/kick: K3 rewrites it
     return LJMD_OK;

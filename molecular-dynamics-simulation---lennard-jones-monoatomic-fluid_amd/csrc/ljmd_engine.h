@@ -103,6 +103,7 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     ljmdh::LaunchPlan plan;           // constant after ljmd_create
     bool tail_on = true;              // ljmd_set_tail_corrections (the reference's use_tail_corrections, default .true.)
     bool positions_compact = false;   // coordinate spread < 2.4 L (always true after a wrap)
+    bool positions_wide = false;      // coordinate spread >= 1.4 L: tile_boxes_kernel frames the wrapped coordinates (never after a wrap)
     bool have_state = false, have_accel = false;
     int steps_since_sort = 0;
 

@@ -143,6 +143,7 @@ struct GeometryArgs {
                             // `mask` then holds only the NEAR pairs (box distance <= r_split, or same row group)
     int P, G, rank, TB, T, W;
     int RT;                 // tiles per Newton-3 row group (same-group pairs always count as NEAR)
+    int wrap_first;         // tile_boxes_kernel: frame the wrapped coordinates (raw input spanning 1.4 L or more, ljmd_set_state)
     double L, invL, rc2_skin;   // rc^2 * (1 + 1e-10): skip only when provably outside
     double rsplit2;         // r_split^2
     double rvfar2;          // mixed precision: box distance^2 beyond which a far pass is VERY FAR (u^3 = r^-6 < 2^-26: the u^6
@@ -360,7 +361,9 @@ __device__ __forceinline__ void block_sum(double (&v)[NVAL], double *lds /* [NVA
 }
 
 // FAST path building blocks.  Preconditions (checked on the host):
-//   (a) every coordinate lies within a span < 2.4 L (true after any wrap), so |d/L| < 2.5,
+//   (a) every coordinate the kernel reads lies within a span < 2.4 L (true after any wrap; the framed copy of the Newton-3
+//       kernels, up to L / 2 beyond either end of what it frames, has it for a raw span < 1.4 L and is taken from the
+//       wrapped coordinates otherwise: GeometryArgs::wrap_first), so |d/L| < 2.5,
 //       n = rndne(d/L) has |n| <= 2 and L*n is exact: fma(-L, n, d) == d - L*n rounded once,
 //       i.e. the same value the reference computes;
 //   (b) rc <= (1 - 1e-9) L/2: rndne and dnint differ only on exact ties of d/L, where

@@ -1134,7 +1134,7 @@ __global__ __launch_bounds__(kTile * W, MIN_WAVES) void pair_n3_kernel(N3Args a)
                 if (a.inline_class) {
                     GeometryArgs ga;
                     ga.pos = nullptr; ga.bbox = const_cast<double *>(a.bbox); ga.pos_tc = nullptr; ga.mask = nullptr; ga.mask_far = nullptr;
-                    ga.P = a.P; ga.G = a.G; ga.rank = a.rank; ga.TB = a.TB; ga.T = a.T; ga.W = a.W; ga.RT = RT;
+                    ga.P = a.P; ga.G = a.G; ga.rank = a.rank; ga.TB = a.TB; ga.T = a.T; ga.W = a.W; ga.RT = RT; ga.wrap_first = 0;
                     ga.L = a.L; ga.invL = a.invL; ga.rc2_skin = a.rc2_skin; ga.rsplit2 = 0.0; ga.rvfar2 = 0.0; ga.pertile_images = 0;
                     ga.both_ties = a.both_ties;
                     unsigned dsc = 0;
@@ -1534,10 +1534,18 @@ __global__ __launch_bounds__(kBlock) void tile_boxes_kernel(GeometryArgs a)
         // face); the box bounds those coordinates.  Forces depend on coordinate differences modulo L only.
         // (the anchor is the first particle of the tile's ROW GROUP: the RT tiles of a group share one frame, so that
         //  the group's box -- the union that decides the image class and INNER of its passes -- stays compact too)
+        // (raw input may put a group's particles more than L / 2 from its first one; the frame then carries them up to
+        //  L / 2 beyond the span of the input, and box differences beyond the 2.5 L of axis_gap unless that span is below
+        //  1.4 L: wider input -- wrap_first -- is wrapped into the box first, as the drift kernel would wrap it)
         const double *g0 = a.pos + (size_t)g * 3 * a.P + (size_t)(tl / a.RT) * a.RT * kTile;
-        x = tile_frame(x, g0[0], a.L, a.invL);
-        y = tile_frame(y, g0[a.P], a.L, a.invL);
-        z = tile_frame(z, g0[2 * (size_t)a.P], a.L, a.invL);
+        double x0 = g0[0], y0 = g0[a.P], z0 = g0[2 * (size_t)a.P];
+        if (a.wrap_first) {
+            x = fma(-a.L, floor(x * a.invL), x); y = fma(-a.L, floor(y * a.invL), y); z = fma(-a.L, floor(z * a.invL), z);
+            x0 = fma(-a.L, floor(x0 * a.invL), x0); y0 = fma(-a.L, floor(y0 * a.invL), y0); z0 = fma(-a.L, floor(z0 * a.invL), z0);
+        }
+        x = tile_frame(x, x0, a.L, a.invL);
+        y = tile_frame(y, y0, a.L, a.invL);
+        z = tile_frame(z, z0, a.L, a.invL);
         double *c = a.pos_tc + o0;
         c[0] = x; c[a.P] = y; c[2 * (size_t)a.P] = z;
     }
