@@ -85,16 +85,10 @@ int ljmd_create(ljmd_t **out, int32_t n, double box_length, double dt, double rc
 
 void ljmd_destroy(ljmd_t *h)
 {
-    if (h && h->multi) {
+    if (h && h->multi)
         ljmdm::destroy(h);
-        return;
-    }
-    if (h) {
-        // the pressure tensor's buffers go here, not in release(): ljmd_storage.cpp links without ljmd_stress.cpp
-        if (h->device >= 0) (void)hipSetDevice(h->device);
-        ljmds::stress_release(&h->stress, h->stream);
-    }
-    release(h);
+    else
+        release(h);
 }
 
 int ljmd_create_multi(ljmd_t **out, int32_t n, double box_length, double dt, double rc, int32_t precision_mode,

@@ -34,6 +34,16 @@ inline int fail(std::nullptr_t, int code, const char *fmt, ...)
     return code;
 }
 
+// the message string itself, for code that sees no handle (the cores of the resident observables)
+inline int fail(std::string *err, int code, const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    failv(err, code, fmt, ap);
+    va_end(ap);
+    return code;
+}
+
 // H: any handle type with a std::string err (ljmd, ljmd_batch)
 template <class H>
 int fail(const H *h, int code, const char *fmt, ...)

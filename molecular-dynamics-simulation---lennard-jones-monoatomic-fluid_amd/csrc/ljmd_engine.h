@@ -18,9 +18,7 @@
 #include <vector>
 
 #include "ljmd_internal.h"
-#include "ljmd_rdf.h"
-#include "ljmd_stress.h"
-#include "ljmd_tcf.h"
+#include "ljmd_resident.h"
 
 using namespace ljmdk;
 
@@ -219,12 +217,13 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     double mig_ext[3] = {0, 0, 0};    // extents of a rank's block after the deal (choose the shard's k-d axes)
     int32_t migrations = 0;
 
-    // resident g(r) (ljmd_rdf_*, ljmd_rdf.cpp); a multi-device parent keeps only nbins here, the ranks own the buffers
+    // the resident observables (entry points and release_resident: ljmd_resident.cpp).  g(r) (ljmd_rdf_*, core
+    // ljmd_rdf.cpp); a multi-device parent keeps only nbins here, the ranks own the buffers
     ljmdr::RdfState rdf;
-    // resident MSD / VACF (ljmd_tcf_*, ljmd_tcf.cpp): one-rank engines only
+    // MSD / VACF (ljmd_tcf_*, core ljmd_tcf.cpp): one-rank engines only
     ljmdt::TcfState tcf;
-    // resident pressure tensor (ljmd_stress_*, ljmd_stress.cpp); a multi-device parent keeps only max_snapshots and the
-    // snapshot count here.  Freed where a handle is destroyed (ljmd_capi.cpp, ljmd_multi.cpp), not by release()
+    // pressure tensor (ljmd_stress_*, core ljmd_stress.cpp); a multi-device parent keeps only max_snapshots and the
+    // snapshot count here
     ljmds::StressState stress;
     bool step_open = false;           // between ljmd_step_begin and ljmd_step_finish (split-phase API)
 
@@ -251,6 +250,9 @@ IntegrateArgs integrate_args(ljmd_t *h);
 // the caller releases whatever exists
 int allocate_engine(ljmd_t *h);
 void release(ljmd_t *h);
+// what ljmd_rdf_configure, ljmd_tcf_configure and ljmd_stress_configure allocated; the engine's device is current
+// (ljmd_resident.cpp; called by release)
+void release_resident(ljmd_t *h);
 // HBM -> host of any of r, ru, v, a (dsts[3 w + k], NULL = skip) and of the last n_records scalar records
 int download_state(ljmd_t *h, double *const dsts[12], unsigned n_records);
 int upload_shard3(ljmd_t *h, double *dst, const double *x, const double *y, const double *z);

@@ -621,11 +621,7 @@ void destroy(ljmd_t *h)
             if (p) (void)hipHostFree(p);
         for (double *p : m->h_xforce)
             if (p) (void)hipHostFree(p);
-        for (ljmd_t *e : m->eng) {
-            (void)hipSetDevice(e->device);
-            ljmds::stress_release(&e->stress, e->stream);      // as ljmd_destroy does for a handle of its own
-            release(e);
-        }
+        for (ljmd_t *e : m->eng) release(e);
         delete m;
     }
     delete h;

@@ -1,5 +1,5 @@
 // ljmd_rdf.h -- g(r) of the system resident on the single / sharded engine (include/ljmd.h: ljmd_rdf_*): argument
-// blocks of the two kernels of ljmd_rdf.hip, the tile-pair bound they skip by, and the host core of ljmd_rdf.cpp.
+// blocks of the two kernels of ljmd_rdf.hip and the tile-pair bound they skip by.  The host side is ljmd_resident.h.
 //
 // The layout is the engine's (ljmd_internal.h): exchange buffer pos[G][3][P], 64-slot tiles, TB tiles per rank block,
 // T = G TB tiles, NaN on the padding slots.
@@ -8,9 +8,6 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <optional>
-#include <string>
 
 namespace ljmdr {
 
@@ -97,46 +94,6 @@ __host__ __device__ inline bool rdf_walk_takes(int I, int u, int u1, int T, bool
 
 hipError_t launch_rdf_boxes(const RdfBoxArgs &a, hipStream_t s);
 hipError_t launch_rdf_pairs(const RdfPairArgs &a, dim3 grid, hipStream_t s);
-
-// ---- host core (ljmd_rdf.cpp): knows nothing of struct ljmd ----
-
-// what the core needs to know of an engine
-struct RdfView {
-    int n = 0, S = 0, P = 0, TB = 0, T = 0, G = 1, rank = 0;
-    double L = 0, invL = 0;
-    const double *pos = nullptr;    // exchange buffer
-    hipStream_t stream = nullptr;
-    bool compact = false;           // coordinate spread < 2.4 L
-    std::optional<int> walk_chunk;  // LJMD_WALK_CHUNK as the handle read it (Knobs::walk_chunk)
-};
-
-struct RdfState {
-    int nbins = 0;                  // 0 = not configured
-    double rmax = 0, dr = 0, inv_dr = 0;
-    unsigned long long *d_hist = nullptr;   // [nbins]
-    unsigned long long *d_count = nullptr;  // [2]
-    double *d_bbox = nullptr;               // [T][kRdfBoxStride]
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the launches of the most recent accumulate
-    bool timed = false;             // ev0 / ev1 have been recorded
-    int64_t snapshots = 0;
-};
-
-// the grid of one accumulate: steps, steps per slice, slices
-struct RdfWalk {
-    int U = 0, chunk = 0, slices = 0, row_blocks = 0, weight = 0;
-};
-// walk_chunk unset: steps per slice by kRdfTargetWorkgroups; set: that many, clamped to [1, min(U, kRdfMaxChunk)] (tests)
-RdfWalk rdf_plan_walk(int TB, int T, int G, std::optional<int> walk_chunk = std::nullopt);
-
-// All return an LJMD_* code and leave a message in *err (and in the thread's last error).  `who` = the public name.
-int rdf_configure(RdfState *st, std::string *err, const char *who, const RdfView &v, int32_t nbins, double rmax);
-int rdf_accumulate(RdfState *st, std::string *err, const char *who, const RdfView &v);
-int rdf_read(RdfState *st, std::string *err, const char *who, const RdfView &v, uint64_t *hist, int64_t *n_snapshots);
-int rdf_reset(RdfState *st, std::string *err, const char *who, const RdfView &v);
-int rdf_profile_read(RdfState *st, std::string *err, const char *who, const RdfView &v, int64_t *visited, int64_t *total,
-                     double *kernel_ms);
-// frees everything after what may still use it; the state is "not configured" afterwards
-void rdf_release(RdfState *st, hipStream_t stream);
 
 }  // namespace ljmdr
 #endif

@@ -1,0 +1,217 @@
+// ljmd_resident.h -- host side of the three observables of the system resident on the single / sharded engine: g(r)
+// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp) and the pressure tensor (ljmd_stress.cpp).  What the three cores share --
+// the view through which they see an engine, their named device buffers, the timer around one accumulate -- and each
+// core's state and functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host,
+// tests/tcf_host, tests/stress_host); every C entry point that takes a handle is in ljmd_resident.cpp.  Host code only:
+// the kernels' side is ljmd_rdf.h, ljmd_tcf.h and ljmd_stress.h.
+#ifndef LJMD_RESIDENT_H
+#define LJMD_RESIDENT_H
+
+#include "ljmd_common.h"
+#include "ljmd_rdf.h"
+#include "ljmd_stress.h"
+#include "ljmd_tcf.h"
+
+#include <array>
+#include <optional>
+#include <string>
+#include <vector>
+
+namespace ljmdh {
+
+// what the cores need to know of an engine; each reads the fields of its own kernels
+struct ResidentView {
+    int n = 0, S = 0, P = 0, TB = 0, T = 0, G = 1, rank = 0;   // G = n_ranks (a multi-device handle: its number of devices)
+    bool multi = false;
+    double L = 0, invL = 0, rc2 = 0;
+    const double *pos = nullptr;    // exchange buffer
+    const double *ru = nullptr, *v = nullptr;   // [3][P]
+    const int *perm = nullptr;      // the DEVICE's permutation, stream-ordered behind the re-sorts
+    hipStream_t stream = nullptr;
+    bool compact = false;           // coordinate spread < 2.4 L
+    std::optional<int> walk_chunk;  // LJMD_WALK_CHUNK as the handle read it (Knobs::walk_chunk)
+};
+
+// one device buffer of a state: where its pointer lives, its size, and what a failed allocation calls it
+struct DeviceBuffer {
+    void **p;
+    size_t bytes;
+    const char *name;
+};
+
+// allocates in the order of the array; the buffer that fails stays NULL: "<who>: out of device memory for <name>"
+template <size_t N>
+int alloc_buffers(std::string *err, const char *who, const std::array<DeviceBuffer, N> &bufs)
+{
+    for (const DeviceBuffer &b : bufs)
+        if (hipMalloc(b.p, b.bytes) != hipSuccess) {
+            *b.p = nullptr;
+            (void)hipGetLastError();
+            return fail(err, LJMD_ERR_ALLOC, "%s: out of device memory for %s (%zu bytes)", who, b.name, b.bytes);
+        }
+    return LJMD_OK;
+}
+
+// frees what exists, after what may still use it on `stream`
+template <size_t N>
+void free_buffers(const std::array<DeviceBuffer, N> &bufs, hipStream_t stream)
+{
+    bool any = false;
+    for (const DeviceBuffer &b : bufs) any = any || *b.p;
+    if (stream && any) (void)hipStreamSynchronize(stream);
+    for (const DeviceBuffer &b : bufs)
+        if (*b.p) (void)hipFree(*b.p);
+}
+
+// device time of the launches of the most recent accumulate
+struct KernelTimer {
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    bool timed = false;             // ev0 / ev1 have been recorded
+
+    hipError_t create()
+    {
+        const hipError_t e = hipEventCreate(&ev0);
+        return e != hipSuccess ? e : hipEventCreate(&ev1);
+    }
+    void destroy()
+    {
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        *this = {};
+    }
+    hipError_t start(hipStream_t s) { return hipEventRecord(ev0, s); }
+    hipError_t stop(hipStream_t s)
+    {
+        const hipError_t e = hipEventRecord(ev1, s);
+        if (e == hipSuccess) timed = true;
+        return e;
+    }
+    // waits for `s`; 0 before the first accumulate
+    hipError_t elapsed_ms(hipStream_t s, float *ms) const
+    {
+        *ms = 0.0f;
+        if (!timed) return hipSuccess;
+        const hipError_t e = hipStreamSynchronize(s);
+        return e != hipSuccess ? e : hipEventElapsedTime(ms, ev0, ev1);
+    }
+};
+
+}  // namespace ljmdh
+
+// Every core function returns an LJMD_* code and leaves a message in *err (and in the thread's last error).  `who` = the
+// public name.  *_release frees everything after what may still use it; the state is "not configured" afterwards.
+// not_configured fails with LJMD_ERR_STATE and the observable's "... is not configured" message.
+
+namespace ljmdr {
+
+using ljmdh::ResidentView;
+
+struct RdfState {
+    int nbins = 0;                  // 0 = not configured
+    double rmax = 0, dr = 0, inv_dr = 0;
+    unsigned long long *d_hist = nullptr;   // [nbins]
+    unsigned long long *d_count = nullptr;  // [2]
+    double *d_bbox = nullptr;               // [T][kRdfBoxStride]
+    ljmdh::KernelTimer timer;
+    int64_t snapshots = 0;
+};
+
+// the grid of one accumulate: steps, steps per slice, slices
+struct RdfWalk {
+    int U = 0, chunk = 0, slices = 0, row_blocks = 0, weight = 0;
+};
+// walk_chunk unset: steps per slice by kRdfTargetWorkgroups; set: that many, clamped to [1, min(U, kRdfMaxChunk)] (tests)
+RdfWalk rdf_plan_walk(int TB, int T, int G, std::optional<int> walk_chunk = std::nullopt);
+
+int not_configured(std::string *err, const char *who);
+int rdf_configure(RdfState *st, std::string *err, const char *who, const ResidentView &v, int32_t nbins, double rmax);
+int rdf_accumulate(RdfState *st, std::string *err, const char *who, const ResidentView &v);
+int rdf_read(RdfState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *hist, int64_t *n_snapshots);
+int rdf_reset(RdfState *st, std::string *err, const char *who, const ResidentView &v);
+int rdf_profile_read(RdfState *st, std::string *err, const char *who, const ResidentView &v, int64_t *visited, int64_t *total,
+                     double *kernel_ms);
+void rdf_release(RdfState *st, hipStream_t stream);
+
+}  // namespace ljmdr
+
+namespace ljmdt {
+
+using ljmdh::ResidentView;
+
+// sizes of one configuration, all in size_t: the ring of n = 262 144 with 512 slots has 6.4e9 bytes
+struct TcfSizes {
+    int slots = 0, ents = 0, nblk = 0;  // ents = slots + 1 entries per row of the partials
+    size_t n_pad = 0;
+    size_t cur_bytes = 0, ring_bytes = 0, part_bytes = 0, flag_bytes = 0, sums_bytes = 0;
+};
+TcfSizes tcf_sizes(int n, int max_lag, int stride);
+
+// the grid of the terms kernel for n_live >= 1 live origins: (nblk, slices), chunk origins per slice
+struct TcfSlices {
+    int chunk = 0, slices = 0;
+};
+TcfSlices tcf_plan_slices(int nblk, int n_live);
+
+struct TcfState {
+    int max_lag = 0;                // 0 = not configured
+    int stride = 0, n = 0;
+    TcfSizes sz;
+    double *d_cur = nullptr, *d_ring = nullptr;
+    unsigned long long *d_part = nullptr;
+    int32_t *d_flag = nullptr, *d_range = nullptr;
+    uint64_t *d_sums = nullptr;
+    ljmdh::KernelTimer timer;
+    int last_live = 0;              // live origins the most recent accumulate visited
+    int64_t s = 0;                  // number of the next snapshot of this trajectory
+    int64_t snapshots = 0;
+    std::vector<int64_t> counts;    // [max_lag + 1] origins that contributed to each lag
+};
+
+int not_configured(std::string *err, const char *who);
+// refuses a multi-device handle and a rank engine of G > 1 itself
+int tcf_configure(TcfState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_lag, int32_t origin_stride);
+int tcf_accumulate(TcfState *st, std::string *err, const char *who, const ResidentView &v);
+// waits for the device; LJMD_ERR_RANGE while the sticky word is set; words [2][max_lag + 1][3] or NULL
+int tcf_fetch(TcfState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *words, int64_t *counts,
+              int64_t *n_snapshots);
+int tcf_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *msd, double *vacf, int64_t *counts,
+             int64_t *n_snapshots);
+int tcf_reset(TcfState *st, std::string *err, const char *who, const ResidentView &v);
+int tcf_profile_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms,
+                     int32_t *origins_live);
+// ljmd_set_state: the stored origins are dropped and the numbering restarts; sums and counts stay
+void tcf_new_trajectory(TcfState *st);
+void tcf_release(TcfState *st, hipStream_t stream);
+
+}  // namespace ljmdt
+
+namespace ljmds {
+
+using ljmdh::ResidentView;
+
+struct StressState {
+    int max_snapshots = 0;          // 0 = not configured
+    int workgroups = 0, blocks = 0; // rows of part / kpart
+    uint64_t *d_series = nullptr;   // [max_snapshots][kStressWords]
+    uint64_t *d_part = nullptr, *d_kpart = nullptr;
+    unsigned long long *d_pcount = nullptr, *d_count = nullptr;
+    unsigned *d_pflag = nullptr, *d_kflag = nullptr;
+    int32_t *d_range = nullptr;
+    double *d_bbox = nullptr;       // [T][kRdfBoxStride]
+    ljmdh::KernelTimer timer;
+    int64_t snapshots = 0;
+};
+
+int not_configured(std::string *err, const char *who);
+int stress_configure(StressState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_snapshots);
+int stress_accumulate(StressState *st, std::string *err, const char *who, const ResidentView &v);
+// words [snapshots][kStressWords], either pointer may be NULL; LJMD_ERR_RANGE while the sticky word is set
+int stress_fetch(StressState *st, std::string *err, const char *who, const ResidentView &v, int64_t *words, int64_t *n_snapshots);
+int stress_read(StressState *st, std::string *err, const char *who, const ResidentView &v, double *p, int64_t *n_snapshots);
+int stress_reset(StressState *st, std::string *err, const char *who, const ResidentView &v);
+int stress_profile_read(StressState *st, std::string *err, const char *who, const ResidentView &v, int64_t *visited,
+                        int64_t *total, double *kernel_ms);
+void stress_release(StressState *st, hipStream_t stream);
+
+}  // namespace ljmds
+#endif

@@ -102,8 +102,7 @@ void release(ljmd_t *h)
     if (!h) return;
     if (h->device >= 0) (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    ljmdr::rdf_release(&h->rdf, h->stream);
-    ljmdt::tcf_release(&h->tcf, h->stream);
+    release_resident(h);
     if (h->comm_stream) (void)hipStreamSynchronize(h->comm_stream);
     if (h->comm) (void)ncclCommDestroy(h->comm);
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);

@@ -1,5 +1,6 @@
 // ljmd_stress.h -- pressure tensor of the system resident on the single / sharded engine (include/ljmd.h:
-// ljmd_stress_*): argument blocks of the three kernels of ljmd_stress.hip and the host core of ljmd_stress.cpp.
+// ljmd_stress_*): argument blocks of the three kernels of ljmd_stress.hip and the conversion of a snapshot's words.  The
+// host side is ljmd_resident.h.
 //
 // The layout is the engine's (ljmd_internal.h): exchange buffer pos[G][3][P], velocities v[3][P] of the own block,
 // 64-slot tiles, TB tiles per rank block, T = G TB tiles, NaN positions and zero velocities on the padding slots.
@@ -61,43 +62,6 @@ hipError_t launch_stress_pairs(const StressPairArgs &a, dim3 grid, hipStream_t s
 hipError_t launch_stress_kinetic(const StressKineticArgs &a, hipStream_t s);
 hipError_t launch_stress_fold(const StressFoldArgs &a, hipStream_t s);
 
-// ---- host core (ljmd_stress.cpp): knows nothing of struct ljmd ----
-
-struct StressView {
-    int n = 0, P = 0, TB = 0, T = 0, G = 1, rank = 0;
-    double L = 0, invL = 0, rc2 = 0;
-    const double *pos = nullptr;    // exchange buffer
-    const double *v = nullptr;      // [3][P]
-    hipStream_t stream = nullptr;
-    bool compact = false;           // coordinate spread < 2.4 L
-    std::optional<int> walk_chunk;  // LJMD_WALK_CHUNK as the handle read it (Knobs::walk_chunk)
-};
-
-struct StressState {
-    int max_snapshots = 0;          // 0 = not configured
-    int workgroups = 0, blocks = 0; // rows of part / kpart
-    uint64_t *d_series = nullptr;   // [max_snapshots][kStressWords]
-    uint64_t *d_part = nullptr, *d_kpart = nullptr;
-    unsigned long long *d_pcount = nullptr, *d_count = nullptr;
-    unsigned *d_pflag = nullptr, *d_kflag = nullptr;
-    int32_t *d_range = nullptr;
-    double *d_bbox = nullptr;       // [T][kRdfBoxStride]
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // around the launches of the most recent accumulate
-    bool timed = false;
-    int64_t snapshots = 0;
-};
-
-// All return an LJMD_* code and leave a message in *err (and in the thread's last error).  `who` = the public name.
-int stress_configure(StressState *st, std::string *err, const char *who, const StressView &v, int32_t max_snapshots);
-int stress_accumulate(StressState *st, std::string *err, const char *who, const StressView &v);
-// words [snapshots][kStressWords], either pointer may be NULL; LJMD_ERR_RANGE while the sticky word is set
-int stress_fetch(StressState *st, std::string *err, const char *who, const StressView &v, int64_t *words, int64_t *n_snapshots);
-int stress_read(StressState *st, std::string *err, const char *who, const StressView &v, double *p, int64_t *n_snapshots);
-int stress_reset(StressState *st, std::string *err, const char *who, const StressView &v);
-int stress_profile_read(StressState *st, std::string *err, const char *who, const StressView &v, int64_t *visited,
-                        int64_t *total, double *kernel_ms);
-// frees everything after what may still use it; the state is "not configured" afterwards
-void stress_release(StressState *st, hipStream_t stream);
 // p[c] = (R(K[c]) + 12 R(S[c])) / ((L L) L) of one snapshot's words (inline: the batch engine's read uses it too)
 inline void stress_doubles(const int64_t *words, double L, double *out6)
 {

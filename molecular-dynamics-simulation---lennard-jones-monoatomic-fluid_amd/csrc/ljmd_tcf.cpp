@@ -1,10 +1,7 @@
-// ljmd_tcf.cpp -- host side of the MSD / VACF accumulation of the system resident on a one-rank engine (include/ljmd.h:
-// ljmd_tcf_*; kernels: ljmd_tcf.hip).  Two layers, as in ljmd_rdf.cpp: the core (namespace ljmdt), which sees an engine
-// only through TcfView and links without anything of struct ljmd (tests/tcf_host), and the C entry points, which run the
-// entry checks and build the view.
-#include "ljmd_tcf.h"
-
-#include "ljmd_common.h"
+// ljmd_tcf.cpp -- host core of the MSD / VACF accumulation of the system resident on a one-rank engine (kernels:
+// ljmd_tcf.hip): guards, sizes, argument blocks, launches, reads and resets.  It sees an engine only through ResidentView
+// and links without anything of struct ljmd (tests/tcf_host); the C entry points are in ljmd_resident.cpp.
+#include "ljmd_resident.h"
 #include "ljmd_tcf_host.h"
 
 #include <algorithm>
@@ -17,28 +14,23 @@ namespace ljmdt {
 
 namespace {
 
-int tfail(std::string *err, int code, const char *fmt, ...)
+// the buffers of a state in the order they are allocated; the sizes and the ring's name matter to configure only
+std::array<DeviceBuffer, 6> buffers(TcfState *st, const TcfSizes &z = {}, const char *ring = "")
 {
-    va_list ap;
-    va_start(ap, fmt);
-    failv(err, code, fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-#define TCF_HIP(err, call)                                                                                          \
-    do {                                                                                                            \
-        hipError_t e_ = (call);                                                                                     \
-        if (e_ != hipSuccess)                                                                                       \
-            return tfail((err), LJMD_ERR_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-    } while (0)
-
-int not_configured(std::string *err, const char *who)
-{
-    return tfail(err, LJMD_ERR_STATE, "%s: MSD / VACF is not configured (call ljmd_tcf_configure first)", who);
+    return {{{(void **)&st->d_sums, z.sums_bytes, "the sums"},
+             {(void **)&st->d_range, sizeof(int32_t), "the range word"},
+             {(void **)&st->d_cur, z.cur_bytes, "the current snapshot"},
+             {(void **)&st->d_part, z.part_bytes, "the partial sums"},
+             {(void **)&st->d_flag, z.flag_bytes, "the range flags"},
+             {(void **)&st->d_ring, z.ring_bytes, ring}}};
 }
 
 }  // namespace
+
+int not_configured(std::string *err, const char *who)
+{
+    return fail(err, LJMD_ERR_STATE, "%s: MSD / VACF is not configured (call ljmd_tcf_configure first)", who);
+}
 
 TcfSizes tcf_sizes(int n, int max_lag, int stride)
 {
@@ -68,61 +60,46 @@ TcfSlices tcf_plan_slices(int nblk, int n_live)
 
 void tcf_release(TcfState *st, hipStream_t stream)
 {
-    void *bufs[] = {st->d_cur, st->d_ring, st->d_part, st->d_flag, st->d_range, st->d_sums};
-    bool any = false;
-    for (void *p : bufs) any = any || p;
-    if (stream && any) (void)hipStreamSynchronize(stream);
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    if (st->ev0) (void)hipEventDestroy(st->ev0);
-    if (st->ev1) (void)hipEventDestroy(st->ev1);
+    free_buffers(buffers(st), stream);
+    st->timer.destroy();
     *st = {};
 }
 
 void tcf_new_trajectory(TcfState *st) { st->s = 0; }     // the window of a snapshot follows from s: no origin is live
 
-int tcf_configure(TcfState *st, std::string *err, const char *who, const TcfView &v, int32_t max_lag, int32_t origin_stride)
+int tcf_configure(TcfState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_lag, int32_t origin_stride)
 {
     static_assert(kTcfMaxLag == LJMD_TCF_MAX_LAG && kTcfMaxOrigins == LJMD_TCF_MAX_ORIGINS,
                   "MSD / VACF limits out of sync with include/ljmd.h");
     if (max_lag < 0 || max_lag > kTcfMaxLag)
-        return tfail(err, LJMD_ERR_INVALID_ARG, "%s: max_lag = %d outside 1..%d (0 switches MSD / VACF off)", who, max_lag,
-                     kTcfMaxLag);
-    if (max_lag > 0 && origin_stride < 1) return tfail(err, LJMD_ERR_INVALID_ARG, "%s: origin_stride must be >= 1", who);
+        return fail(err, LJMD_ERR_INVALID_ARG, "%s: max_lag = %d outside 1..%d (0 switches MSD / VACF off)", who, max_lag,
+                    kTcfMaxLag);
+    if (max_lag > 0 && origin_stride < 1) return fail(err, LJMD_ERR_INVALID_ARG, "%s: origin_stride must be >= 1", who);
     if (max_lag > 0 && max_lag / origin_stride + 1 > kTcfMaxOrigins)
-        return tfail(err, LJMD_ERR_INVALID_ARG, "%s: max_lag / origin_stride + 1 = %d exceeds LJMD_TCF_MAX_ORIGINS (%d)", who,
-                     max_lag / origin_stride + 1, kTcfMaxOrigins);
+        return fail(err, LJMD_ERR_INVALID_ARG, "%s: max_lag / origin_stride + 1 = %d exceeds LJMD_TCF_MAX_ORIGINS (%d)", who,
+                    max_lag / origin_stride + 1, kTcfMaxOrigins);
     if (max_lag > 0 && (v.multi || v.G != 1))
-        return tfail(err, LJMD_ERR_INVALID_ARG, "%s: n_ranks = %d%s: MSD / VACF of the resident system needs a one-rank "
-                                                "engine (ljmd_create with n_ranks = 1)", who, v.G,
-                     v.multi ? " (multi-device handle)" : "");
+        return fail(err, LJMD_ERR_INVALID_ARG, "%s: n_ranks = %d%s: MSD / VACF of the resident system needs a one-rank "
+                                               "engine (ljmd_create with n_ranks = 1)", who, v.G,
+                    v.multi ? " (multi-device handle)" : "");
     if (max_lag > 0 && (v.n < 1 || (size_t)v.n > kTcfMaxN || v.P < v.n))
-        return tfail(err, LJMD_ERR_INVALID_ARG, "%s: n = %d outside 1..%zu", who, v.n, kTcfMaxN);
+        return fail(err, LJMD_ERR_INVALID_ARG, "%s: n = %d outside 1..%zu", who, v.n, kTcfMaxN);
     tcf_release(st, v.stream);
     if (max_lag == 0) return LJMD_OK;
     const TcfSizes z = tcf_sizes(v.n, max_lag, origin_stride);
     char ring[48];
     std::snprintf(ring, sizeof ring, "the origin ring (%d slots)", z.slots);
+    const auto bufs = buffers(st, z, ring);
     auto body = [&]() -> int {
         try {
             st->counts.assign((size_t)max_lag + 1, 0);
         } catch (const std::bad_alloc &) {
-            return tfail(err, LJMD_ERR_ALLOC, "%s: out of host memory for the counts", who);
+            return fail(err, LJMD_ERR_ALLOC, "%s: out of host memory for the counts", who);
         }
-        void **bufs[6] = {(void **)&st->d_sums, (void **)&st->d_range, (void **)&st->d_cur, (void **)&st->d_part,
-                          (void **)&st->d_flag, (void **)&st->d_ring};
-        const size_t sizes[6] = {z.sums_bytes, sizeof(int32_t), z.cur_bytes, z.part_bytes, z.flag_bytes, z.ring_bytes};
-        const char *names[6] = {"the sums", "the range word", "the current snapshot", "the partial sums", "the range flags", ring};
-        for (int k = 0; k < 6; ++k)
-            if (hipMalloc(bufs[k], sizes[k]) != hipSuccess) {
-                *bufs[k] = nullptr;
-                (void)hipGetLastError();
-                return tfail(err, LJMD_ERR_ALLOC, "%s: out of device memory for %s (%zu bytes)", who, names[k], sizes[k]);
-            }
-        TCF_HIP(err, hipEventCreate(&st->ev0));
-        TCF_HIP(err, hipEventCreate(&st->ev1));
+        LJMD_TRY(alloc_buffers(err, who, bufs));
+        LJMD_HIP(err, st->timer.create());
         // the padding of cur and of the ring is zeroed here and never written; part and flag are written before read
-        for (int k = 0; k < 6; ++k) TCF_HIP(err, hipMemsetAsync(*bufs[k], 0, sizes[k], v.stream));
+        for (const DeviceBuffer &b : bufs) LJMD_HIP(err, hipMemsetAsync(*b.p, 0, b.bytes, v.stream));
         return LJMD_OK;
     };
     const int rc_ = body();
@@ -137,18 +114,18 @@ int tcf_configure(TcfState *st, std::string *err, const char *who, const TcfView
     return LJMD_OK;
 }
 
-int tcf_accumulate(TcfState *st, std::string *err, const char *who, const TcfView &v)
+int tcf_accumulate(TcfState *st, std::string *err, const char *who, const ResidentView &v)
 {
     if (st->max_lag == 0) return not_configured(err, who);
     if (v.n != st->n || !v.ru || !v.v || !v.perm)
-        return tfail(err, LJMD_ERR_STATE, "%s: the engine is not the one MSD / VACF was configured for", who);
+        return fail(err, LJMD_ERR_STATE, "%s: the engine is not the one MSD / VACF was configured for", who);
     const TcfWindow w = tcf_window(st->s, st->max_lag, st->stride, st->sz.slots);
     TcfGatherArgs ga{};
     ga.ru = v.ru; ga.v = v.v; ga.perm = v.perm;
     ga.cur = st->d_cur;
     ga.store = w.store_slot >= 0 ? st->d_ring + (size_t)w.store_slot * 6 * st->sz.n_pad : nullptr;
     ga.n = v.n; ga.P = v.P; ga.n_pad = st->sz.n_pad;
-    TCF_HIP(err, hipEventRecord(st->ev0, v.stream));
+    LJMD_HIP(err, st->timer.start(v.stream));
     hipError_t e = launch_tcf_gather(ga, v.stream);
     if (e == hipSuccess && w.n_live > 0) {
         const TcfSlices p = tcf_plan_slices(st->sz.nblk, w.n_live);
@@ -166,9 +143,8 @@ int tcf_accumulate(TcfState *st, std::string *err, const char *who, const TcfVie
         e = launch_tcf_terms(ta, v.stream);
         if (e == hipSuccess) e = launch_tcf_fold(fa, v.stream);
     }
-    if (e != hipSuccess) return tfail(err, LJMD_ERR_HIP, "%s: MSD / VACF launch failed: %s", who, hipGetErrorString(e));
-    TCF_HIP(err, hipEventRecord(st->ev1, v.stream));
-    st->timed = true;
+    if (e != hipSuccess) return fail(err, LJMD_ERR_HIP, "%s: MSD / VACF launch failed: %s", who, hipGetErrorString(e));
+    LJMD_HIP(err, st->timer.stop(v.stream));
     st->last_live = w.n_live;
     tcf_count(w, st->stride, st->counts.data());
     ++st->s;
@@ -176,24 +152,24 @@ int tcf_accumulate(TcfState *st, std::string *err, const char *who, const TcfVie
     return LJMD_OK;
 }
 
-int tcf_fetch(TcfState *st, std::string *err, const char *who, const TcfView &v, uint64_t *words, int64_t *counts,
+int tcf_fetch(TcfState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *words, int64_t *counts,
               int64_t *n_snapshots)
 {
     if (st->max_lag == 0) return not_configured(err, who);
     int32_t range = 0;
-    TCF_HIP(err, hipMemcpyAsync(&range, st->d_range, sizeof range, hipMemcpyDeviceToHost, v.stream));
-    if (words) TCF_HIP(err, hipMemcpyAsync(words, st->d_sums, st->sz.sums_bytes, hipMemcpyDeviceToHost, v.stream));
-    TCF_HIP(err, hipStreamSynchronize(v.stream));
+    LJMD_HIP(err, hipMemcpyAsync(&range, st->d_range, sizeof range, hipMemcpyDeviceToHost, v.stream));
+    if (words) LJMD_HIP(err, hipMemcpyAsync(words, st->d_sums, st->sz.sums_bytes, hipMemcpyDeviceToHost, v.stream));
+    LJMD_HIP(err, hipStreamSynchronize(v.stream));
     // the handle is not poisoned: the trajectory itself is sound
     if (range != 0)
-        return tfail(err, LJMD_ERR_RANGE, "%s: an MSD or VACF term was not finite or |term| >= 2^40 and entered as 0; the "
-                                          "flag stays until ljmd_tcf_reset", who);
+        return fail(err, LJMD_ERR_RANGE, "%s: an MSD or VACF term was not finite or |term| >= 2^40 and entered as 0; the "
+                                         "flag stays until ljmd_tcf_reset", who);
     if (counts) std::copy(st->counts.begin(), st->counts.end(), counts);
     if (n_snapshots) *n_snapshots = st->snapshots;
     return LJMD_OK;
 }
 
-int tcf_read(TcfState *st, std::string *err, const char *who, const TcfView &v, double *msd, double *vacf, int64_t *counts,
+int tcf_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *msd, double *vacf, int64_t *counts,
              int64_t *n_snapshots)
 {
     if (st->max_lag == 0) return not_configured(err, who);
@@ -202,7 +178,7 @@ int tcf_read(TcfState *st, std::string *err, const char *who, const TcfView &v, 
         try {
             w.resize(st->sz.sums_bytes / sizeof(uint64_t));
         } catch (const std::bad_alloc &) {
-            return tfail(err, LJMD_ERR_ALLOC, "%s: out of host memory", who);
+            return fail(err, LJMD_ERR_ALLOC, "%s: out of host memory", who);
         }
     }
     LJMD_TRY(tcf_fetch(st, err, who, v, w.empty() ? nullptr : w.data(), counts, n_snapshots));
@@ -217,117 +193,26 @@ int tcf_read(TcfState *st, std::string *err, const char *who, const TcfView &v, 
     return LJMD_OK;
 }
 
-int tcf_reset(TcfState *st, std::string *err, const char *who, const TcfView &v)
+int tcf_reset(TcfState *st, std::string *err, const char *who, const ResidentView &v)
 {
     if (st->max_lag == 0) return not_configured(err, who);
-    TCF_HIP(err, hipMemsetAsync(st->d_sums, 0, st->sz.sums_bytes, v.stream));
-    TCF_HIP(err, hipMemsetAsync(st->d_range, 0, sizeof(int32_t), v.stream));
+    LJMD_HIP(err, hipMemsetAsync(st->d_sums, 0, st->sz.sums_bytes, v.stream));
+    LJMD_HIP(err, hipMemsetAsync(st->d_range, 0, sizeof(int32_t), v.stream));
     std::fill(st->counts.begin(), st->counts.end(), 0);
     st->s = 0;
     st->snapshots = 0;
     return LJMD_OK;
 }
 
-int tcf_profile_read(TcfState *st, std::string *err, const char *who, const TcfView &v, double *kernel_ms,
+int tcf_profile_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms,
                      int32_t *origins_live)
 {
     if (st->max_lag == 0) return not_configured(err, who);
     float ms = 0.0f;
-    if (st->timed) {
-        TCF_HIP(err, hipStreamSynchronize(v.stream));
-        TCF_HIP(err, hipEventElapsedTime(&ms, st->ev0, st->ev1));
-    }
+    LJMD_HIP(err, st->timer.elapsed_ms(v.stream, &ms));
     if (kernel_ms) *kernel_ms = (double)ms;
-    if (origins_live) *origins_live = st->timed ? st->last_live : 0;
+    if (origins_live) *origins_live = st->timer.timed ? st->last_live : 0;
     return LJMD_OK;
 }
 
 }  // namespace ljmdt
-
-// ---- C ABI: compiled with the engine; the host test links the core alone (tests/tcf_host: -DLJMD_TCF_CORE_ONLY) ----
-#ifndef LJMD_TCF_CORE_ONLY
-
-#include "ljmd_engine.h"
-
-namespace {
-
-using ljmdt::TcfView;
-
-TcfView view_of(const ljmd_t *h)
-{
-    TcfView v;
-    v.n = h->n; v.P = h->plan.P; v.G = h->G;
-    v.multi = h->multi != nullptr;
-    v.ru = h->d_ru; v.v = h->d_v; v.perm = h->d_perm;
-    v.stream = h->stream;
-    return v;
-}
-
-// the start of every entry point but configure: a handle, and the feature configured on it (a rank engine and a
-// multi-device handle never are)
-int configured(ljmd_t *h, const char *who)
-{
-    LJMD_TRY(entry_checks(h, who, kHandle));
-    if (h->tcf.max_lag == 0)
-        return fail(h, LJMD_ERR_STATE, "%s: MSD / VACF is not configured (call ljmd_tcf_configure first)", who);
-    return LJMD_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ljmd_tcf_configure(ljmd_t *h, int32_t max_lag, int32_t origin_stride)
-{
-    static const char *who = "ljmd_tcf_configure";
-    LJMD_TRY(entry_checks(h, who, kHandle));
-    if (!h->multi) LJMD_HIP(h, hipSetDevice(h->device));
-    return ljmdt::tcf_configure(&h->tcf, &h->err, who, view_of(h), max_lag, origin_stride);
-}
-
-int ljmd_tcf_accumulate(ljmd_t *h)
-{
-    static const char *who = "ljmd_tcf_accumulate";
-    LJMD_TRY(configured(h, who));
-    LJMD_TRY(entry_checks(h, who, kHaveState | kHaveAccel | kNotPoisoned));
-    if (h->step_open || h->forces_pending)
-        return fail(h, LJMD_ERR_STATE, "%s: inside a split-phase step (call ljmd_step_finish first)", who);
-    LJMD_HIP(h, hipSetDevice(h->device));
-    return ljmdt::tcf_accumulate(&h->tcf, &h->err, who, view_of(h));
-}
-
-int ljmd_tcf_read(ljmd_t *h, double *msd, double *vacf, int64_t *counts, int64_t *n_snapshots)
-{
-    static const char *who = "ljmd_tcf_read";
-    LJMD_TRY(configured(h, who));
-    LJMD_HIP(h, hipSetDevice(h->device));
-    return ljmdt::tcf_read(&h->tcf, &h->err, who, view_of(h), msd, vacf, counts, n_snapshots);
-}
-
-int ljmd_tcf_read_exact(ljmd_t *h, int64_t *words, int64_t *counts, int64_t *n_snapshots)
-{
-    static const char *who = "ljmd_tcf_read_exact";
-    LJMD_TRY(configured(h, who));
-    LJMD_HIP(h, hipSetDevice(h->device));
-    return ljmdt::tcf_fetch(&h->tcf, &h->err, who, view_of(h), reinterpret_cast<uint64_t *>(words), counts, n_snapshots);
-}
-
-int ljmd_tcf_reset(ljmd_t *h)
-{
-    static const char *who = "ljmd_tcf_reset";
-    LJMD_TRY(configured(h, who));
-    LJMD_HIP(h, hipSetDevice(h->device));
-    return ljmdt::tcf_reset(&h->tcf, &h->err, who, view_of(h));
-}
-
-int ljmd_tcf_profile_read(ljmd_t *h, double *kernel_ms, int32_t *origins_live)
-{
-    static const char *who = "ljmd_tcf_profile_read";
-    LJMD_TRY(configured(h, who));
-    LJMD_HIP(h, hipSetDevice(h->device));
-    return ljmdt::tcf_profile_read(&h->tcf, &h->err, who, view_of(h), kernel_ms, origins_live);
-}
-
-}  // extern "C"
-
-#endif  // LJMD_TCF_CORE_ONLY

@@ -10,7 +10,7 @@
 // LJMD_ERR_ALLOC branch of configure is not reached here.)
 #include "ljmd.h"
 #include "ljmd_common.h"
-#include "ljmd_rdf.h"
+#include "ljmd_resident.h"
 
 #include <algorithm>
 #include <cmath>
@@ -81,9 +81,9 @@ hipError_t launch_rdf_pairs(const RdfPairArgs &a, dim3 grid, hipStream_t)
 
 namespace {
 
-RdfView view_for(int n, int G, int rank, std::vector<double> &pos)
+ResidentView view_for(int n, int G, int rank, std::vector<double> &pos)
 {
-    RdfView v;
+    ResidentView v;
     v.n = n; v.G = G; v.rank = rank;
     v.S = n / G;
     v.P = (v.S + 255) / 256 * 256;
@@ -100,7 +100,7 @@ RdfView view_for(int n, int G, int rank, std::vector<double> &pos)
 void guards_and_sequences()
 {
     std::vector<double> pos;
-    const RdfView v = view_for(1000, 1, 0, pos);
+    const ResidentView v = view_for(1000, 1, 0, pos);
     RdfState st;
     std::string err;
     uint64_t hist[64];
@@ -154,7 +154,7 @@ void guards_and_sequences()
     check(rdf_read(&st, &err, who, v, hist, &snaps) == LJMD_OK && snaps == 0 && hist[0] == 0 && hist[63] == 0, "reset zeroes");
 
     // not compact: nothing may be skipped
-    RdfView loose = v;
+    ResidentView loose = v;
     loose.compact = false;
     check(rdf_accumulate(&st, &err, who, loose) == LJMD_OK && g_last.skip == 0, "positions not compact: skip off");
 
@@ -162,13 +162,13 @@ void guards_and_sequences()
     check(rdf_configure(&st, &err, who, v, 16, 2.0) == LJMD_OK && st.nbins == 16 && st.snapshots == 0, "reconfigure");
     check(rdf_read(&st, &err, who, v, hist, &snaps) == LJMD_OK && snaps == 0 && hist[0] == 0 && hist[15] == 0, "reconfigure zeroes");
     check(rdf_configure(&st, &err, who, v, 0, 0.0) == LJMD_OK && st.nbins == 0 && !st.d_hist && !st.d_bbox && !st.d_count &&
-              !st.ev0 && !st.ev1, "off frees");
+              !st.timer.ev0 && !st.timer.ev1, "off frees");
     check(rdf_accumulate(&st, &err, who, v) == LJMD_ERR_STATE && rdf_read(&st, &err, who, v, hist, &snaps) == LJMD_ERR_STATE,
           "off: as before configure");
 
     // a rank engine: ordered walk over all column tiles
     std::vector<double> pos4;
-    const RdfView rv = view_for(4096, 4, 2, pos4);
+    const ResidentView rv = view_for(4096, 4, 2, pos4);
     check(rdf_configure(&st, &err, who, rv, 8192, 3.0) == LJMD_OK, "configure on a rank view");
     check(rdf_accumulate(&st, &err, who, rv) == LJMD_OK && g_last.G == 4 && g_last.rank == 2 && g_last.U == rv.T &&
               g_last.TB == rv.TB, "rank view: arguments");
@@ -312,13 +312,13 @@ void walk_enumeration()
     check(rdf_plan_walk(132, 132, 1, 0).chunk == 1 && rdf_plan_walk(132, 132, 1, -5).chunk == 1 &&
               rdf_plan_walk(132, 132, 1, 1000).chunk == 67 && rdf_plan_walk(132, 132, 1, 1000).slices == 1,
           "walk: a request is clamped to [1, U]");
-    // from the environment to the launch: read_knobs -> (the handle's Knobs) -> RdfView -> the grid of rdf_accumulate
+    // from the environment to the launch: read_knobs -> (the handle's Knobs) -> ResidentView -> the grid of rdf_accumulate
     setenv("LJMD_WALK_CHUNK", "65", 1);
     const std::optional<int> knob = ljmdh::read_knobs().walk_chunk;
     unsetenv("LJMD_WALK_CHUNK");
     check(knob && *knob == 65 && !ljmdh::read_knobs().walk_chunk, "walk: read_knobs reads LJMD_WALK_CHUNK, unset is unset");
     std::vector<double> pos;
-    RdfView v = view_for(8200, 1, 0, pos);
+    ResidentView v = view_for(8200, 1, 0, pos);
     v.walk_chunk = knob;
     RdfState st;
     std::string err;

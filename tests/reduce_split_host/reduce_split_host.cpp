@@ -116,8 +116,7 @@ hipError_t launch_gather_perm(const int *, int *, const int *, int, hipStream_t 
 
 }  // namespace ljmdk
 
-namespace ljmdr { void rdf_release(RdfState *, hipStream_t) {} }
-namespace ljmdt { void tcf_release(TcfState *, hipStream_t) {} }
+namespace ljmdh { void release_resident(ljmd_t *) {} }
 
 namespace {
 

@@ -10,7 +10,7 @@
 // (The fake hipMalloc cannot fail, so the LJMD_ERR_ALLOC branch of configure is not reached here.)
 #include "ljmd.h"
 #include "ljmd_internal.h"
-#include "ljmd_stress.h"
+#include "ljmd_resident.h"
 
 #include <algorithm>
 #include <cmath>
@@ -270,9 +270,9 @@ System make_system(int n, int G, int TB, double L, double rc, unsigned seed)
     return s;
 }
 
-StressView view_of(const System &s, int rank, bool compact = true)
+ResidentView view_of(const System &s, int rank, bool compact = true)
 {
-    StressView v;
+    ResidentView v;
     v.n = s.n; v.P = s.P; v.TB = s.TB; v.T = s.G * s.TB; v.G = s.G; v.rank = rank;
     v.L = s.L; v.invL = 1.0 / s.L; v.rc2 = s.rc * s.rc;
     v.pos = s.pos.data();
@@ -303,7 +303,7 @@ void brute(const System &s, int i0, int i1, uint64_t (&row)[12][3], bool &bad)
 void guards_and_sequences()
 {
     const System s = make_system(300, 1, 8, 10.0, 2.5, 1);
-    const StressView v = view_of(s, 0);
+    const ResidentView v = view_of(s, 0);
     StressState st;
     std::string err;
     std::vector<int64_t> words(4 * kStressWords, -1);
@@ -327,7 +327,7 @@ void guards_and_sequences()
           "max_snapshots < 0");
     check(stress_configure(&st, &err, who, v, kStressMaxSnapshots + 1) == LJMD_ERR_INVALID_ARG && has(err, "max_snapshots = 262145"),
           "max_snapshots too large");
-    StressView big = v;
+    ResidentView big = v;
     big.n = kStressMaxN + 1;
     check(stress_configure(&st, &err, who, big, 4) == LJMD_ERR_INVALID_ARG && has(err, "caller: n = 8388609 outside 1..8388608"), "n too large");
     check(st.max_snapshots == 0 && !st.d_series && !st.d_part && !st.d_bbox, "refused configure allocates nothing");
@@ -396,7 +396,7 @@ void guards_and_sequences()
     // reconfigure empties, off frees
     check(stress_configure(&st, &err, who, v, 2) == LJMD_OK && st.max_snapshots == 2 && st.snapshots == 0, "reconfigure");
     check(stress_configure(&st, &err, who, v, 0) == LJMD_OK && st.max_snapshots == 0 && !st.d_series && !st.d_part && !st.d_kpart &&
-              !st.d_bbox && !st.ev0 && !st.ev1, "off frees");
+              !st.d_bbox && !st.timer.ev0 && !st.timer.ev1, "off frees");
     check(stress_accumulate(&st, &err, who, v) == LJMD_ERR_STATE && stress_fetch(&st, &err, who, v, nullptr, nullptr) == LJMD_ERR_STATE,
           "off: as before configure");
     check(stress_configure(&st, &err, who, v, 2) == LJMD_OK && stress_accumulate(&st, &err, who, v) == LJMD_OK, "configured again");
@@ -412,7 +412,7 @@ void walks_against_brute_force()
     const Case cases[] = {{200, 5, 2.5}, {256, 4, 4.9}, {130, 3, 1.2}, {64, 1, 4.9}, {2, 1, 4.9}};
     for (const Case &c : cases) {
         const System s = make_system(c.n, 1, c.TB, 10.0, c.rc, 100 + c.n);
-        const StressView v = view_of(s, 0);
+        const ResidentView v = view_of(s, 0);
         StressState st;
         std::string err;
         uint64_t want[12][3];
@@ -440,7 +440,7 @@ void plans_under_an_override()
             const std::vector<double> pos((size_t)G * 3 * P, NAN), vel((size_t)3 * P, 0.0);
             const int asked[] = {1, 2, 63, 64, 65, U - 1, U, U + 7};
             for (int chunk : asked) {
-                StressView v;
+                ResidentView v;
                 v.n = T * 64; v.P = P; v.TB = TB; v.T = T; v.G = G; v.rank = G - 1;
                 v.L = 10.0; v.invL = 0.1; v.rc2 = 6.25;
                 v.pos = pos.data();
@@ -460,7 +460,7 @@ void plans_under_an_override()
                 check(stress_profile_read(&st, &err, "o", v, &vis, &tot, nullptr) == LJMD_OK && vis == st.workgroups &&
                           tot == 2 * (int64_t)st.workgroups, "override: the fold reads one row per workgroup");
                 // a view with another value of the knob is another plan: refused, unless the grid happens to be the same
-                StressView other = v;
+                ResidentView other = v;
                 other.walk_chunk = std::nullopt;
                 const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(TB, T, G, std::nullopt);
                 StressState st2;
@@ -483,7 +483,7 @@ void rank_partials()
     bool bad = false;
     brute(s, 0, s.n, all, bad);
     for (int g = 0; g < G; ++g) {
-        const StressView v = view_of(s, g);
+        const ResidentView v = view_of(s, g);
         StressState st;
         std::string err;
         uint64_t want[12][3];
@@ -508,7 +508,7 @@ void range_flag()
     System s = make_system(128, 1, 2, 10.0, 2.5, 9);
     for (int k = 0; k < 3; ++k) s.pos[(size_t)k * s.P + 1] = s.pos[(size_t)k * s.P] + (k == 0 ? 0.05 : 0.0);
     for (int k = 0; k < 3; ++k) s.xyz[3 + k] = s.pos[(size_t)k * s.P + 1];
-    const StressView v = view_of(s, 0);
+    const ResidentView v = view_of(s, 0);
     StressState st;
     std::string err;
     uint64_t want[12][3];

@@ -9,7 +9,7 @@
 // cannot fail, so the LJMD_ERR_ALLOC branch of configure is not reached here.)
 #include "ljmd.h"
 #include "ljmd_internal.h"
-#include "ljmd_tcf.h"
+#include "ljmd_resident.h"
 
 #include <algorithm>
 #include <cmath>
@@ -184,9 +184,9 @@ struct Sys {
     {
         std::iota(perm.begin(), perm.end(), 0);
     }
-    TcfView view() const
+    ResidentView view() const
     {
-        TcfView w;
+        ResidentView w;
         w.n = n; w.P = P; w.G = 1;
         w.ru = ru.data(); w.v = v.data(); w.perm = perm.data();
         return w;
@@ -310,7 +310,7 @@ void guards_and_sequences()
 {
     Sys y(1000);
     y.advance(true);
-    const TcfView v = y.view();
+    const ResidentView v = y.view();
     TcfState st;
     g_st = &st;
     std::string err;
@@ -335,11 +335,11 @@ void guards_and_sequences()
     check(tcf_configure(&st, &err, who, v, 3, 0) == LJMD_ERR_INVALID_ARG && has(err, "caller: origin_stride must be >= 1"), "stride 0");
     check(tcf_configure(&st, &err, who, v, 512, 1) == LJMD_ERR_INVALID_ARG && has(err, "= 513 exceeds LJMD_TCF_MAX_ORIGINS (512)"), "too many origins");
     check(tcf_configure(&st, &err, who, v, 1024, 2) == LJMD_ERR_INVALID_ARG && has(err, "exceeds LJMD_TCF_MAX_ORIGINS"), "too many origins, stride 2");
-    TcfView rank = v;
+    ResidentView rank = v;
     rank.G = 2;
     check(tcf_configure(&st, &err, who, rank, 4, 1) == LJMD_ERR_INVALID_ARG && has(err, "caller: n_ranks = 2") &&
               has(err, "needs a one-rank engine"), "a rank engine is refused");
-    TcfView multi = v;
+    ResidentView multi = v;
     multi.multi = true; multi.G = 2; multi.ru = multi.v = nullptr; multi.perm = nullptr;
     check(tcf_configure(&st, &err, who, multi, 4, 1) == LJMD_ERR_INVALID_ARG && has(err, "n_ranks") && has(err, "multi-device"),
           "a multi-device handle is refused");
@@ -406,7 +406,7 @@ void guards_and_sequences()
 
     // reconfigure zeroes, off frees
     check(tcf_configure(&st, &err, who, v, 3, 1) == LJMD_OK && st.max_lag == 3 && st.snapshots == 0 && st.s == 0 && st.sz.slots == 4, "reconfigure");
-    check(tcf_configure(&st, &err, who, v, 0, 0) == LJMD_OK && st.max_lag == 0 && !st.d_ring && !st.d_cur && !st.d_sums && !st.ev0 && !st.ev1,
+    check(tcf_configure(&st, &err, who, v, 0, 0) == LJMD_OK && st.max_lag == 0 && !st.d_ring && !st.d_cur && !st.d_sums && !st.timer.ev0 && !st.timer.ev1,
           "off frees");
     check(tcf_accumulate(&st, &err, who, v) == LJMD_ERR_STATE && tcf_reset(&st, &err, who, v) == LJMD_ERR_STATE, "off: as before configure");
     check(tcf_configure(&st, &err, who, v, 2, 1) == LJMD_OK, "configure again");
