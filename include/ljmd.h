@@ -552,6 +552,70 @@ int ljmd_stress_reset(ljmd_t *h);
 int ljmd_stress_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *tile_pairs_total, double *kernel_ms);
 int ljmd_stress_from_exact(const int64_t *words /* [12][3] */, double box_length, double *out6);
 
+/*
+ * Heat flux of the resident system, one snapshot per call, recorded where r and v live (ljmd_heatflux_*): no snapshot
+ * leaves the device.  Its autocorrelation is the Green-Kubo integrand of the thermal conductivity.  One-rank engines
+ * only (ljmd_create with n_ranks = 1); n <= 2^23.
+ *
+ * Definition.  One snapshot is 9 signed 192-bit integers, E[3] then P[3] then C[3] with axes x, y, z, each three int64
+ * limbs, least significant first (the layout of ljmd_stress_read_exact): 216 bytes.  All arithmetic is unfused, left
+ * to right, and a term t enters its integer as Q(t) = RNE(t 2^64).
+ *   Convective part: for every particle k2 = vx*vx + vy*vy + vz*vz of the resident velocities and the terms k2*vx,
+ *   k2*vy, k2*vz, entering E[a].
+ *   Pair parts, over the ORDERED pairs i != j of the wrapped positions resident now; the minimum image and the pair
+ *   arithmetic are those of ljmd_stress_* above, word for word:
+ *     d0 = x_i - x_j ; d = d0 - L * round(d0 * invL) (half away from zero) per axis ; r2 = dx*dx + dy*dy + dz*dz ;
+ *     if r2 < rc2 (strict): u = 1.0 / r2 ; u3 = u*u*u ; u6 = u3*u3 ; mdu = 2.0*u6 - u3 ; fx = mdu*dx*u, fy, fz likewise;
+ *     wx = vx_i + vx_j, wy, wz likewise ; phi = u6 - u3 ; g = fx*wx + fy*wy + fz*wz ;
+ *     potential terms phi*wx, phi*wy, phi*wz entering P[a]; collisional terms g*dx, g*dy, g*dz entering C[a].
+ *   Under i <-> j w, r2 and phi keep their bits, every d, every f and g change sign exactly: all six terms are the same
+ *   from both sides, so an unordered pair may be evaluated once and added twice -- the integer is the same.
+ *   Range: a pair is out of range when any of fx, fy, fz, u6, wx, wy, wz, g or of its six terms is not finite or has
+ *   |t| >= 2^40; all six of its terms then enter as 0 and a sticky word is set.  The same holds for a particle's k2 and
+ *   its three terms.  An arithmetic flag: nothing wraps, nothing faults.
+ *   Doubles: j[a] = (0.5 * R(E[a]) + R(P[a]) + 6.0 * R(C[a])) / V with V = (L*L)*L and R(x) = RNE(x) 2^-64, ONE rounding
+ *   of each integer; parts[p][a] holds the three summands, each divided by V, in the order convective, potential,
+ *   collisional -- the host-only ljmd_heatflux_from_exact(words[9][3], L, j[3], parts[3][3] or NULL).
+ *   Where the factors come from.  The Irving-Kirkwood flux of a pair potential is
+ *     J V = sum_i e_i v_i + 1/2 sum_{i != j} (F_ij . v_i) r_ij ,   e_i = 1/2 v_i^2 + 1/2 sum_{j != i} phi_ij ,
+ *   with phi_ij = 4 (u6 - u3), F_ij = 24 f (the force on i from j) and r_ij = d.  The kinetic energies give 1/2 E.  The
+ *   potential energies give 1/2 sum_{i != j} 4 phi v_i; phi is symmetric, so v_i may be replaced by (v_i + v_j) / 2:
+ *   1/4 * 4 = 1 times P.  In the last sum (F_ij . v_i) r_ij and (F_ji . v_j) r_ji = (F_ij . v_j) r_ij are the two
+ *   orders of one pair, so v_i may be replaced by (v_i + v_j) / 2 as well: 1/4 * 24 = 6 times C.  No tail correction:
+ *   ljmd_set_tail_corrections does not apply.  No enthalpy term: a one-component system at zero total momentum needs
+ *   none.
+ * The integers depend on the particle set alone: not on slot order, re-sorts, tiling, precision mode or knobs.
+ * configure: 1 <= max_snapshots <= LJMD_HEATFLUX_MAX_SNAPSHOTS and n <= 2^23; allocates and zeroes the series on the
+ * device; calling it again reconfigures and zeroes; 0 switches the feature off and frees it.  A failed guard returns
+ * LJMD_ERR_INVALID_ARG and leaves the earlier configuration in place; a failed allocation LJMD_ERR_ALLOC with the
+ * feature off.  Works with or without a state.  On a rank engine (n_ranks > 1) or a multi-device handle
+ * (ljmd_create_multi) configure with max_snapshots > 0 returns LJMD_ERR_INVALID_ARG ("... n_ranks = <G>: a pair term
+ * needs the velocities of both particles and a rank holds only its own ..."), and the other five calls LJMD_ERR_STATE
+ * ("not configured").  ljmd_set_state, the other setters, ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_* and ljmd_migrate leave
+ * configuration and series alone, and it leaves theirs alone.
+ * accumulate: appends one snapshot, stream-ordered on the engine's stream behind everything enqueued so far
+ * (ljmd_enqueue_steps* included), no host wait.  Guards and their order are those of ljmd_stress_accumulate:
+ * LJMD_ERR_STATE before configure, without a state, without valid accelerations, on a poisoned handle and between
+ * ljmd_step_begin and ljmd_step_finish; then LJMD_ERR_STATE when the series is full, before anything is launched.  It
+ * reads the exchange buffer and the velocities and writes only buffers of its own: r, ru, v, a, the step records, the
+ * other three observables and every later result stay bitwise what they are without the call.
+ * read_exact / read: wait for the device; words[n][9][3] (read_exact) or j[n][3] and parts[n][3][3] (read) for the n
+ * snapshots taken since configure / reset, and n -- any pointer may be NULL; they clear nothing.  While the sticky word
+ * is set they return LJMD_ERR_RANGE, until ljmd_heatflux_reset; the handle is not poisoned and stepping is unaffected.
+ * reset: empties the series and clears the sticky word.
+ * profile_read, for the most recent accumulate (zeros before the first): the tile pairs its walk evaluated, those it
+ * considered, and the time of its launches from HIP events, as ljmd_stress_profile_read; any pointer may be NULL.
+ * read_exact, read, reset and profile_read return LJMD_ERR_STATE before configure.
+ */
+#define LJMD_HEATFLUX_MAX_SNAPSHOTS 262144
+int ljmd_heatflux_configure(ljmd_t *h, int32_t max_snapshots);
+int ljmd_heatflux_accumulate(ljmd_t *h);
+int ljmd_heatflux_read_exact(ljmd_t *h, int64_t *words /* [n][9][3] */, int64_t *n_snapshots);
+int ljmd_heatflux_read(ljmd_t *h, double *j /* [n][3] */, double *parts /* [n][3][3], may be NULL */, int64_t *n_snapshots);
+int ljmd_heatflux_reset(ljmd_t *h);
+int ljmd_heatflux_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *tile_pairs_total, double *kernel_ms);
+int ljmd_heatflux_from_exact(const int64_t *words /* [9][3] */, double box_length, double *j3, double *parts9 /* may be NULL */);
+
 /* ---- batch engine: many independent small systems on one device ------------------------------------------------
  *
  * One ljmd_batch_t holds B replicas on one device -- the ensemble runs of the reference's run-many framework

@@ -144,6 +144,13 @@ PROTOTYPES = {
     "ljmd_stress_reset": (C.c_int, [C.c_void_p]),
     "ljmd_stress_profile_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_double_p]),
     "ljmd_stress_from_exact": (C.c_int, [c_int64_p, C.c_double, c_double_p]),
+    "ljmd_heatflux_configure": (C.c_int, [C.c_void_p, C.c_int32]),
+    "ljmd_heatflux_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_heatflux_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ljmd_heatflux_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int64_p]),
+    "ljmd_heatflux_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_heatflux_profile_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_double_p]),
+    "ljmd_heatflux_from_exact": (C.c_int, [c_int64_p, C.c_double, c_double_p, c_double_p]),
     "ljmd_batch_rdf_configure": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     "ljmd_batch_rdf_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_batch_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
@@ -168,6 +175,7 @@ BATCH_TCF_MAX_ORIGINS = 512
 TCF_MAX_LAG = 4096
 TCF_MAX_ORIGINS = 512
 STRESS_MAX_SNAPSHOTS = 262144
+HEATFLUX_MAX_SNAPSHOTS = 262144
 BATCH_STRESS_MAX_SNAPSHOTS = 262144
 
 _lib = None

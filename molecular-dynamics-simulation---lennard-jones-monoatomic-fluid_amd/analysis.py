@@ -150,3 +150,23 @@ def viscosity_green_kubo(acf, dt_sample: float, V: float, T: float) -> np.ndarra
     run = np.zeros_like(acf)
     run[1:] = np.cumsum(0.5 * (acf[1:] + acf[:-1]) * dt_sample)
     return (V / T) * run
+
+
+def heat_flux_acf(j, max_lag=None, origin_stride: int = 1) -> np.ndarray:
+    """j [n_snap, 3]: a heat-flux series (Engine.heatflux_read) -> the time-origin average of J(0) . J(tau) / 3 at
+    max_lag + 1 lags.  Formula, origin convention and counts are those of compute_vacf_tau_timeorig with the three
+    components as the velocity of one particle."""
+    j = np.asarray(j, dtype=np.float64)
+    if j.ndim != 2 or j.shape[1] != 3:
+        raise ValueError(f"heat_flux_acf: j must have shape (n_snap, 3), got {j.shape}")
+    jx, jy, jz = (j[:, c][:, None] for c in range(3))
+    return compute_vacf_tau_timeorig(jx, jy, jz, max_lag, origin_stride) / 3.0
+
+
+def thermal_conductivity_green_kubo(acf, dt_sample: float, V: float, T: float) -> np.ndarray:
+    """Green-Kubo running thermal conductivity lambda(tau) = V / T^2 * integral_0^tau acf, the integral by the trapezoid
+    rule on the sampling grid (lambda[0] = 0); reduced units (k_B = 1)."""
+    acf = np.asarray(acf, dtype=np.float64)
+    run = np.zeros_like(acf)
+    run[1:] = np.cumsum(0.5 * (acf[1:] + acf[:-1]) * dt_sample)
+    return (V / (T * T)) * run

@@ -225,6 +225,8 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     // pressure tensor (ljmd_stress_*, core ljmd_stress.cpp); a multi-device parent keeps only max_snapshots and the
     // snapshot count here
     ljmds::StressState stress;
+    // heat flux (ljmd_heatflux_*, core ljmd_heatflux.cpp): one-rank engines only
+    ljmdq::HeatfluxState heatflux;
     bool step_open = false;           // between ljmd_step_begin and ljmd_step_finish (split-phase API)
 
     bool profiling = false;
@@ -250,7 +252,7 @@ IntegrateArgs integrate_args(ljmd_t *h);
 // the caller releases whatever exists
 int allocate_engine(ljmd_t *h);
 void release(ljmd_t *h);
-// what ljmd_rdf_configure, ljmd_tcf_configure and ljmd_stress_configure allocated; the engine's device is current
+// what ljmd_rdf_configure, ljmd_tcf_configure, ljmd_stress_configure and ljmd_heatflux_configure allocated; the engine's device is current
 // (ljmd_resident.cpp; called by release)
 void release_resident(ljmd_t *h);
 // HBM -> host of any of r, ru, v, a (dsts[3 w + k], NULL = skip) and of the last n_records scalar records

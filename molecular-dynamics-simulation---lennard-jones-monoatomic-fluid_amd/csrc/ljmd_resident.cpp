@@ -1,8 +1,9 @@
-// ljmd_resident.cpp -- the C entry points of the three observables of the system resident on the single / sharded
-// engine (include/ljmd.h: ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_*) and the release of what they allocated.  Each runs the
-// entry checks, builds the view of the engine and calls the observable's core (ljmd_rdf.cpp, ljmd_tcf.cpp,
-// ljmd_stress.cpp); g(r) and the pressure tensor dispatch a multi-device parent to its rank engines.  MSD / VACF takes
-// one-rank engines only: its core refuses every other handle at configure, so a parent never has it configured.
+// ljmd_resident.cpp -- the C entry points of the four observables of the system resident on the single / sharded
+// engine (include/ljmd.h: ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_*, ljmd_heatflux_*) and the release of what they
+// allocated.  Each runs the entry checks, builds the view of the engine and calls the observable's core (ljmd_rdf.cpp,
+// ljmd_tcf.cpp, ljmd_stress.cpp, ljmd_heatflux.cpp); g(r) and the pressure tensor dispatch a multi-device parent to its
+// rank engines.  MSD / VACF and the heat flux take one-rank engines only: their cores refuse every other handle at
+// configure, so a parent never has them configured.
 #include "ljmd_engine.h"
 #include "ljmd_multi.h"
 
@@ -24,7 +25,7 @@ ResidentView view_of(const ljmd_t *h)
     return v;
 }
 
-// one of the three: whether it is configured on a handle, and the failure where it is not
+// one of the four: whether it is configured on a handle, and the failure where it is not
 struct Observable {
     bool (*configured)(const ljmd_t *h);
     int (*not_configured)(std::string *err, const char *who);
@@ -32,6 +33,7 @@ struct Observable {
 const Observable kRdf = {[](const ljmd_t *h) { return h->rdf.nbins != 0; }, ljmdr::not_configured};
 const Observable kTcf = {[](const ljmd_t *h) { return h->tcf.max_lag != 0; }, ljmdt::not_configured};
 const Observable kStress = {[](const ljmd_t *h) { return h->stress.max_snapshots != 0; }, ljmds::not_configured};
+const Observable kHeatflux = {[](const ljmd_t *h) { return h->heatflux.max_snapshots != 0; }, ljmdq::not_configured};
 
 // a handle, and the observable configured on it
 int configured(ljmd_t *h, const char *who, const Observable &o)
@@ -133,6 +135,7 @@ void ljmdh::release_resident(ljmd_t *h)
     ljmdr::rdf_release(&h->rdf, h->stream);
     ljmdt::tcf_release(&h->tcf, h->stream);
     ljmds::stress_release(&h->stress, h->stream);
+    ljmdq::heatflux_release(&h->heatflux, h->stream);
 }
 
 extern "C" {
@@ -355,6 +358,56 @@ int ljmd_stress_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *ti
     }
     LJMD_TRY(configured(h, who, kStress));
     return profile_read_ranks(h, ljmd_stress_profile_read, tile_pairs_visited, tile_pairs_total, kernel_ms);
+}
+
+// ---- heat flux -------------------------------------------------------------
+// one-rank engines only, as MSD / VACF: the core refuses every other handle at configure
+
+int ljmd_heatflux_configure(ljmd_t *h, int32_t max_snapshots)
+{
+    static const char *who = "ljmd_heatflux_configure";
+    LJMD_TRY(entry_checks(h, who, kHandle));
+    if (!h->multi) LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdq::heatflux_configure(&h->heatflux, &h->err, who, view_of(h), max_snapshots);
+}
+
+int ljmd_heatflux_accumulate(ljmd_t *h)
+{
+    static const char *who = "ljmd_heatflux_accumulate";
+    LJMD_TRY(accumulate_checks(h, who, kHeatflux));
+    return ljmdq::heatflux_accumulate(&h->heatflux, &h->err, who, view_of(h));
+}
+
+int ljmd_heatflux_read_exact(ljmd_t *h, int64_t *words, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_heatflux_read_exact";
+    LJMD_TRY(configured(h, who, kHeatflux));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdq::heatflux_fetch(&h->heatflux, &h->err, who, view_of(h), words, n_snapshots);
+}
+
+int ljmd_heatflux_read(ljmd_t *h, double *j, double *parts, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_heatflux_read";
+    LJMD_TRY(configured(h, who, kHeatflux));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdq::heatflux_read(&h->heatflux, &h->err, who, view_of(h), j, parts, n_snapshots);
+}
+
+int ljmd_heatflux_reset(ljmd_t *h)
+{
+    static const char *who = "ljmd_heatflux_reset";
+    LJMD_TRY(configured(h, who, kHeatflux));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdq::heatflux_reset(&h->heatflux, &h->err, who, view_of(h));
+}
+
+int ljmd_heatflux_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *tile_pairs_total, double *kernel_ms)
+{
+    static const char *who = "ljmd_heatflux_profile_read";
+    LJMD_TRY(configured(h, who, kHeatflux));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdq::heatflux_profile_read(&h->heatflux, &h->err, who, view_of(h), tile_pairs_visited, tile_pairs_total, kernel_ms);
 }
 
 }  // extern "C"

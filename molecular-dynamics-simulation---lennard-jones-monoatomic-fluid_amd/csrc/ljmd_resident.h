@@ -1,13 +1,15 @@
-// ljmd_resident.h -- host side of the three observables of the system resident on the single / sharded engine: g(r)
-// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp) and the pressure tensor (ljmd_stress.cpp).  What the three cores share --
-// the view through which they see an engine, their named device buffers, the timer around one accumulate -- and each
-// core's state and functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host,
-// tests/tcf_host, tests/stress_host); every C entry point that takes a handle is in ljmd_resident.cpp.  Host code only:
-// the kernels' side is ljmd_rdf.h, ljmd_tcf.h and ljmd_stress.h.
+// ljmd_resident.h -- host side of the four observables of the system resident on the single / sharded engine: g(r)
+// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp), the pressure tensor (ljmd_stress.cpp) and the heat flux
+// (ljmd_heatflux.cpp).  What the cores share -- the view through which they see an engine, their named device buffers,
+// the timer around one accumulate -- and each core's state and functions.  A core knows nothing of struct ljmd and links
+// without the engine (tests/rdf_host, tests/tcf_host, tests/stress_host, tests/heatflux_host); every C entry point that
+// takes a handle is in ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_tcf.h, ljmd_stress.h
+// and ljmd_heatflux.h.
 #ifndef LJMD_RESIDENT_H
 #define LJMD_RESIDENT_H
 
 #include "ljmd_common.h"
+#include "ljmd_heatflux.h"
 #include "ljmd_rdf.h"
 #include "ljmd_stress.h"
 #include "ljmd_tcf.h"
@@ -214,4 +216,37 @@ int stress_profile_read(StressState *st, std::string *err, const char *who, cons
 void stress_release(StressState *st, hipStream_t stream);
 
 }  // namespace ljmds
+
+namespace ljmdq {
+
+using ljmdh::ResidentView;
+
+struct HeatfluxState {
+    int max_snapshots = 0;          // 0 = not configured
+    int workgroups = 0, blocks = 0; // rows of part / kpart
+    uint64_t *d_series = nullptr;   // [max_snapshots][kHeatfluxWords]
+    uint64_t *d_part = nullptr, *d_kpart = nullptr;
+    unsigned long long *d_pcount = nullptr, *d_count = nullptr;
+    unsigned *d_pflag = nullptr, *d_kflag = nullptr;
+    int32_t *d_range = nullptr;
+    double *d_bbox = nullptr;       // [T][kRdfBoxStride]
+    ljmdh::KernelTimer timer;
+    int64_t snapshots = 0;
+};
+
+int not_configured(std::string *err, const char *who);
+// refuses a multi-device handle and a rank engine of G > 1 itself
+int heatflux_configure(HeatfluxState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_snapshots);
+int heatflux_accumulate(HeatfluxState *st, std::string *err, const char *who, const ResidentView &v);
+// words [snapshots][kHeatfluxWords], either pointer may be NULL; LJMD_ERR_RANGE while the sticky word is set
+int heatflux_fetch(HeatfluxState *st, std::string *err, const char *who, const ResidentView &v, int64_t *words, int64_t *n_snapshots);
+// j [snapshots][3], parts [snapshots][3][3], any pointer may be NULL
+int heatflux_read(HeatfluxState *st, std::string *err, const char *who, const ResidentView &v, double *j, double *parts,
+                  int64_t *n_snapshots);
+int heatflux_reset(HeatfluxState *st, std::string *err, const char *who, const ResidentView &v);
+int heatflux_profile_read(HeatfluxState *st, std::string *err, const char *who, const ResidentView &v, int64_t *visited,
+                          int64_t *total, double *kernel_ms);
+void heatflux_release(HeatfluxState *st, hipStream_t stream);
+
+}  // namespace ljmdq
 #endif

@@ -31,6 +31,8 @@ module ljmd_c_api
   public :: ljmd_tcf_configure, ljmd_tcf_accumulate, ljmd_tcf_read, ljmd_tcf_read_exact, ljmd_tcf_reset, ljmd_tcf_profile_read
   public :: ljmd_stress_configure, ljmd_stress_accumulate, ljmd_stress_read, ljmd_stress_read_exact, ljmd_stress_reset
   public :: ljmd_stress_profile_read, ljmd_stress_from_exact, ljmd_time_origin_average
+  public :: ljmd_heatflux_configure, ljmd_heatflux_accumulate, ljmd_heatflux_read, ljmd_heatflux_read_exact
+  public :: ljmd_heatflux_reset, ljmd_heatflux_profile_read, ljmd_heatflux_from_exact
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_stress_configure, ljmd_batch_stress_accumulate, ljmd_batch_stress_read, ljmd_batch_stress_read_exact
@@ -46,6 +48,7 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_ORIGINS = 512
   integer(c_int32_t), parameter, public :: LJMD_STRESS_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_STRESS_MAX_SNAPSHOTS = 262144
+  integer(c_int32_t), parameter, public :: LJMD_HEATFLUX_MAX_SNAPSHOTS = 262144
 
   interface
     function ljmd_compute_lj_potential_energy(n, box_length, rc, rx, ry, rz, ax, ay, az, &
@@ -461,6 +464,59 @@ module ljmd_c_api
     function ljmd_stress_from_exact(words, box_length, out6) bind(C, name="ljmd_stress_from_exact") result(status)
       import :: c_int, c_double, c_ptr
       type(c_ptr), value :: words, out6
+      real(c_double), value :: box_length
+      integer(c_int) :: status
+    end function
+
+    ! heat flux of the system resident on a one-rank engine handle (ljmd.h: ljmd_heatflux_*); j = c_loc of
+    ! [3, n_snapshots] doubles, parts = c_loc of [3 axes, 3 parts, n_snapshots] doubles (convective, potential,
+    ! collisional), words = c_loc of [3, 9, n_snapshots] 64-bit words in Fortran order; c_null_ptr skips an output
+    function ljmd_heatflux_configure(handle, max_snapshots) bind(C, name="ljmd_heatflux_configure") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_heatflux_accumulate(handle) bind(C, name="ljmd_heatflux_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_heatflux_read(handle, j, parts, n_snapshots) bind(C, name="ljmd_heatflux_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, j, parts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_heatflux_read_exact(handle, words, n_snapshots) bind(C, name="ljmd_heatflux_read_exact") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_heatflux_reset(handle) bind(C, name="ljmd_heatflux_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_heatflux_profile_read(handle, tile_pairs_visited, tile_pairs_total, kernel_ms) &
+        bind(C, name="ljmd_heatflux_profile_read") result(status)
+      import :: c_int, c_int64_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: tile_pairs_visited, tile_pairs_total
+      real(c_double), intent(out) :: kernel_ms
+      integer(c_int) :: status
+    end function
+
+    ! host only: one snapshot's words [3, 9] -> j[3] and, unless c_null_ptr, parts [3 axes, 3 parts]
+    function ljmd_heatflux_from_exact(words, box_length, j3, parts9) bind(C, name="ljmd_heatflux_from_exact") result(status)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: words, j3, parts9
       real(c_double), value :: box_length
       integer(c_int) :: status
     end function

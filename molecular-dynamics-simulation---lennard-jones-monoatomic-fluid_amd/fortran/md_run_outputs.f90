@@ -10,6 +10,8 @@
 !   md_simulation_gpu (ljmd_tcf_*) and md_simulation_many_gpu (ljmd_batch_tcf_*).
 !   <dir>/pressure_tensor_gpu.dat, <dir>/stress_acf_gpu.dat: the pressure tensor md_simulation_gpu recorded on the device
 !   (ljmd_stress_*) and its Green-Kubo autocorrelations (write_pressure_tensor_file, write_stress_acf_file).
+!   <dir>/heat_flux_gpu.dat, <dir>/heat_flux_acf_gpu.dat: the heat flux md_simulation_gpu recorded on the device
+!   (ljmd_heatflux_*) and its Green-Kubo autocorrelation (write_heat_flux_file, write_heat_flux_acf_file).
 !==============================================================================
 module md_run_outputs
   use, intrinsic :: iso_c_binding, only: c_int64_t
@@ -19,6 +21,7 @@ module md_run_outputs
   implicit none
   private
   public :: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, write_stress_acf_file
+  public :: write_heat_flux_file, write_heat_flux_acf_file
 
 contains
 
@@ -189,6 +192,45 @@ contains
     end do
     close(iu_a)
   end subroutine write_stress_acf_file
+
+  ! heat_flux_gpu.dat: per sampling instant its time, J_x, J_y, J_z and the nine parts (ljmd_heatflux_read: convective
+  ! x y z, potential x y z, collisional x y z, each over V); times(k) is the time of snapshot k
+  subroutine write_heat_flux_file(filename, n_snapshots, times, j, parts)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: n_snapshots
+    real(kind=dp_kind), intent(in) :: times(n_snapshots), j(3, n_snapshots), parts(3, 3, n_snapshots)
+    integer :: iu_j, ierr, k
+    open(newunit=iu_j, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_heat_flux_file(): cannot open heat_flux_gpu.dat.'
+    write(iu_j, '(a)') '# time   J_x   J_y   J_z   conv_x   conv_y   conv_z   pot_x   pot_y   pot_z   coll_x   coll_y   coll_z'
+    do k = 1, n_snapshots
+      write(iu_j, '(es24.16e3,12(2x,es24.16e3))') times(k), j(:, k), parts(:, :, k)
+    end do
+    close(iu_j)
+  end subroutine write_heat_flux_file
+
+  ! heat_flux_acf_gpu.dat: per lag, lag, tau = lag * output_interval * dt, the autocorrelation <J(0) . J(tau)> / 3 and the
+  ! running Green-Kubo thermal conductivity lambda(tau) = V / T^2 * trapezoid integral of the ACF up to tau, with the
+  ! run's mean temperature (k_B = 1)
+  subroutine write_heat_flux_acf_file(filename, max_lag, output_interval, dt, volume, temperature, acf)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: max_lag
+    integer(kind=int_kind), intent(in) :: output_interval
+    real(kind=dp_kind), intent(in) :: dt, volume, temperature
+    real(kind=dp_kind), intent(in) :: acf(0:max_lag)
+    real(kind=dp_kind) :: h, run
+    integer :: iu_a, ierr, lag
+    open(newunit=iu_a, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_heat_flux_acf_file(): cannot open heat_flux_acf_gpu.dat.'
+    write(iu_a, '(a)') '# lag   tau   ACF_J   lambda'
+    h = dble(output_interval) * dt
+    run = 0.d0
+    do lag = 0, max_lag
+      if (lag > 0) run = run + 0.5d0 * (acf(lag) + acf(lag - 1)) * h
+      write(iu_a, '(i0,3(2x,es24.16e3))') lag, dble(lag) * h, acf(lag), (volume / (temperature * temperature)) * run
+    end do
+    close(iu_a)
+  end subroutine write_heat_flux_acf_file
 
   subroutine write_curve(filename, header, errmsg, lag_max, c, cn)
     character(len=*), intent(in) :: filename, header, errmsg

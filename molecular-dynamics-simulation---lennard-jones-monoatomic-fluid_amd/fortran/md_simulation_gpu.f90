@@ -32,7 +32,13 @@
 ! many sampling instants, lag, tau, the time-origin averaged shear and normal-difference autocorrelations --
 ! ljmd_time_origin_average on the series as the velocity of one particle, each divided by its three components -- and the
 ! running Green-Kubo viscosities V / <T> times their trapezoid integrals; every other output file is the same with and
-! without it).
+! without it), LJMD_HEATFLUX (default 0 = off; 1: the heat flux of the resident system is recorded on the device --
+! ljmd_heatflux_* -- at the same sampling instants, and outputs/one_run/heat_flux_gpu.dat gets the time, J_x, J_y, J_z
+! and the nine parts (convective, potential, collisional, x y z each) of every instant; with LJMD_HEATFLUX_MAX_LAG > 0
+! outputs/one_run/heat_flux_acf_gpu.dat also gets, per lag up to that many sampling instants, lag, tau, the time-origin
+! averaged <J(0) . J(tau)> / 3 -- ljmd_time_origin_average on the series as the velocity of one particle -- and the
+! running Green-Kubo thermal conductivity V / <T>^2 times its trapezoid integral; one-rank engines only: with
+! LJMD_GPUS > 1 the program stops before an engine is created; every other output file is the same with and without it).
 !==============================================================================
 program md_simulation_gpu
   use, intrinsic :: iso_c_binding
@@ -43,7 +49,7 @@ program md_simulation_gpu
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
   use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
-                              write_stress_acf_file
+                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file
   implicit none
 
   type(sim_params) :: params
@@ -76,6 +82,12 @@ program md_simulation_gpu
   real(c_double), allocatable, target :: stress_p(:, :), stress_times(:)   ! [6, snapshots], [snapshots]
   real(c_double), allocatable, target :: stress_c(:, :), stress_shear(:), stress_normal(:)
   integer(c_int64_t) :: stress_snapshots
+  logical :: heatflux_on
+  integer :: heatflux_max_lag, heatflux_lags
+  real(c_double), allocatable, target :: heatflux_j(:, :), heatflux_parts(:, :, :)     ! [3, snapshots], [3, 3, snapshots]
+  real(c_double), allocatable, target :: heatflux_times(:)
+  real(c_double), allocatable, target :: heatflux_c(:, :), heatflux_acf(:)
+  integer(c_int64_t) :: heatflux_snapshots
   real(kind=dp_kind) :: mean_temp, std_temp
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
@@ -121,11 +133,20 @@ program md_simulation_gpu
   call get_environment_variable('LJMD_STRESS_MAX_LAG', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) stress_max_lag
   if (stress_max_lag < 0) stop 'md_simulation: LJMD_STRESS_MAX_LAG must be >= 0.'
+  heatflux_on = .false.
+  call get_environment_variable('LJMD_HEATFLUX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) heatflux_on = trim(env) /= '0'
+  heatflux_max_lag = 0
+  call get_environment_variable('LJMD_HEATFLUX_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) heatflux_max_lag
+  if (heatflux_max_lag < 0) stop 'md_simulation: LJMD_HEATFLUX_MAX_LAG must be >= 0.'
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
   if (n_gpus > 1 .and. tcf_max_lag > 0) &
     error stop 'md_simulation: LJMD_TCF_MAX_LAG needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
+  if (n_gpus > 1 .and. heatflux_on) &
+    error stop 'md_simulation: LJMD_HEATFLUX needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1) then
     allocate(device_list(n_gpus))
     device_list = [(int(k - 1, c_int32_t), k = 1, n_gpus)]
@@ -154,6 +175,14 @@ program md_simulation_gpu
     if (n_snapshots_expected > LJMD_STRESS_MAX_SNAPSHOTS) stop 'md_simulation: more sampling instants than LJMD_STRESS_MAX_SNAPSHOTS.'
     call ljmd_check(ljmd_stress_configure(engine, int(n_snapshots_expected, c_int32_t)), engine, 'ljmd_stress_configure')
     allocate(stress_times(n_snapshots_expected))
+  end if
+  if (heatflux_on) then
+    n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
+    if (n_snapshots_expected < 1) stop 'md_simulation: LJMD_HEATFLUX needs at least one sampling instant.'
+    if (n_snapshots_expected > LJMD_HEATFLUX_MAX_SNAPSHOTS) &
+      stop 'md_simulation: more sampling instants than LJMD_HEATFLUX_MAX_SNAPSHOTS.'
+    call ljmd_check(ljmd_heatflux_configure(engine, int(n_snapshots_expected, c_int32_t)), engine, 'ljmd_heatflux_configure')
+    allocate(heatflux_times(n_snapshots_expected))
   end if
   ! t = 0 forces and energies (:236-243)
   call ljmd_check(ljmd_compute_forces(engine, epot, d_epot, dd_epot), engine, 'ljmd_compute_forces')
@@ -203,6 +232,10 @@ program md_simulation_gpu
       call ljmd_check(ljmd_stress_accumulate(engine), engine, 'ljmd_stress_accumulate')
       stress_times(num_samples + 1) = time
     end if
+    if (sample_now .and. heatflux_on) then
+      call ljmd_check(ljmd_heatflux_accumulate(engine), engine, 'ljmd_heatflux_accumulate')
+      heatflux_times(num_samples + 1) = time
+    end if
     count = segment_length(step)
     if (async_io .and. count > 0) call enqueue_segment(count)
     if (sample_now) then
@@ -237,6 +270,12 @@ program md_simulation_gpu
     call ljmd_check(ljmd_stress_read(engine, c_loc(stress_p), stress_snapshots), engine, 'ljmd_stress_read')
     if (stress_snapshots /= num_samples) stop 'md_simulation: the pressure tensor series and the samples disagree.'
   end if
+  if (heatflux_on) then
+    allocate(heatflux_j(3, max(num_samples, 1)), heatflux_parts(3, 3, max(num_samples, 1)))
+    call ljmd_check(ljmd_heatflux_read(engine, c_loc(heatflux_j), c_loc(heatflux_parts), heatflux_snapshots), engine, &
+                    'ljmd_heatflux_read')
+    if (heatflux_snapshots /= num_samples) stop 'md_simulation: the heat flux series and the samples disagree.'
+  end if
   call ljmd_destroy(engine)
 
   if (num_samples <= 0) stop 'md_simulation: no samples were taken (check warmup_steps/output_interval).'
@@ -269,6 +308,25 @@ program md_simulation_gpu
       call stats_mean_std(stats, Q_T, mean_temp, std_temp)
       call write_stress_acf_file('outputs/one_run/stress_acf_gpu.dat', stress_lags, output_interval, params%dt, params%volume, &
                                  mean_temp, stress_shear, stress_normal)
+    end if
+  end if
+  if (heatflux_on) then
+    call write_heat_flux_file('outputs/one_run/heat_flux_gpu.dat', int(num_samples), heatflux_times, heatflux_j, heatflux_parts)
+    if (heatflux_max_lag > 0 .and. num_samples >= 2) then
+      ! the three components as the velocity of one particle: [1, snapshots] each
+      allocate(heatflux_c(num_samples, 3))
+      heatflux_c(:, 1) = heatflux_j(1, 1:num_samples)
+      heatflux_c(:, 2) = heatflux_j(2, 1:num_samples)
+      heatflux_c(:, 3) = heatflux_j(3, 1:num_samples)
+      heatflux_lags = min(heatflux_max_lag, int(num_samples) - 1)
+      allocate(heatflux_acf(0:heatflux_lags))
+      call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(num_samples, c_int32_t), 1_c_int32_t, c_loc(heatflux_c(1, 1)), &
+                                               c_loc(heatflux_c(1, 2)), c_loc(heatflux_c(1, 3)), int(heatflux_lags, c_int32_t), &
+                                               1_c_int32_t, c_loc(heatflux_acf)), c_null_ptr, 'ljmd_time_origin_average')
+      heatflux_acf = heatflux_acf / 3.d0
+      call stats_mean_std(stats, Q_T, mean_temp, std_temp)
+      call write_heat_flux_acf_file('outputs/one_run/heat_flux_acf_gpu.dat', heatflux_lags, output_interval, params%dt, &
+                                    params%volume, mean_temp, heatflux_acf)
     end if
   end if
   write(*, '(a,i0,a,i0,a,f10.2,a,es11.4,a)') 'md_simulation_gpu: N=', params%n, ' steps=', total_steps, &

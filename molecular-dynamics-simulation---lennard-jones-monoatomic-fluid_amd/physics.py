@@ -485,6 +485,62 @@ class Engine:
         self._ck(self._lib.ljmd_stress_profile_read(self._h, C.byref(vis), C.byref(tot), C.byref(ms)))
         return {"tile_pairs_visited": vis.value, "tile_pairs_total": tot.value, "kernel_ms": ms.value}
 
+    # -- heat flux of the resident system (include/ljmd.h: ljmd_heatflux_*) -------------------
+    def heatflux_configure(self, max_snapshots: int) -> None:
+        """ljmd_heatflux_configure: room for max_snapshots snapshots of the heat flux on the device; 0 switches the
+        feature off.  The series starts empty.  One-rank engines only."""
+        if isinstance(max_snapshots, bool) or not isinstance(max_snapshots, (int, np.integer)):
+            raise TypeError(f"heatflux_configure: max_snapshots must be an integer, got {max_snapshots!r}")
+        self._ck(self._lib.ljmd_heatflux_configure(self._h, int(max_snapshots)))
+
+    def heatflux_accumulate(self) -> None:
+        """appends the heat flux of the state resident now to the series (stream-ordered: no host wait)"""
+        self._ck(self._lib.ljmd_heatflux_accumulate(self._h))
+
+    def _heatflux_count(self) -> int:
+        """snapshots in the series (ljmd_heatflux_read_exact without a buffer); raises as the reads do"""
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_heatflux_read_exact(self._h, None, C.byref(snaps)))
+        return snaps.value
+
+    def heatflux_read(self):
+        """-> (j[n_snapshots, 3], parts[n_snapshots, 3, 3]): the heat flux (1/2 sum v^2 v + sum phi w + 6 sum (f . w) d)
+        / V per snapshot and its three summands over V, parts[:, 0] convective, parts[:, 1] potential, parts[:, 2]
+        collisional; nothing is cleared."""
+        n = max(self._heatflux_count(), 1)
+        j = np.empty((n, 3), dtype=np.float64)
+        parts = np.empty((n, 3, 3), dtype=np.float64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_heatflux_read(self._h, j.ctypes.data_as(c_double_p), parts.ctypes.data_as(c_double_p),
+                                              C.byref(snaps)))
+        return j[:snaps.value].copy(), parts[:snaps.value].copy()
+
+    def heatflux_read_exact(self, raw: bool = False):
+        """-> sums[n_snapshots, 9]: the exact integer sums of Q(term) = RNE(term 2^64), E[3], P[3] then C[3], as Python
+        ints in an object array -- or, raw=True, the library's int64 words [n_snapshots, 9, 3] (three little-endian
+        limbs of a signed 192-bit integer)."""
+        words = np.empty((max(self._heatflux_count(), 1), 9, 3), dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_heatflux_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        words = words[:snaps.value].copy()
+        if raw:
+            return words
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:2], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums
+
+    def heatflux_reset(self) -> None:
+        self._ck(self._lib.ljmd_heatflux_reset(self._h))
+
+    def heatflux_profile(self) -> dict:
+        """ljmd_heatflux_profile_read for the most recent heatflux_accumulate -> {'tile_pairs_visited',
+        'tile_pairs_total', 'kernel_ms'}"""
+        vis, tot, ms = C.c_int64(), C.c_int64(), C.c_double()
+        self._ck(self._lib.ljmd_heatflux_profile_read(self._h, C.byref(vis), C.byref(tot), C.byref(ms)))
+        return {"tile_pairs_visited": vis.value, "tile_pairs_total": tot.value, "kernel_ms": ms.value}
+
     # -- measurement -----------------------------------------------------------
     def profile_enable(self, on: bool = True) -> None:
         self._ck(self._lib.ljmd_profile_enable(self._h, 1 if on else 0))
