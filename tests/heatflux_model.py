@@ -42,10 +42,11 @@ def kinetic_words(v):
     return out, bad
 
 
-def pair_words(r, v, L: float, rc: float):
+def pair_words(r, v, L: float, rc: float, want_stats: bool = True):
     """r, v [3, n] -> (P[3] + C[3] Python ints over the ordered pairs, range flag, stats).  stats, over the ordered pairs
     that entered: 'pairs' their number; 'phi' the sum of u6 - u3 (math.fsum); 'abs_P'[a] the sum of |phi w_a|;
-    'abs_C'[a] the sum of (|fx wx| + |fy wy| + |fz wz|) |d_a|, which bounds every intermediate of g d_a."""
+    'abs_C'[a] the sum of (|fx wx| + |fy wy| + |fz wz|) |d_a|, which bounds every intermediate of g d_a.  With
+    want_stats=False they are not formed (None): the integers and the flag do not depend on them."""
     x, y, z = (np.ascontiguousarray(r[k], dtype=np.float64) for k in range(3))
     vv = [np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(3, -1)[k]) for k in range(3)]
     n = x.size
@@ -78,12 +79,16 @@ def pair_words(r, v, L: float, rc: float):
             sums, bad, ok = _sum_terms(terms, f + [u6] + w + [g])
             S = [a + b for a, b in zip(S, sums)]
             flag = flag or bad
+            if not want_stats:
+                continue
             pairs += int(np.count_nonzero(ok))
             phis.append(math.fsum(phi[ok]))
             gabs = np.abs(f[0] * w[0]) + np.abs(f[1] * w[1]) + np.abs(f[2] * w[2])
             for a in range(3):
                 abs_p[a].append(math.fsum(np.abs(terms[a][ok])))
                 abs_c[a].append(math.fsum((gabs * np.abs(dd[a]))[ok]))
+    if not want_stats:
+        return S, flag, None
     stats = {"pairs": pairs, "phi": math.fsum(phis), "abs_P": [math.fsum(t) for t in abs_p],
              "abs_C": [math.fsum(t) for t in abs_c]}
     return S, flag, stats
@@ -92,7 +97,7 @@ def pair_words(r, v, L: float, rc: float):
 def words(r, v, L: float, rc: float):
     """one snapshot -> (E[3] + P[3] + C[3] as a list of 9 Python ints, range flag)"""
     E, kbad = kinetic_words(v)
-    S, sbad, _ = pair_words(r, v, L, rc)
+    S, sbad, _ = pair_words(r, v, L, rc, want_stats=False)
     return E + S, kbad or sbad
 
 

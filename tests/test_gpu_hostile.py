@@ -11,6 +11,7 @@ import functools
 import numpy as np
 import pytest
 
+import heatflux_model
 import hostile_configs as hc
 import reproducible_model as M
 import stress_model
@@ -47,6 +48,7 @@ def config(name):
         "slab_rc15": lambda: _with_rc(config("slab"), 0.15),
         "sheets_rc15": lambda: _with_rc(config("sheets"), 0.15),
         "raw_droplet_rc15": lambda: _with_rc(config("raw_droplet"), 0.15),
+        "raw_slab_rc15": lambda: _with_rc(config("raw_slab"), 0.15),
         "droplet_M": lambda: hc.droplet(hc.DROPLET_M),
         "raw_slab_M": lambda: hc.raw_images(hc.slab(hc.SLAB_M)),
         "below_n3_span": lambda: _at_span(config("droplet"), N3_SPAN, above=()),
@@ -449,8 +451,11 @@ def test_rdf_walk_counts_equal_the_oracle(oracle, name, rmax_over_L):
     assert 0 < prof["tile_pairs_visited"] < prof["tile_pairs_total"], prof
 
 
-@pytest.mark.parametrize("name", ["droplet", "slab", "sheets", "droplet_rc15", "slab_rc15", "sheets_rc15"])
+@pytest.mark.parametrize("name", ["droplet", "slab", "sheets", "droplet_rc15", "slab_rc15", "sheets_rc15", "raw_droplet_rc15",
+                                  "raw_slab_rc15"])
 def test_stress_walk_words_equal_the_model(name):
+    """the raw names: spans of 2.38 L (droplet) and 1.27, 2.35, 2.35 L (slab), below the 2.4 L at which skipping switches
+    off, so box differences approach the 2.5 L that rdf_axis_gap covers"""
     p, r, v = config(name)
     with Engine(p) as eng:
         set_state(eng, r, v)
@@ -464,6 +469,33 @@ def test_stress_walk_words_equal_the_model(name):
     assert not flag and words.shape == (1, 12)
     assert list(words[0]) == want, [c for c in range(12) if words[0][c] != want[c]]
     assert 0 < prof["tile_pairs_visited"] < prof["tile_pairs_total"], prof
+
+
+@pytest.mark.parametrize("name", ["droplet_rc15", "slab_rc15", "sheets_rc15", "raw_droplet_rc15", "raw_slab_rc15"])
+def test_heatflux_walk_words_equal_the_model(name):
+    """heatflux_pairs_kernel has its own copy of the walk and reads the velocities from the column side as well.  sheets:
+    every tile box has zero width in z and every velocity pair is still distinct.  The pressure tensor accumulated on the
+    same engine must have visited the same tile pairs: the same bound on the same boxes"""
+    p, r, v = config(name)
+    with Engine(p) as eng:
+        set_state(eng, r, v)
+        eng.compute_forces()
+        eng.heatflux_configure(1)
+        eng.heatflux_accumulate()
+        words = eng.heatflux_read_exact()
+        prof = eng.heatflux_profile()
+        eng.stress_configure(1)
+        eng.stress_accumulate()
+        sprof = eng.stress_profile()
+        st = eng.get_state(("r", "v"))
+    assert np.array_equal(np.stack(st["r"]), r) and np.array_equal(np.stack(st["v"]), v)
+    want, flag = heatflux_model.words(r, v, p.box_length, p.rc)
+    print(f"heatflux {name}: tile pairs visited {prof['tile_pairs_visited']} of {prof['tile_pairs_total']}")
+    assert not flag and words.shape == (1, 9)
+    assert list(words[0]) == want, [heatflux_model.ROWS[c] for c in range(9) if words[0][c] != want[c]]
+    assert all(w != 0 for w in want)
+    assert 0 < prof["tile_pairs_visited"] < prof["tile_pairs_total"], prof
+    assert (sprof["tile_pairs_visited"], sprof["tile_pairs_total"]) == (prof["tile_pairs_visited"], prof["tile_pairs_total"])
 
 
 # ---- h. sharded on one card --------------------------------------------------------------------------------------------

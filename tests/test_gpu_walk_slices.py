@@ -1,24 +1,32 @@
-"""-m gpu: the tile walk shared by rdf_pairs_kernel and stress_pairs_kernel beyond one step per slice.
+"""-m gpu: the tile walk of rdf_pairs_kernel, stress_pairs_kernel and heatflux_pairs_kernel beyond one step per slice.
 
-rdf_plan_walk gives every system below n ~ 16 000 slices of ONE column-tile step, so the 64-lane ballot block of the two
-kernels runs with one valid lane in every other test that pins them to a reference.  LJMD_WALK_CHUNK sets the steps per
-slice: here the blocks have many live lanes, a slice has a second block, a partial last block, the tie step and the wrap
-of the unordered walk and the own tile of the ordered walk fall into a later block -- at sizes whose exact reference is
-affordable.  Every comparison is integer equality: the g(r) counts with oracle.rdf_histogram_np, the 12 stress words
-with stress_model.words, both on the state get_state returns; one reference per state, one engine run per knob value.
+rdf_plan_walk gives every system below n ~ 16 000 slices of ONE column-tile step, so the 64-lane ballot block of the three
+kernels (each carries its own copy of the loop) runs with one valid lane in every other test that pins them to a
+reference.  LJMD_WALK_CHUNK sets the steps per slice: here the blocks have many live lanes, a slice has a second block, a
+partial last block, the tie step and the wrap of the unordered walk and the own tile of the ordered walk fall into a later
+block -- at sizes whose exact reference is affordable.  Every comparison is integer equality: the g(r) counts with
+oracle.rdf_histogram_np, the 12 stress words with stress_model.words, the 9 heat-flux words with heatflux_model.words, all
+on the state get_state returns; one reference per state, one engine run per knob value.  The heat flux exists on one-rank
+engines only (cases A and W); whenever it is measured, the pressure tensor is accumulated on the same engine and the two
+walks must have visited the same number of tile pairs: they skip by the same bound on the same boxes.
 
   case A  one rank, n = 8200: T = 132 tiles, U = 67 steps, the tie step u = 66
+  case W  one rank, n = 2100 at rc = 0.49 L: T = 36 (33 live tiles, the last with 52 particles, 3 of padding only), U = 19,
+          the tie step u = 18; one block of 19 live lanes, and slices of 7, 7 and 5 steps with the tie in the short one
   case B  devices [0, 0], n = 4400: TB = 36, T = U = 72; rank 1 meets its own tiles I >= 64 in the second block
   case C  devices [0, 0, 0, 0], n = 4096: T = U = 64, one full block and no tail
   case D  two rank engines, n = 4400, the test performing the exchange: partials that differ and add up
-and two runs at n = 131 072 with the knob unset (129 steps per slice on one rank, 64 on four), where the one-rank and the
-four-rank walk must agree with each other, with the stateless g(r) kernel and with the engine's own virial."""
+a heat-flux series across slices (the workgroups' partial rows are never cleared between accumulates), two runs at
+n = 131 072 with the knob unset (129 steps per slice on one rank, 64 on four), where the one-rank and the four-rank walk
+must agree with each other, with the stateless g(r) kernel and with the engine's own virial, and the heat flux at that size
+with the planner's slices against slices of 1 and of 64 steps."""
 import functools
 import hashlib
 
 import numpy as np
 import pytest
 
+import heatflux_model
 import stress_model
 from ljmd_amd import Engine, analysis, md_types, synthetic
 
@@ -29,7 +37,15 @@ CASES = {
     "A": dict(n=8200, devices=None, T=132, chunks=(None, 2, 33, 64, 65, 66, 67, 1000)),
     "B": dict(n=4400, devices=[0, 0], T=72, chunks=(None, 64, 65, 71, 72)),
     "C": dict(n=4096, devices=[0, 0, 0, 0], T=64, chunks=(64,)),
+    "W": dict(n=2100, devices=None, T=36, chunks=(None, 19, 7)),
 }
+WHATS = ("rdf", "stress", "heatflux")
+
+
+def _cases(cases, whats=WHATS):
+    """(case, what) pairs: the heat flux is refused on multi-device handles, so it joins the one-rank cases only"""
+    return [(c, w) for c in cases for w in whats if w != "heatflux" or CASES[c]["devices"] is None]
+
 
 # ---- states and their references --------------------------------------------------------------------------------------
 _STATES = {}
@@ -47,6 +63,14 @@ def _key(r, v, L):
 def _model_words(key, rc):
     r, v, L = _STATES[key]
     words, flag = stress_model.words(r, v, L, rc)
+    assert not flag
+    return tuple(words)
+
+
+@functools.lru_cache(maxsize=None)
+def _heatflux_words(key, rc):
+    r, v, L = _STATES[key]
+    words, flag = heatflux_model.words(r, v, L, rc)
     assert not flag
     return tuple(words)
 
@@ -105,12 +129,28 @@ def _measure(eng, what, rcut):
     eng.stress_accumulate()
     words = eng.stress_read_exact()
     assert words.shape == (1, 12)
-    return tuple(words[0]), eng.stress_profile()
+    if what == "stress":
+        return tuple(words[0]), eng.stress_profile()
+    # the heat flux beside the pressure tensor of the same state at the same rc: the two copies of the walk skip by the
+    # same bound (rc2 (1 + 1e-10), rdf_tile_gap2) on the same boxes, so they visit the same tile pairs
+    assert what == "heatflux"
+    eng.heatflux_configure(1)
+    eng.heatflux_accumulate()
+    words = eng.heatflux_read_exact()
+    assert words.shape == (1, 9)
+    prof, sprof = eng.heatflux_profile(), eng.stress_profile()
+    prof["stress_walk"] = (sprof["tile_pairs_total"], sprof["tile_pairs_visited"])
+    return tuple(words[0]), prof
+
+
+def _walks_agree(prof):
+    """the heat flux's tile-pair counts against those of the pressure tensor accumulated beside it (_measure)"""
+    return "stress_walk" not in prof or prof["stress_walk"] == (prof["tile_pairs_total"], prof["tile_pairs_visited"])
 
 
 def _want(what, r, v, L, rcut):
     key = _key(r, v, L)
-    return _oracle_hist(key, rcut) if what == "rdf" else _model_words(key, rcut)
+    return {"rdf": _oracle_hist, "stress": _model_words, "heatflux": _heatflux_words}[what](key, rcut)
 
 
 def _same(what, got, want):
@@ -141,10 +181,12 @@ def _sweep(monkeypatch, what, case, kind, rcut, steps=0, chunks=None):
             assert r1.tobytes() == r.tobytes() and v1.tobytes() == v.tobytes()
         want = _want(what, r1, v1, L, rcut)
         assert _same(what, got, want), (what, case, kind, "LJMD_WALK_CHUNK", chunk)
+        assert _walks_agree(prof), (what, case, kind, "LJMD_WALK_CHUNK", chunk, prof)
         profiles[chunk] = prof
     totals = {(q["tile_pairs_total"], q["tile_pairs_visited"]) for q in profiles.values()}
     assert len(totals) == 1, {k: (q["tile_pairs_total"], q["tile_pairs_visited"]) for k, q in profiles.items()}
     total, visited = totals.pop()
+    print("%s case %s %s rc = %.4f: tile pairs visited %d of %d" % (what, case, kind, rcut, visited, total))
     T = c["T"]
     assert total == (T * (T // 2) + T // 2 if c["devices"] is None else T * T), (total, T)
     assert 0 < visited <= total
@@ -152,16 +194,14 @@ def _sweep(monkeypatch, what, case, kind, rcut, steps=0, chunks=None):
 
 
 # ---- 1. the knob values of cases A, B, C ------------------------------------------------------------------------------
-@pytest.mark.parametrize("what", ["rdf", "stress"])
-@pytest.mark.parametrize("case", ["A", "B", "C"])
+@pytest.mark.parametrize("case, what", _cases("ABC"))
 def test_compact_state_sparse_ballots(monkeypatch, what, case):
     """rc = rmax = 2.5: the boxes keep a sparse subset of the valid lanes"""
     total, visited = _sweep(monkeypatch, what, case, "compact", 2.5)
     assert visited < total
 
 
-@pytest.mark.parametrize("what", ["rdf", "stress"])
-@pytest.mark.parametrize("case", ["A", "B", "C"])
+@pytest.mark.parametrize("case, what", _cases("ABC"))
 def test_spread_state_full_ballots(monkeypatch, what, case):
     """positions not known to be compact: nothing is skipped, every valid lane's bit is set"""
     c = CASES[case]
@@ -178,7 +218,7 @@ def test_case_b_at_a_wide_cutoff(monkeypatch, what):
     _sweep(monkeypatch, what, "B", "compact", 0.49 * L)
 
 
-@pytest.mark.parametrize("what", ["rdf", "stress"])
+@pytest.mark.parametrize("what", WHATS)
 def test_case_a_after_steps_across_re_sorts(monkeypatch, what):
     """25 steps with a re-sort every 3, then one slice of all 67 steps: the slot order is the engine's own"""
     monkeypatch.setenv("LJMD_RESORT_EVERY", "3")
@@ -186,8 +226,9 @@ def test_case_a_after_steps_across_re_sorts(monkeypatch, what):
     assert visited < total
 
 
-@pytest.mark.parametrize("what", ["rdf", "stress"])
-@pytest.mark.parametrize("case, chunks", [("A", (None, 65, 67)), ("B", (None, 65, 72))])
+@pytest.mark.parametrize("case, chunks, what", [
+    pytest.param(case, chunks, what, id="%s-chunks%d-%s" % (case, k, what))
+    for k, (case, chunks) in enumerate([("A", (None, 65, 67)), ("B", (None, 65, 72))]) for _c, what in _cases(case)])
 def test_state_spanning_a_box_face_keeps_skipping(monkeypatch, what, case, chunks):
     """raw input with a subset shifted by +L: still compact (spread ~2 L < 2.4 L), so the walk skips by boxes that span a
     face of the periodic box"""
@@ -196,6 +237,63 @@ def test_state_spanning_a_box_face_keeps_skipping(monkeypatch, what, case, chunk
     assert 1.5 * L < max(np.ptp(r[k]) for k in range(3)) < 2.4 * L
     total, visited = _sweep(monkeypatch, what, case, "face", 2.5, chunks=chunks)
     assert visited < total
+
+
+@pytest.mark.parametrize("what", ["stress", "heatflux"])
+def test_case_w_wide_cutoff_many_live_lanes(monkeypatch, what):
+    """rc = 0.49 L at n = 2100: nearly every tile pair is kept, so a block of 19 valid lanes has (nearly) 19 set bits and
+    the bit loop runs that often per ballot; with 7 steps per slice the tie step is the last of a slice of 5"""
+    L = _config(CASES["W"]["n"])[0]
+    total, visited = _sweep(monkeypatch, what, "W", "compact", 0.49 * L)
+    assert total == 36 * 18 + 18
+
+
+# ---- 1b. a heat-flux series across slices -------------------------------------------------------------------------------
+def test_heatflux_series_across_slices(monkeypatch):
+    """d_part, d_pcount and d_pflag are never cleared: every workgroup of the (row blocks, slices) grid rewrites its own
+    rows on every accumulate, also a slice in which nothing was visited.  Three accumulates 5 steps apart at 7 steps per
+    slice (slices of 7, 7 and 5 of the 19 steps) with a re-sort every 2 steps, each row against the model of its own state;
+    after a reset row 0 is the current state's; and an engine with the knob unset returns the same rows for the states"""
+    n, rc = 2100, 2.5
+    L, dt, r, v = _input(n, "compact")
+    p = md_types.init_params(n, L, dt, rc)
+    monkeypatch.setenv("LJMD_RESORT_EVERY", "2")
+    _set_chunk(monkeypatch, 7)
+    states = []
+    with Engine(p) as eng:
+        eng.set_state(r[0], r[1], r[2], v[0], v[1], v[2])
+        eng.compute_forces()
+        eng.heatflux_configure(4)
+        for k in range(3):
+            if k:
+                eng.verlet_steps(5)
+            eng.heatflux_accumulate()
+            st = eng.get_state(("r", "v"))
+            states.append((np.stack(st["r"]), np.stack(st["v"])))
+        rows = eng.heatflux_read_exact()
+        eng.heatflux_reset()
+        eng.heatflux_accumulate()
+        again = eng.heatflux_read_exact()
+        prof = eng.heatflux_profile()
+    want = [_want("heatflux", r1, v1, L, rc) for r1, v1 in states]
+    assert len(set(want)) == 3 and all(w != 0 for row in want for w in row)
+    assert rows.shape == (3, 9) and again.shape == (1, 9)
+    for k in range(3):
+        assert tuple(rows[k]) == want[k], ("LJMD_WALK_CHUNK = 7, snapshot", k)
+    assert tuple(again[0]) == want[2]
+    print("heatflux series n = %d: tile pairs visited %d of %d" % (n, prof["tile_pairs_visited"], prof["tile_pairs_total"]))
+    assert 0 < prof["tile_pairs_visited"] < prof["tile_pairs_total"] == 36 * 18 + 18
+    _set_chunk(monkeypatch, None)
+    with Engine(p) as eng:
+        eng.heatflux_configure(4)
+        for r1, v1 in states:
+            eng.set_state(r1[0], r1[1], r1[2], v1[0], v1[1], v1[2])
+            eng.compute_forces()
+            eng.heatflux_accumulate()
+        other = eng.heatflux_read_exact()
+    assert other.shape == (3, 9)
+    for k in range(3):
+        assert tuple(other[k]) == want[k], ("LJMD_WALK_CHUNK unset, snapshot", k)
 
 
 # ---- 2. case D: rank engines ------------------------------------------------------------------------------------------
@@ -324,3 +422,29 @@ def test_natural_size_rdf_against_the_stateless_kernel(monkeypatch, rmax_over_L,
         assert np.array_equal(hist, want), (name, np.flatnonzero(hist != want)[:8])
         assert prof["tile_pairs_total"] == BIG_TOTALS[name], (name, prof)
         assert 0 < prof["tile_pairs_visited"] <= prof["tile_pairs_total"]
+
+
+def test_natural_size_heatflux_across_slicings(monkeypatch):
+    """No exact model is affordable at n = 131 072, but integer sums depend on no slicing: the 9 words of the planner's own
+    8 slices of 129 steps (two full blocks and one lane) equal those of 1025 slices of one step -- the shape the small
+    systems pin to the model -- and of slices of 64 steps, whole blocks with no tail.  Three engines, one accumulate each"""
+    p, r, v = synthetic.make_config(N_BIG, seed=7000 + N_BIG)
+    p = md_types.init_params(N_BIG, p.box_length, p.dt, 2.5)
+    words, visited = {}, {}
+    for chunk in (None, 1, 64):
+        _set_chunk(monkeypatch, chunk)
+        with Engine(p) as eng:
+            eng.set_state(r[0], r[1], r[2], v[0], v[1], v[2])
+            eng.compute_forces()
+            words[chunk], prof = _measure(eng, "heatflux", p.rc)
+            st = eng.get_state(("r", "v"))
+        assert np.stack(st["r"]).tobytes() == r.tobytes() and np.stack(st["v"]).tobytes() == v.tobytes()
+        assert prof["tile_pairs_total"] == BIG_TOTALS["one"], (chunk, prof)
+        assert 0 < prof["tile_pairs_visited"] < prof["tile_pairs_total"] // 4, (chunk, prof)
+        assert _walks_agree(prof), (chunk, prof)
+        visited[chunk] = prof["tile_pairs_visited"]
+    print("heatflux n = %d: tile pairs visited %d of %d" % (N_BIG, visited[None], BIG_TOTALS["one"]))
+    assert len(words[None]) == 9 and all(w != 0 for w in words[None])
+    for chunk in (1, 64):
+        assert words[chunk] == words[None], (chunk, [c for c in range(9) if words[chunk][c] != words[None][c]])
+        assert visited[chunk] == visited[None]
