@@ -725,8 +725,8 @@ int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on);
  * Setting the mode the handle already has changes nothing.  Works on both kinds of handle. */
 int ljmd_batch_set_precision(ljmd_batch_t *h, int32_t precision_mode);
 /* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL.
- * Both include the g(r), MSD / VACF and pressure tensor launches of that call (ljmd_batch_rdf_configure /
- * ljmd_batch_tcf_configure / ljmd_batch_stress_configure with every > 0).
+ * Both include the g(r), MSD / VACF, pressure tensor and heat flux launches of that call (ljmd_batch_rdf_configure /
+ * ljmd_batch_tcf_configure / ljmd_batch_stress_configure / ljmd_batch_heatflux_configure with every > 0).
  * Replicas of different kernel classes (n <= 128, 512, 1024, 2048, 4096) run as separate groups of launches, by
  * default each on a stream of its own (LJMD_BATCH_GROUP_STREAMS=0: one after another on the handle's stream); the
  * kernel time is then the span from the first group's first launch to the last group's end, not a sum over groups,
@@ -842,6 +842,45 @@ int ljmd_batch_stress_accumulate(ljmd_batch_t *h);
 int ljmd_batch_stress_read_exact(ljmd_batch_t *h, int64_t *words /* [n][B][12][3] */, int64_t *n_snapshots);
 int ljmd_batch_stress_read(ljmd_batch_t *h, double *p /* [n][B][6] */, int64_t *n_snapshots);
 int ljmd_batch_stress_reset(ljmd_batch_t *h);
+/*
+ * Heat flux of every replica, a series of snapshots on the device (ljmd_batch_heatflux_*): the ensemble whose averaged
+ * autocorrelation is the Green-Kubo integrand of the thermal conductivity.
+ *
+ * Definition.  Per replica b one snapshot is exactly the 9 signed 192-bit integers E[3], P[3], C[3] of ljmd_heatflux_*
+ * above, for that replica's own n_b, L_b, rc_b and its resident wrapped r and v: the per-pair and per-particle
+ * arithmetic, Q(t) = RNE(t 2^64), the range rule and the limb layout are those of that comment; 216 bytes.  The integers
+ * depend on the replica's particle set alone: not on B, its slot, the other replicas, launch grouping, group streams,
+ * precision mode or the order of the particles.  The series is sample-major like the scalars of ljmd_batch_steps:
+ * words[snapshot][B][9][3], j[snapshot][B][3] and parts[snapshot][B][3][3] with (j, parts) =
+ * ljmd_heatflux_from_exact(words, L_b, ., .) per (snapshot, replica).
+ * configure: 0 <= max_snapshots <= LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS, every >= 0; max_snapshots = 0 switches the feature
+ * off and frees it; otherwise allocates and zeroes 216 B max_snapshots bytes and a sticky range word per replica;
+ * calling it again reconfigures and zeroes.  A failed guard returns LJMD_ERR_INVALID_ARG and leaves the earlier
+ * configuration in place; a failed allocation LJMD_ERR_ALLOC with the feature off.  ljmd_batch_set_state,
+ * ljmd_batch_set_precision, ljmd_batch_set_accel, ljmd_batch_set_unwrapped, ljmd_batch_set_tail_corrections, the
+ * ljmd_batch_rdf_* / ljmd_batch_tcf_* / ljmd_batch_stress_* calls and ljmd_batch_prepare leave configuration and series
+ * alone, and it leaves theirs alone; the warm-up of ljmd_batch_prepare takes no snapshot.
+ * accumulate: appends one snapshot of every replica, stream-ordered (no host wait).  LJMD_ERR_STATE before configure,
+ * before ljmd_batch_set_state, on a poisoned handle, and then when the series is full, before anything is launched.  It
+ * reads r and v and writes only its own two buffers.
+ * every > 0: ljmd_batch_steps appends the state after steps every, 2 every, ... of each call; its nsteps must then be a
+ * multiple of every (LJMD_ERR_INVALID_ARG), and a call whose snapshots do not all fit the series is refused with
+ * LJMD_ERR_STATE, both before anything is launched.  r, ru, v, a, the sampled scalars and the other three observables
+ * stay bitwise what they are without the feature; ljmd_batch_profile_read counts the new launches and their time.  A
+ * call that fails half-way (a poisoned handle) leaves the snapshot count where it was.
+ * read_exact / read: wait for the device; the n snapshots taken since configure / reset, and n -- any pointer may be
+ * NULL; they clear nothing, and a poisoned handle may still be read.  While any replica's sticky word is set they return
+ * LJMD_ERR_RANGE, the message naming the lowest such replica ("replica <b>"), until ljmd_batch_heatflux_reset; the
+ * handle is not poisoned and stepping goes on.  read_exact has then filled `words` all the same (an out-of-range pair or
+ * particle entered as zeros; the other replicas' rows are whole) and left n_snapshots alone; read has written nothing.  reset: empties the series and clears the words.  accumulate, read_exact,
+ * read and reset return LJMD_ERR_STATE before configure.
+ */
+#define LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS 262144
+int ljmd_batch_heatflux_configure(ljmd_batch_t *h, int32_t max_snapshots, int32_t every);
+int ljmd_batch_heatflux_accumulate(ljmd_batch_t *h);
+int ljmd_batch_heatflux_read_exact(ljmd_batch_t *h, int64_t *words /* [n][B][9][3] */, int64_t *n_snapshots);
+int ljmd_batch_heatflux_read(ljmd_batch_t *h, double *j /* [n][B][3] */, double *parts /* [n][B][3][3], may be NULL */, int64_t *n_snapshots);
+int ljmd_batch_heatflux_reset(ljmd_batch_t *h);
 
 /*
  * Independent initial configurations on the device (ljmd_batch_prepare): per replica b, with n = n_b, L = L_b and k the
@@ -862,8 +901,8 @@ int ljmd_batch_stress_reset(ljmd_batch_t *h);
  *      setting), ekin0 = what ljmd_batch_kinetic_energy returns for it; scale = sqrt((target - epot0) / ekin0) in IEEE
  *      doubles on the host; v <- v * scale on the device, one rounding each.  The accelerations of the force call stay
  *      valid (the positions did not change).
- *   e. warmup_steps velocity-Verlet steps as ljmd_batch_steps takes them, nothing sampled and no g(r), MSD, VACF or
- *      pressure tensor snapshot taken whatever `every` is configured to; then ru <- r again, as a production run that read this state
+ *   e. warmup_steps velocity-Verlet steps as ljmd_batch_steps takes them, nothing sampled and no g(r), MSD, VACF,
+ *      pressure tensor or heat flux snapshot taken whatever `every` is configured to; then ru <- r again, as a production run that read this state
  *      from rv_init.dat would start.  (ljmd_batch_profile_read then describes the warm-up.)
  * Afterwards the handle has a state and valid accelerations; the range flags are cleared, a poison is cleared as
  * ljmd_batch_set_state clears it, the MSD / VACF snapshot numbering restarts at 0 and the accumulators' sums stay.

@@ -165,6 +165,11 @@ PROTOTYPES = {
     "ljmd_batch_stress_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
     "ljmd_batch_stress_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
     "ljmd_batch_stress_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_heatflux_configure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32]),
+    "ljmd_batch_heatflux_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_heatflux_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ljmd_batch_heatflux_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int64_p]),
+    "ljmd_batch_heatflux_reset": (C.c_int, [C.c_void_p]),
     "ljmd_batch_prepare": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
     "ljmd_tcf_from_exact": (C.c_int, [c_int64_p, C.c_int32, C.c_int64, c_double_p]),
 }
@@ -177,6 +182,7 @@ TCF_MAX_ORIGINS = 512
 STRESS_MAX_SNAPSHOTS = 262144
 HEATFLUX_MAX_SNAPSHOTS = 262144
 BATCH_STRESS_MAX_SNAPSHOTS = 262144
+BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
 
 _lib = None
 

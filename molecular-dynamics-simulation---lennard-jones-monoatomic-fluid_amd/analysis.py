@@ -163,6 +163,22 @@ def heat_flux_acf(j, max_lag=None, origin_stride: int = 1) -> np.ndarray:
     return compute_vacf_tau_timeorig(jx, jy, jz, max_lag, origin_stride) / 3.0
 
 
+def heat_flux_acf_ensemble(j, max_lag=None, origin_stride: int = 1):
+    """j [n_snap, B, 3]: the heat-flux series of a batch of B identical replicas (BatchEngine.heatflux_read) ->
+    (mean[max_lag + 1], stderr[max_lag + 1]): per lag the mean over the replicas of heat_flux_acf(j[:, b]) and its
+    standard error, the sample standard deviation (ddof = 1) over sqrt(B); with B = 1 the error is not defined (NaN).
+    The replicas are taken as independent runs of one state point: the error falls as 1 / sqrt(B)."""
+    j = np.asarray(j, dtype=np.float64)
+    if j.ndim != 3 or j.shape[2] != 3 or j.shape[1] < 1:
+        raise ValueError(f"heat_flux_acf_ensemble: j must have shape (n_snap, B, 3) with B >= 1, got {j.shape}")
+    B = j.shape[1]
+    acf = np.stack([heat_flux_acf(j[:, b], max_lag, origin_stride) for b in range(B)])
+    mean = acf.mean(axis=0)
+    if B < 2:
+        return mean, np.full_like(mean, np.nan)
+    return mean, acf.std(axis=0, ddof=1) / np.sqrt(B)
+
+
 def thermal_conductivity_green_kubo(acf, dt_sample: float, V: float, T: float) -> np.ndarray:
     """Green-Kubo running thermal conductivity lambda(tau) = V / T^2 * integral_0^tau acf, the integral by the trapezoid
     rule on the sampling grid (lambda[0] = 0); reduced units (k_B = 1)."""

@@ -1,7 +1,7 @@
 // ljmd_batch_host.h -- what the host files of the batch engine share (ljmd_batch.cpp: lifecycle, planning, step loop;
-// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF; ljmd_stress_batch.cpp: pressure tensor): the handle, the
-// entry guard, the poison and allocation helpers, and the form in which the step loop sees an accumulator.  Host code
-// only; the kernels' side is ljmd_batch.h.
+// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF; ljmd_stress_batch.cpp: pressure tensor;
+// ljmd_heatflux_batch.cpp: heat flux): the handle, the entry guard, the poison and allocation helpers, and the form in
+// which the step loop sees an accumulator.  Host code only; the kernels' side is ljmd_batch.h.
 #ifndef LJMD_BATCH_HOST_H
 #define LJMD_BATCH_HOST_H
 
@@ -70,17 +70,21 @@ struct BatchAccumulator {
     int (*room)(ljmd_batch *h, int snapshots, const char *who) = nullptr;
 };
 
-// pressure tensor series (ljmd_stress_batch.cpp): off while max_snapshots == 0, and every is 0 then.  That file is not
-// linked into every program that links ljmd_batch.cpp (tests/batch_trace), so the handle carries its entry into the
-// step loop and its release: ljmd_batch_stress_configure fills both, and default-constructed means nothing is called
-struct BatchStress {
+// a series of snapshots of exact integer sums -- the pressure tensor's (ljmd_stress_batch.cpp) and the heat flux's
+// (ljmd_heatflux_batch.cpp): off while max_snapshots == 0, and every is 0 then.  Those files are not linked into every
+// program that links ljmd_batch.cpp (tests/batch_trace), so the handle carries their entry into the step loop and their
+// release: ljmd_batch_stress_configure / ljmd_batch_heatflux_configure fill both, and default-constructed means nothing
+// is called
+struct BatchSeries {
     int32_t max_snapshots = 0, every = 0;
     int64_t count = 0;                // snapshots in the series
-    uint64_t *d_words = nullptr;      // [max_snapshots][B][12][3] signed 192-bit
-    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_stress_reset
+    uint64_t *d_words = nullptr;      // [max_snapshots][B][sums][3] signed 192-bit: 12 sums (stress), 9 (heat flux)
+    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_stress_reset / ljmd_batch_heatflux_reset
     BatchAccumulator acc;
     void (*release)(ljmd_batch *h) = nullptr;
 };
+using BatchStress = BatchSeries;
+using BatchHeatflux = BatchSeries;
 
 }  // namespace ljmdb
 
@@ -111,6 +115,7 @@ struct ljmd_batch {
     ljmdb::BatchRdf rdf;
     ljmdb::BatchTcf tcf;
     ljmdb::BatchStress stress;
+    ljmdb::BatchHeatflux heatflux;
     std::string err;
 };
 
@@ -122,10 +127,10 @@ inline bool reproducible(const ljmd_batch *h) { return h->mode == LJMD_PRECISION
 inline double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
 
 // What an entry point requires before it starts, checked in this order after the NULL handle: configured g(r),
-// configured MSD / VACF, configured pressure tensor, a state, valid accelerations, no poison (LJMD_ERR_STATE each);
-// kNeedDevice: the handle's device is then made current (ljmd_batch.cpp)
+// configured MSD / VACF, configured pressure tensor, configured heat flux, a state, valid accelerations, no poison
+// (LJMD_ERR_STATE each); kNeedDevice: the handle's device is then made current (ljmd_batch.cpp)
 enum BatchNeed : unsigned { kNeedRdf = 1, kNeedTcf = 2, kNeedState = 4, kNeedAccel = 8, kNeedSound = 16, kNeedDevice = 32,
-                         kNeedStress = 64 };
+                         kNeedStress = 64, kNeedHeatflux = 128 };
 int enter(ljmd_batch *h, const char *who, unsigned need);
 
 // fails the call as fail() does and poisons the handle: LJMD_ERR_STATE from the guarded calls until ljmd_batch_set_state
@@ -162,12 +167,13 @@ int host_alloc(const ljmd_batch *h, const char *who, F &&grow)
 
 BatchAccumulator rdf_accumulator(const ljmd_batch *h);    // ljmd_batch_rdf.cpp
 BatchAccumulator tcf_accumulator(const ljmd_batch *h);    // ljmd_batch_tcf.cpp
-using BatchAccumulators = std::array<BatchAccumulator, 3>;
+using BatchAccumulators = std::array<BatchAccumulator, 4>;
 inline BatchAccumulators accumulators(const ljmd_batch *h)
 {
-    BatchAccumulator stress = h->stress.acc;
+    BatchAccumulator stress = h->stress.acc, heatflux = h->heatflux.acc;
     stress.every = h->stress.every;
-    return {rdf_accumulator(h), tcf_accumulator(h), stress};
+    heatflux.every = h->heatflux.every;
+    return {rdf_accumulator(h), tcf_accumulator(h), stress, heatflux};
 }
 
 // one snapshot of the resident state outside ljmd_batch_steps, on the handle's stream (ljmd_batch_*_accumulate)

@@ -37,6 +37,8 @@ module ljmd_c_api
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_stress_configure, ljmd_batch_stress_accumulate, ljmd_batch_stress_read, ljmd_batch_stress_read_exact
   public :: ljmd_batch_stress_reset
+  public :: ljmd_batch_heatflux_configure, ljmd_batch_heatflux_accumulate, ljmd_batch_heatflux_read
+  public :: ljmd_batch_heatflux_read_exact, ljmd_batch_heatflux_reset
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -48,6 +50,7 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_ORIGINS = 512
   integer(c_int32_t), parameter, public :: LJMD_STRESS_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_STRESS_MAX_SNAPSHOTS = 262144
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_HEATFLUX_MAX_SNAPSHOTS = 262144
 
   interface
@@ -639,6 +642,45 @@ module ljmd_c_api
     end function
 
     function ljmd_batch_stress_reset(handle) bind(C, name="ljmd_batch_stress_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    ! heat flux of every replica of a batch handle (ljmd.h: ljmd_batch_heatflux_*); j = c_loc of [3, B, n_snapshots]
+    ! doubles, parts = c_loc of [3, 3, B, n_snapshots] doubles (axis fastest, then convective / potential / collisional),
+    ! words = c_loc of [3, 9, B, n_snapshots] 64-bit words in Fortran order; c_null_ptr skips an output
+    function ljmd_batch_heatflux_configure(handle, max_snapshots, every) bind(C, name="ljmd_batch_heatflux_configure") &
+        result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_snapshots, every
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_heatflux_accumulate(handle) bind(C, name="ljmd_batch_heatflux_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_heatflux_read(handle, j, parts, n_snapshots) bind(C, name="ljmd_batch_heatflux_read") &
+        result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, j, parts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_heatflux_read_exact(handle, words, n_snapshots) bind(C, name="ljmd_batch_heatflux_read_exact") &
+        result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_heatflux_reset(handle) bind(C, name="ljmd_batch_heatflux_reset") result(status)
       import :: c_int, c_ptr
       type(c_ptr), value :: handle
       integer(c_int) :: status

@@ -33,6 +33,11 @@
 ! and p_xx, p_yy, p_zz, p_xy, p_xz, p_yz without tail correction, and with LJMD_STRESS_MAX_LAG > 0
 ! outputs/run_NNNN/stress_acf_gpu.dat the shear and normal-difference autocorrelations and running Green-Kubo
 ! viscosities of the run -- the files and formats of md_simulation_gpu; every other file stays byte-identical),
+! LJMD_HEATFLUX (default 0 = off; 1: the heat flux of every run is recorded on the device, ljmd_batch_heatflux_*, at every
+! sampling instant that writes an rva.dat record; outputs/run_NNNN/heat_flux_gpu.dat gets per instant its time, J_x, J_y,
+! J_z and the nine parts, and with LJMD_HEATFLUX_MAX_LAG > 0 outputs/run_NNNN/heat_flux_acf_gpu.dat the autocorrelation
+! and running Green-Kubo thermal conductivity of the run -- the files and formats of md_simulation_gpu; every other file
+! stays byte-identical),
 ! LJMD_SEED_BASE (unset: the rv_init.dat files above are read; s >= 1: NO rv_init.dat is read -- run i is prepared on the
 ! device, ljmd_batch_prepare, with seed s + i - 1: the reference's FCC lattice, its generator's velocities, centre of
 ! mass removed, scaled to the target_total_energy of the run's own or the shared input file, then that file's
@@ -51,7 +56,7 @@ program md_simulation_many_gpu
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
   use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
-                              write_stress_acf_file
+                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file
   implicit none
 
   character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
@@ -92,6 +97,11 @@ program md_simulation_many_gpu
   real(c_double), allocatable, target :: stress_p(:, :, :)      ! [6, n_runs, snapshots]
   real(c_double), allocatable :: stress_times(:, :)             ! [snapshots, n_runs]
   integer(c_int64_t) :: stress_snapshots
+  logical :: heatflux_on
+  integer :: heatflux_max_lag
+  real(c_double), allocatable, target :: heatflux_j(:, :, :), heatflux_parts(:, :, :, :)   ! [3, n_runs, snapshots], [3, 3, ...]
+  real(c_double), allocatable :: heatflux_times(:, :)           ! [snapshots, n_runs]
+  integer(c_int64_t) :: heatflux_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -127,6 +137,13 @@ program md_simulation_many_gpu
   call get_environment_variable('LJMD_STRESS_MAX_LAG', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) stress_max_lag
   if (stress_max_lag < 0) stop 'md_simulation_many: LJMD_STRESS_MAX_LAG must be >= 0.'
+  heatflux_on = .false.
+  call get_environment_variable('LJMD_HEATFLUX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) heatflux_on = trim(env) /= '0'
+  heatflux_max_lag = 0
+  call get_environment_variable('LJMD_HEATFLUX_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) heatflux_max_lag
+  if (heatflux_max_lag < 0) stop 'md_simulation_many: LJMD_HEATFLUX_MAX_LAG must be >= 0.'
 
   seed_base = 0
   call get_environment_variable('LJMD_SEED_BASE', env, status=ios)
@@ -208,6 +225,14 @@ program md_simulation_many_gpu
                           'ljmd_batch_stress_configure')
     allocate(stress_times(n_snapshots_expected, n_runs))
   end if
+  if (heatflux_on) then
+    if (n_snapshots_expected < 1) stop 'md_simulation_many: LJMD_HEATFLUX needs at least one sampling instant.'
+    if (n_snapshots_expected > LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS) &
+      stop 'md_simulation_many: more sampling instants than LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS.'
+    call ljmd_batch_check(ljmd_batch_heatflux_configure(batch, int(n_snapshots_expected, c_int32_t), 0_c_int32_t), batch, &
+                          'ljmd_batch_heatflux_configure')
+    allocate(heatflux_times(n_snapshots_expected, n_runs))
+  end if
   do i = 1, n_runs
     open(newunit=iu_rva(i), file=trim(run_dir(i)) // '/rva.dat', form='unformatted', status='replace', &
          action='write', iostat=ios)
@@ -241,6 +266,10 @@ program md_simulation_many_gpu
     if (stress_on) then
       call ljmd_batch_check(ljmd_batch_stress_accumulate(batch), batch, 'ljmd_batch_stress_accumulate')
       stress_times(num_samples, :) = time_run
+    end if
+    if (heatflux_on) then
+      call ljmd_batch_check(ljmd_batch_heatflux_accumulate(batch), batch, 'ljmd_batch_heatflux_accumulate')
+      heatflux_times(num_samples, :) = time_run
     end if
     call ljmd_batch_check(ljmd_batch_get_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(ux), c_loc(uy), &
                                                c_loc(uz), c_loc(vx), c_loc(vy), c_loc(vz), c_loc(ax), c_loc(ay), &
@@ -276,6 +305,12 @@ program md_simulation_many_gpu
     call ljmd_batch_check(ljmd_batch_stress_read(batch, c_loc(stress_p), stress_snapshots), batch, 'ljmd_batch_stress_read')
     if (stress_snapshots /= num_samples) stop 'md_simulation_many: the pressure tensor series and the samples disagree.'
   end if
+  if (heatflux_on) then
+    allocate(heatflux_j(3, n_runs, max(num_samples, 1)), heatflux_parts(3, 3, n_runs, max(num_samples, 1)))
+    call ljmd_batch_check(ljmd_batch_heatflux_read(batch, c_loc(heatflux_j), c_loc(heatflux_parts), heatflux_snapshots), &
+                          batch, 'ljmd_batch_heatflux_read')
+    if (heatflux_snapshots /= num_samples) stop 'md_simulation_many: the heat flux series and the samples disagree.'
+  end if
   call ljmd_batch_destroy(batch)
   do i = 1, n_runs
     close(iu_out(i))
@@ -306,6 +341,11 @@ program md_simulation_many_gpu
   if (stress_on) then
     do i = 1, n_runs
       call write_stress(i)
+    end do
+  end if
+  if (heatflux_on) then
+    do i = 1, n_runs
+      call write_heat_flux(i)
     end do
   end if
   if (any_own) then
@@ -391,6 +431,35 @@ contains
     call write_stress_acf_file(trim(run_dir(irun)) // '/stress_acf_gpu.dat', lags, output_interval, rparams(irun)%dt, &
                                rparams(irun)%volume, mean_temp, shear, normal)
   end subroutine write_stress
+
+  ! run i's heat_flux_gpu.dat and, with LJMD_HEATFLUX_MAX_LAG > 0, heat_flux_acf_gpu.dat: what md_simulation_gpu writes for
+  ! one run (md_run_outputs: write_heat_flux_file, write_heat_flux_acf_file), from the run's rows of the series
+  subroutine write_heat_flux(irun)
+    integer, intent(in) :: irun
+    real(c_double), allocatable, target :: j(:, :), parts(:, :, :), c(:, :), acf(:)
+    real(kind=dp_kind) :: mean_temp, std_temp
+    integer :: ns, lags
+    ns = int(num_samples)
+    allocate(j(3, ns), parts(3, 3, ns))
+    j = heatflux_j(:, irun, 1:ns)
+    parts = heatflux_parts(:, :, irun, 1:ns)
+    call write_heat_flux_file(trim(run_dir(irun)) // '/heat_flux_gpu.dat', ns, heatflux_times(1:ns, irun), j, parts)
+    if (heatflux_max_lag <= 0 .or. ns < 2) return
+    ! the three components as the velocity of one particle: [1, snapshots] each
+    allocate(c(ns, 3))
+    c(:, 1) = j(1, :)
+    c(:, 2) = j(2, :)
+    c(:, 3) = j(3, :)
+    lags = min(heatflux_max_lag, ns - 1)
+    allocate(acf(0:lags))
+    call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(ns, c_int32_t), 1_c_int32_t, c_loc(c(1, 1)), c_loc(c(1, 2)), &
+                                             c_loc(c(1, 3)), int(lags, c_int32_t), 1_c_int32_t, c_loc(acf)), c_null_ptr, &
+                    'ljmd_time_origin_average')
+    acf = acf / 3.d0
+    call stats_mean_std(stats(irun), Q_T, mean_temp, std_temp)
+    call write_heat_flux_acf_file(trim(run_dir(irun)) // '/heat_flux_acf_gpu.dat', lags, output_interval, rparams(irun)%dt, &
+                                  rparams(irun)%volume, mean_temp, acf)
+  end subroutine write_heat_flux
 
   ! LJMD_SEED_BASE: every run's initial configuration on the device (seed_base + i - 1, the run's target_total_energy,
   ! the shared warmup_steps), then each run's rv_init_gpu.dat: the two records of rv_init.dat

@@ -879,6 +879,61 @@ class BatchEngine:
     def stress_reset(self) -> None:
         self._ck(self._lib.ljmd_batch_stress_reset(self._h))
 
+    # -- heat flux on the device (include/ljmd.h: ljmd_batch_heatflux_*) --------
+    def heatflux_configure(self, max_snapshots: int, every: int = 0) -> None:
+        """ljmd_batch_heatflux_configure: room for max_snapshots snapshots of every replica's heat flux on the device;
+        every > 0: steps() appends the state after steps every, 2 every, ... by itself.  max_snapshots = 0 switches the
+        feature off.  The series starts empty."""
+        for name, val in (("max_snapshots", max_snapshots), ("every", every)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise TypeError(f"heatflux_configure: {name} must be an integer, got {val!r}")
+            if not -2 ** 31 <= int(val) <= 2 ** 31 - 1:
+                raise ValueError(f"heatflux_configure: {name} must lie within the int32 range")
+        self._ck(self._lib.ljmd_batch_heatflux_configure(self._h, int(max_snapshots), int(every)))
+        self._heatflux_max = int(max_snapshots)
+
+    def heatflux_accumulate(self) -> None:
+        """appends the heat flux of every replica's resident state to the series (no host wait)"""
+        self._ck(self._lib.ljmd_batch_heatflux_accumulate(self._h))
+
+    def _heatflux_rows(self, who: str) -> int:
+        """snapshots in the series (ljmd_batch_heatflux_read_exact without a buffer); raises as the reads do"""
+        if getattr(self, "_heatflux_max", 0) < 1:
+            raise ValueError(f"{who}: call heatflux_configure with max_snapshots >= 1 first")
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_heatflux_read_exact(self._h, None, C.byref(snaps)))
+        return snaps.value
+
+    def heatflux_read(self):
+        """-> (j[n_snapshots, B, 3], parts[n_snapshots, B, 3, 3]): the heat flux (1/2 sum v^2 v + sum phi w +
+        6 sum (f . w) d) / V_b per snapshot and replica and its three summands over V_b, parts[..., 0, :] convective,
+        parts[..., 1, :] potential, parts[..., 2, :] collisional; nothing is cleared"""
+        n = max(self._heatflux_rows("heatflux_read"), 1)
+        j = np.empty((n, self.n_replicas, 3), dtype=np.float64)
+        parts = np.empty((n, self.n_replicas, 3, 3), dtype=np.float64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_heatflux_read(self._h, _ptr(j), _ptr(parts), C.byref(snaps)))
+        return j[:snaps.value].copy(), parts[:snaps.value].copy()
+
+    def heatflux_read_exact(self, raw: bool = False):
+        """-> sums[n_snapshots, B, 9]: the exact integer sums of Q(term) = RNE(term 2^64), E[3], P[3] then C[3], as
+        Python ints in an object array -- or, raw=True, the library's int64 words [n_snapshots, B, 9, 3] (three
+        little-endian limbs of a signed 192-bit integer)"""
+        words = np.empty((max(self._heatflux_rows("heatflux_read_exact"), 1), self.n_replicas, 9, 3), dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_heatflux_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        words = words[:snaps.value].copy()
+        if raw:
+            return words
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:3], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums
+
+    def heatflux_reset(self) -> None:
+        self._ck(self._lib.ljmd_batch_heatflux_reset(self._h))
+
     @staticmethod
     def per_replica(params_list, device: int = 0,
                     precision_mode: int = _lib.PRECISION_FP64) -> "PerReplicaBatchEngine":
