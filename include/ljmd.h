@@ -492,6 +492,67 @@ int ljmd_tcf_reset(ljmd_t *h);
 int ljmd_tcf_profile_read(ljmd_t *h, double *kernel_ms, int32_t *origins_live);
 
 /*
+ * Van Hove self-correlation G_s(r, tau) = < delta(r - |ru_i(t0 + tau) - ru_i(t0)|) > of the resident system, the
+ * distribution behind the MSD, time-origin averaged where ru lives (ljmd_vanhove_*): no snapshot leaves the device.
+ * One-rank engines only (ljmd_create with n_ranks = 1).
+ *
+ * Definition.  Parameters max_lag, origin_stride, nbins, rmax; dr = rmax / nbins.  Snapshots, their numbering s, the
+ * origin rule and the ring slot are those of ljmd_tcf_* above, word for word: a snapshot is stored as an origin when
+ * s % origin_stride == 0, in ring slot (s / origin_stride) % slots with slots = max_lag / origin_stride + 1 <=
+ * LJMD_VANHOVE_MAX_ORIGINS; an origin t0 contributes at 1 <= s - t0 <= max_lag; the lag-0 row of an origin is added
+ * when the next snapshot arrives; count[l] is kept on the host; a term pairs a particle with itself by id, the index
+ * in the arrays of the last ljmd_set_state.  A snapshot here is the resident ru only (numbered from the last
+ * configure, reset or ljmd_set_state).  Per particle i, origin t0 and lag l, unfused and left to right:
+ *   d = ru(t0 + l) - ru(t0) per axis ;  r2 = (dx*dx + dy*dy) + dz*dz     (the MSD term of ljmd_tcf_*, bit for bit)
+ *   r4 = r2 * r2 ;  r = sqrt(r2) (correctly rounded) ;  bin = int(r / dr) exactly (the true quotient, truncated)
+ *   H[l][bin] += 1 for bin < nbins, else H[l][nbins] += 1 (the overflow column); H is [max_lag + 1][nbins + 1] uint64
+ *   S2[l] += Q(r2), S4[l] += Q(r4), Q(t) = RNE(t 2^64): signed 192-bit integers, three int64 limbs, least significant
+ *   first (the layout of ljmd_tcf_read_exact)
+ * Range: when r2 or r4 is not finite or |r4| >= 2^40 the particle counts in the overflow column, enters both sums as 0
+ * and sets a sticky range word.  Invariants: every row of H sums to n count[l]; S2 equals ljmd_tcf_*'s S[MSD] for the
+ * same snapshots and the same (max_lag, origin_stride), integer for integer.  The integers depend on the snapshots
+ * alone: not on slot order, re-sort state or interval, tiling knobs, step form, precision mode (given the same ru) or
+ * on how the kernels split the work (LJMD_VANHOVE_CHUNK, read at ljmd_create: live origins per slice of the grid).
+ * r2[l] = fixed(S2[l]) / ((double)n * (double)count[l]) and r4[l] likewise, through ljmd_tcf_from_exact: one rounding,
+ * one division, 0 where count[l] == 0.  The non-Gaussian parameter is alpha2 = 3 r4 / (5 r2^2) - 1.
+ * configure: 1 <= max_lag <= LJMD_VANHOVE_MAX_LAG, origin_stride >= 1, 1 <= nbins <= LJMD_VANHOVE_MAX_BINS, rmax finite
+ * and > 0 (rmax / nbins a normal number), n <= 2^23; max_lag = 0 switches the feature off and frees everything (the
+ * other arguments are then ignored); otherwise allocates and zeroes; calling it again reconfigures and zeroes.  A
+ * failed guard returns LJMD_ERR_INVALID_ARG and leaves the earlier configuration in place; a failed allocation
+ * LJMD_ERR_ALLOC with the feature off, the message naming the buffer and its byte count.  Works with or without a
+ * state.  The origin ring, the feature's own (not that of ljmd_tcf_*), is slots x 3 x n_pad x 8 bytes, n_pad = n rounded
+ * up to 1024 -- 3.2 GB at n = 262 144 with 512 origins; every size is computed in size_t.  On a rank engine (n_ranks > 1)
+ * or a multi-device handle (ljmd_create_multi) configure returns LJMD_ERR_INVALID_ARG ("... n_ranks = <G>: ... needs a
+ * one-rank engine"), and the other five calls LJMD_ERR_STATE ("not configured").
+ * accumulate: the resident ru is the next snapshot, stream-ordered on the engine's stream behind everything enqueued so
+ * far (ljmd_enqueue_steps* included), no host wait.  Guards and their order are those of ljmd_rdf_accumulate.  It
+ * writes only buffers of its own: r, ru, v, a, the step records, the slot permutation, the other observables and every
+ * later result stay bitwise what they are without the call.
+ * read / read_exact: wait for the device; hist[max_lag + 1][nbins + 1], r2[max_lag + 1], r4[max_lag + 1] (read) or
+ * words[2][max_lag + 1][3], S2 then S4 (read_exact), counts[max_lag + 1], the number of snapshots since configure /
+ * reset -- any pointer may be NULL; they clear nothing.  With the range word set they return LJMD_ERR_RANGE until
+ * ljmd_vanhove_reset; the handle is not poisoned and stepping is unaffected.
+ * reset: zeroes the histogram, sums, counts, numbering and range word.
+ * profile_read, for the most recent accumulate (zeros before the first): the HIP-event time of its launches and the
+ * number of live origins it visited; either pointer may be NULL; waits for the device.
+ * read, read_exact, reset and profile_read return LJMD_ERR_STATE before configure.
+ * ljmd_set_state starts a new trajectory: the stored origins are dropped and the numbering restarts at 0; histogram,
+ * sums and counts stay.  The other setters, ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_*, ljmd_heatflux_* and ljmd_migrate leave
+ * everything alone.
+ */
+#define LJMD_VANHOVE_MAX_LAG 4096
+#define LJMD_VANHOVE_MAX_ORIGINS 512
+#define LJMD_VANHOVE_MAX_BINS 4096
+int ljmd_vanhove_configure(ljmd_t *h, int32_t max_lag, int32_t origin_stride, int32_t nbins, double rmax);
+int ljmd_vanhove_accumulate(ljmd_t *h);
+int ljmd_vanhove_read(ljmd_t *h, uint64_t *hist /* [max_lag+1][nbins+1] */, double *r2 /* [max_lag+1] */,
+                      double *r4 /* [max_lag+1] */, int64_t *counts, int64_t *n_snapshots);
+int ljmd_vanhove_read_exact(ljmd_t *h, uint64_t *hist, int64_t *words /* [2][max_lag+1][3]: S2 then S4 */,
+                            int64_t *counts, int64_t *n_snapshots);
+int ljmd_vanhove_reset(ljmd_t *h);
+int ljmd_vanhove_profile_read(ljmd_t *h, double *kernel_ms, int32_t *origins_live);
+
+/*
  * Pressure tensor of the resident system, one snapshot per call, recorded where r and v live (ljmd_stress_*): no
  * snapshot leaves the device.  One-rank engines, rank engines and multi-device handles; n <= 2^23.
  *

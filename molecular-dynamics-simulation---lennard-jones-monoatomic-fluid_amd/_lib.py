@@ -137,6 +137,12 @@ PROTOTYPES = {
     "ljmd_tcf_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_int64_p]),
     "ljmd_tcf_reset": (C.c_int, [C.c_void_p]),
     "ljmd_tcf_profile_read": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
+    "ljmd_vanhove_configure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_double]),
+    "ljmd_vanhove_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_vanhove_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_double_p, c_double_p, c_int64_p, c_int64_p]),
+    "ljmd_vanhove_read_exact": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p, c_int64_p, c_int64_p]),
+    "ljmd_vanhove_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_vanhove_profile_read": (C.c_int, [C.c_void_p, c_double_p, c_int32_p]),
     "ljmd_stress_configure": (C.c_int, [C.c_void_p, C.c_int32]),
     "ljmd_stress_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_stress_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
@@ -179,6 +185,9 @@ BATCH_TCF_MAX_LAG = 4096
 BATCH_TCF_MAX_ORIGINS = 512
 TCF_MAX_LAG = 4096
 TCF_MAX_ORIGINS = 512
+VANHOVE_MAX_LAG = 4096
+VANHOVE_MAX_ORIGINS = 512
+VANHOVE_MAX_BINS = 4096
 STRESS_MAX_SNAPSHOTS = 262144
 HEATFLUX_MAX_SNAPSHOTS = 262144
 BATCH_STRESS_MAX_SNAPSHOTS = 262144

@@ -186,3 +186,47 @@ def thermal_conductivity_green_kubo(acf, dt_sample: float, V: float, T: float) -
     run = np.zeros_like(acf)
     run[1:] = np.cumsum(0.5 * (acf[1:] + acf[:-1]) * dt_sample)
     return (V / (T * T)) * run
+
+
+# -- van Hove self-correlation (Engine.vanhove_read: hist[max_lag + 1, nbins + 1] with the overflow column last) --------
+def _vanhove_rows(hist, counts, n: int):
+    """-> (inside [rows, nbins] float64, overflow fraction [rows], 1 / (n count) [rows], 0 where count == 0)"""
+    hist = np.asarray(hist)
+    counts = np.asarray(counts, dtype=np.float64)
+    if hist.ndim != 2 or hist.shape[1] < 2 or counts.shape != (hist.shape[0],) or n < 1:
+        raise ValueError("van Hove: hist must be [max_lag + 1, nbins + 1], counts [max_lag + 1], n >= 1")
+    norm = np.zeros_like(counts)
+    np.divide(1.0, n * counts, out=norm, where=counts > 0)
+    return hist[:, :-1].astype(np.float64), hist[:, -1].astype(np.float64) * norm, norm
+
+
+def van_hove_self(hist, counts, n: int, dr: float):
+    """-> (r_centers[nbins], G_s[max_lag + 1, nbins], overflow[max_lag + 1]): G_s[l, b] = H[l, b] / (n count[l]
+    V_shell(b)) with V_shell(b) = 4 pi / 3 ((b + 1)^3 - b^3) dr^3, so that sum_b G_s[l, b] V_shell(b) = 1 - overflow[l],
+    the fraction of the displacements beyond rmax.  Rows without an origin (count 0) are 0."""
+    inside, overflow, norm = _vanhove_rows(hist, counts, n)
+    b = np.arange(inside.shape[1], dtype=np.float64)
+    shell = 4.0 * math.pi / 3.0 * ((b + 1.0) ** 3 - b ** 3) * dr ** 3
+    return (b + 0.5) * dr, inside * norm[:, None] / shell[None, :], overflow
+
+
+def self_intermediate_scattering(hist, counts, n: int, dr: float, k):
+    """-> (F_s, overflow[max_lag + 1]): F_s(k, l) = sum_b H[l, b] sinc(k r_b) / (n count[l]) at the bin centres r_b =
+    (b + 1/2) dr, sinc(x) = sin(x) / x -- the isotropic average of exp(i k . d) over the displacements inside rmax.
+    k a number -> F_s[max_lag + 1]; k an array -> F_s[k.shape + (max_lag + 1,)].  The displacements in the overflow
+    column are left out: their fraction is returned beside it."""
+    inside, overflow, norm = _vanhove_rows(hist, counts, n)
+    centres = (np.arange(inside.shape[1], dtype=np.float64) + 0.5) * dr
+    k = np.asarray(k, dtype=np.float64)
+    weight = np.sinc(k[..., None] * centres / math.pi)           # np.sinc(x) = sin(pi x) / (pi x)
+    return (weight[..., None, :] * inside).sum(axis=-1) * norm, overflow      # one row's sum does not depend on k's shape
+
+
+def non_gaussian_parameter(r2, r4):
+    """alpha_2 = 3 <r^4> / (5 <r^2>^2) - 1 per lag (0 for a Gaussian distribution of displacements in three dimensions);
+    0 where <r^2> == 0"""
+    r2 = np.asarray(r2, dtype=np.float64)
+    r4 = np.asarray(r4, dtype=np.float64)
+    out = np.zeros(np.broadcast(r2, r4).shape)
+    np.divide(3.0 * r4, 5.0 * (r2 * r2), out=out, where=r2 != 0.0)
+    return np.where(r2 != 0.0, out - 1.0, 0.0)

@@ -110,6 +110,7 @@ int ljmd_set_state(ljmd_t *h, const double *rx, const double *ry, const double *
     h->drift_prefused = false;
     h->step_open = false;
     ljmdt::tcf_new_trajectory(&h->tcf);     // resident MSD / VACF: the origins are dropped, sums and counts stay
+    ljmdv::vanhove_new_trajectory(&h->vanhove);     // van Hove: likewise
     LJMD_HIP(h, hipSetDevice(h->device));
     if (h->poisoned) {
         // a batch of steps failed half-way: drain the stream, forget whatever records were in flight and take the

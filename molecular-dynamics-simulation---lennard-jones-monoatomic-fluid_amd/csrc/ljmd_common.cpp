@@ -105,6 +105,7 @@ Knobs read_knobs()
     k.reduce_split = opt_int("LJMD_REDUCE_SPLIT");
     if (k.reduce_split) k.reduce_split = std::max(0, *k.reduce_split);
     k.walk_chunk = opt_int("LJMD_WALK_CHUNK");
+    k.vanhove_chunk = opt_int("LJMD_VANHOVE_CHUNK");
     k.fp32_far_stream = flag("LJMD_FP32_FAR_STREAM", k.fp32_far_stream);
     k.fp32_vfar = flag("LJMD_FP32_VFAR", k.fp32_vfar);
     {

@@ -127,6 +127,8 @@ struct Knobs {
                                             // reduction's first phase (0 = one launch; unset: by system size)
     std::optional<int> walk_chunk;          // LJMD_WALK_CHUNK: column-tile steps per slice of the resident g(r) / pressure tensor /
                                             // heat flux walk, clamped to [1, steps] (tests; unset: by the grid rdf_plan_walk aims at)
+    std::optional<int> vanhove_chunk;       // LJMD_VANHOVE_CHUNK: live origins per slice of the van Hove terms kernel, clamped to
+                                            // [1, min(live origins, 128)] (tests; unset: by the grid vanhove_plan_slices aims at)
     bool fp32_far_stream = true;            // LJMD_FP32_FAR_STREAM: the fp32 far pass on a stream of its own
     bool fp32_vfar = true;                  // LJMD_FP32_VFAR: the very-far form of the fp32 kernel
     double fp32_split = 5.0;                // LJMD_FP32_SPLIT: boxes closer than this stay fp64

@@ -1,9 +1,9 @@
-// ljmd_resident.cpp -- the C entry points of the four observables of the system resident on the single / sharded
-// engine (include/ljmd.h: ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_*, ljmd_heatflux_*) and the release of what they
-// allocated.  Each runs the entry checks, builds the view of the engine and calls the observable's core (ljmd_rdf.cpp,
-// ljmd_tcf.cpp, ljmd_stress.cpp, ljmd_heatflux.cpp); g(r) and the pressure tensor dispatch a multi-device parent to its
-// rank engines.  MSD / VACF and the heat flux take one-rank engines only: their cores refuse every other handle at
-// configure, so a parent never has them configured.
+// ljmd_resident.cpp -- the C entry points of the five observables of the system resident on the single / sharded
+// engine (include/ljmd.h: ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_*, ljmd_heatflux_*, ljmd_vanhove_*) and the release of
+// what they allocated.  Each runs the entry checks, builds the view of the engine and calls the observable's core
+// (ljmd_rdf.cpp, ljmd_tcf.cpp, ljmd_stress.cpp, ljmd_heatflux.cpp, ljmd_vanhove.cpp); g(r) and the pressure tensor
+// dispatch a multi-device parent to its rank engines.  MSD / VACF, the heat flux and the van Hove function take one-rank
+// engines only: their cores refuse every other handle at configure, so a parent never has them configured.
 #include "ljmd_engine.h"
 #include "ljmd_multi.h"
 
@@ -22,10 +22,11 @@ ResidentView view_of(const ljmd_t *h)
     v.stream = h->stream;
     v.compact = h->positions_compact;
     v.walk_chunk = h->knobs.walk_chunk;
+    v.vanhove_chunk = h->knobs.vanhove_chunk;
     return v;
 }
 
-// one of the four: whether it is configured on a handle, and the failure where it is not
+// one of the five: whether it is configured on a handle, and the failure where it is not
 struct Observable {
     bool (*configured)(const ljmd_t *h);
     int (*not_configured)(std::string *err, const char *who);
@@ -34,6 +35,7 @@ const Observable kRdf = {[](const ljmd_t *h) { return h->rdf.nbins != 0; }, ljmd
 const Observable kTcf = {[](const ljmd_t *h) { return h->tcf.max_lag != 0; }, ljmdt::not_configured};
 const Observable kStress = {[](const ljmd_t *h) { return h->stress.max_snapshots != 0; }, ljmds::not_configured};
 const Observable kHeatflux = {[](const ljmd_t *h) { return h->heatflux.max_snapshots != 0; }, ljmdq::not_configured};
+const Observable kVanHove = {[](const ljmd_t *h) { return h->vanhove.max_lag != 0; }, ljmdv::not_configured};
 
 // a handle, and the observable configured on it
 int configured(ljmd_t *h, const char *who, const Observable &o)
@@ -136,6 +138,7 @@ void ljmdh::release_resident(ljmd_t *h)
     ljmdt::tcf_release(&h->tcf, h->stream);
     ljmds::stress_release(&h->stress, h->stream);
     ljmdq::heatflux_release(&h->heatflux, h->stream);
+    ljmdv::vanhove_release(&h->vanhove, h->stream);
 }
 
 extern "C" {
@@ -408,6 +411,57 @@ int ljmd_heatflux_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *
     LJMD_TRY(configured(h, who, kHeatflux));
     LJMD_HIP(h, hipSetDevice(h->device));
     return ljmdq::heatflux_profile_read(&h->heatflux, &h->err, who, view_of(h), tile_pairs_visited, tile_pairs_total, kernel_ms);
+}
+
+// ---- van Hove self-correlation ---------------------------------------------
+// one-rank engines only, as MSD / VACF: the core refuses every other handle at configure
+
+int ljmd_vanhove_configure(ljmd_t *h, int32_t max_lag, int32_t origin_stride, int32_t nbins, double rmax)
+{
+    static const char *who = "ljmd_vanhove_configure";
+    LJMD_TRY(entry_checks(h, who, kHandle));
+    if (!h->multi) LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdv::vanhove_configure(&h->vanhove, &h->err, who, view_of(h), max_lag, origin_stride, nbins, rmax);
+}
+
+int ljmd_vanhove_accumulate(ljmd_t *h)
+{
+    static const char *who = "ljmd_vanhove_accumulate";
+    LJMD_TRY(accumulate_checks(h, who, kVanHove));
+    return ljmdv::vanhove_accumulate(&h->vanhove, &h->err, who, view_of(h));
+}
+
+int ljmd_vanhove_read(ljmd_t *h, uint64_t *hist, double *r2, double *r4, int64_t *counts, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_vanhove_read";
+    LJMD_TRY(configured(h, who, kVanHove));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdv::vanhove_read(&h->vanhove, &h->err, who, view_of(h), hist, r2, r4, counts, n_snapshots);
+}
+
+int ljmd_vanhove_read_exact(ljmd_t *h, uint64_t *hist, int64_t *words, int64_t *counts, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_vanhove_read_exact";
+    LJMD_TRY(configured(h, who, kVanHove));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdv::vanhove_fetch(&h->vanhove, &h->err, who, view_of(h), hist, reinterpret_cast<uint64_t *>(words), counts,
+                                n_snapshots);
+}
+
+int ljmd_vanhove_reset(ljmd_t *h)
+{
+    static const char *who = "ljmd_vanhove_reset";
+    LJMD_TRY(configured(h, who, kVanHove));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdv::vanhove_reset(&h->vanhove, &h->err, who, view_of(h));
+}
+
+int ljmd_vanhove_profile_read(ljmd_t *h, double *kernel_ms, int32_t *origins_live)
+{
+    static const char *who = "ljmd_vanhove_profile_read";
+    LJMD_TRY(configured(h, who, kVanHove));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdv::vanhove_profile_read(&h->vanhove, &h->err, who, view_of(h), kernel_ms, origins_live);
 }
 
 }  // extern "C"

@@ -1,10 +1,11 @@
-// ljmd_resident.h -- host side of the four observables of the system resident on the single / sharded engine: g(r)
-// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp), the pressure tensor (ljmd_stress.cpp) and the heat flux
-// (ljmd_heatflux.cpp).  What the cores share -- the view through which they see an engine, their named device buffers,
-// the timer around one accumulate -- and each core's state and functions.  A core knows nothing of struct ljmd and links
-// without the engine (tests/rdf_host, tests/tcf_host, tests/stress_host, tests/heatflux_host); every C entry point that
-// takes a handle is in ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_tcf.h, ljmd_stress.h
-// and ljmd_heatflux.h.
+// ljmd_resident.h -- host side of the five observables of the system resident on the single / sharded engine: g(r)
+// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp), the pressure tensor (ljmd_stress.cpp), the heat flux
+// (ljmd_heatflux.cpp) and the van Hove self-correlation (ljmd_vanhove.cpp).  What the cores share -- the view through
+// which they see an engine, their named device buffers, the timer around one accumulate -- and each core's state and
+// functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host, tests/tcf_host,
+// tests/stress_host, tests/heatflux_host, tests/vanhove_host); every C entry point that takes a handle is in
+// ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_tcf.h, ljmd_stress.h, ljmd_heatflux.h and
+// ljmd_vanhove.h.
 #ifndef LJMD_RESIDENT_H
 #define LJMD_RESIDENT_H
 
@@ -13,6 +14,7 @@
 #include "ljmd_rdf.h"
 #include "ljmd_stress.h"
 #include "ljmd_tcf.h"
+#include "ljmd_vanhove.h"
 
 #include <array>
 #include <optional>
@@ -32,6 +34,7 @@ struct ResidentView {
     hipStream_t stream = nullptr;
     bool compact = false;           // coordinate spread < 2.4 L
     std::optional<int> walk_chunk;  // LJMD_WALK_CHUNK as the handle read it (Knobs::walk_chunk)
+    std::optional<int> vanhove_chunk;   // LJMD_VANHOVE_CHUNK as the handle read it (Knobs::vanhove_chunk)
 };
 
 // one device buffer of a state: where its pointer lives, its size, and what a failed allocation calls it
@@ -249,4 +252,58 @@ int heatflux_profile_read(HeatfluxState *st, std::string *err, const char *who, 
 void heatflux_release(HeatfluxState *st, hipStream_t stream);
 
 }  // namespace ljmdq
+namespace ljmdv {
+
+using ljmdh::ResidentView;
+
+// sizes of one configuration, all in size_t: the ring of n = 262 144 with 512 slots has 3.2e9 bytes
+struct VhSizes {
+    int slots = 0, ents = 0, nblk = 0;  // ents = slots + 1 entries per row of the partials
+    size_t n_pad = 0;
+    size_t cur_bytes = 0, ring_bytes = 0, part_bytes = 0, flag_bytes = 0, sums_bytes = 0, hist_bytes = 0;
+};
+VhSizes vanhove_sizes(int n, int max_lag, int stride, int nbins);
+
+// the grid of the terms kernel for n_live >= 1 live origins: (nblk, slices), chunk origins per slice
+struct VhSlices {
+    int chunk = 0, slices = 0;
+};
+// chunk unset: origins per slice by kVhTargetWorkgroups; set: that many, clamped to [1, min(n_live, kVhMaxChunk)] (tests)
+VhSlices vanhove_plan_slices(int nblk, int n_live, std::optional<int> chunk = std::nullopt);
+
+struct VanHoveState {
+    int max_lag = 0;                // 0 = not configured
+    int stride = 0, n = 0, nbins = 0;
+    double rmax = 0, dr = 0, inv_dr = 0;
+    VhSizes sz;
+    double *d_cur = nullptr, *d_ring = nullptr;
+    unsigned long long *d_hist = nullptr, *d_part = nullptr;
+    int32_t *d_flag = nullptr, *d_range = nullptr;
+    uint64_t *d_sums = nullptr;
+    ljmdh::KernelTimer timer;
+    int last_live = 0;              // live origins the most recent accumulate visited
+    int64_t s = 0;                  // number of the next snapshot of this trajectory
+    int64_t snapshots = 0;
+    std::vector<int64_t> counts;    // [max_lag + 1] origins that contributed to each lag
+};
+
+int not_configured(std::string *err, const char *who);
+// refuses a multi-device handle and a rank engine of G > 1 itself
+int vanhove_configure(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_lag,
+                      int32_t origin_stride, int32_t nbins, double rmax);
+int vanhove_accumulate(VanHoveState *st, std::string *err, const char *who, const ResidentView &v);
+// waits for the device; LJMD_ERR_RANGE while the sticky word is set; hist [max_lag + 1][nbins + 1] or NULL, words
+// [2][max_lag + 1][3] or NULL
+int vanhove_fetch(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *hist, uint64_t *words,
+                  int64_t *counts, int64_t *n_snapshots);
+int vanhove_read(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *hist, double *r2,
+                 double *r4, int64_t *counts, int64_t *n_snapshots);
+int vanhove_reset(VanHoveState *st, std::string *err, const char *who, const ResidentView &v);
+int vanhove_profile_read(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms,
+                         int32_t *origins_live);
+// ljmd_set_state: the stored origins are dropped and the numbering restarts; histogram, sums and counts stay
+void vanhove_new_trajectory(VanHoveState *st);
+void vanhove_release(VanHoveState *st, hipStream_t stream);
+
+}  // namespace ljmdv
 #endif

@@ -29,6 +29,8 @@ module ljmd_c_api
   public :: ljmd_batch_rdf_configure, ljmd_batch_rdf_accumulate, ljmd_batch_rdf_read, ljmd_batch_rdf_reset
   public :: ljmd_rdf_configure, ljmd_rdf_accumulate, ljmd_rdf_read, ljmd_rdf_reset, ljmd_rdf_profile_read
   public :: ljmd_tcf_configure, ljmd_tcf_accumulate, ljmd_tcf_read, ljmd_tcf_read_exact, ljmd_tcf_reset, ljmd_tcf_profile_read
+  public :: ljmd_vanhove_configure, ljmd_vanhove_accumulate, ljmd_vanhove_read, ljmd_vanhove_read_exact, ljmd_vanhove_reset
+  public :: ljmd_vanhove_profile_read
   public :: ljmd_stress_configure, ljmd_stress_accumulate, ljmd_stress_read, ljmd_stress_read_exact, ljmd_stress_reset
   public :: ljmd_stress_profile_read, ljmd_stress_from_exact, ljmd_time_origin_average
   public :: ljmd_heatflux_configure, ljmd_heatflux_accumulate, ljmd_heatflux_read, ljmd_heatflux_read_exact
@@ -48,6 +50,9 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_BATCH_MAX_N = 4096
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_LAG = 4096
   integer(c_int32_t), parameter, public :: LJMD_TCF_MAX_ORIGINS = 512
+  integer(c_int32_t), parameter, public :: LJMD_VANHOVE_MAX_LAG = 4096
+  integer(c_int32_t), parameter, public :: LJMD_VANHOVE_MAX_ORIGINS = 512
+  integer(c_int32_t), parameter, public :: LJMD_VANHOVE_MAX_BINS = 4096
   integer(c_int32_t), parameter, public :: LJMD_STRESS_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_STRESS_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
@@ -412,6 +417,53 @@ module ljmd_c_api
     end function
 
     function ljmd_tcf_profile_read(handle, kernel_ms, origins_live) bind(C, name="ljmd_tcf_profile_read") result(status)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      real(c_double), intent(out) :: kernel_ms
+      integer(c_int32_t), intent(out) :: origins_live
+      integer(c_int) :: status
+    end function
+
+    ! van Hove self-correlation of the system resident on a one-rank engine handle (ljmd.h: ljmd_vanhove_*); hist = c_loc
+    ! of [nbins + 1, max_lag + 1] 64-bit counts in Fortran order (the overflow column last), r2, r4, counts = c_loc of
+    ! max_lag + 1 values, words [3, max_lag + 1, 2] in Fortran order; c_null_ptr skips an output
+    function ljmd_vanhove_configure(handle, max_lag, origin_stride, nbins, rmax) bind(C, name="ljmd_vanhove_configure") &
+        result(status)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_lag, origin_stride, nbins
+      real(c_double), value :: rmax
+      integer(c_int) :: status
+    end function
+
+    function ljmd_vanhove_accumulate(handle) bind(C, name="ljmd_vanhove_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_vanhove_read(handle, hist, r2, r4, counts, n_snapshots) bind(C, name="ljmd_vanhove_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, hist, r2, r4, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_vanhove_read_exact(handle, hist, words, counts, n_snapshots) bind(C, name="ljmd_vanhove_read_exact") &
+        result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, hist, words, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_vanhove_reset(handle) bind(C, name="ljmd_vanhove_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_vanhove_profile_read(handle, kernel_ms, origins_live) bind(C, name="ljmd_vanhove_profile_read") result(status)
       import :: c_int, c_int32_t, c_double, c_ptr
       type(c_ptr), value :: handle
       real(c_double), intent(out) :: kernel_ms

@@ -12,6 +12,8 @@
 !   (ljmd_stress_*) and its Green-Kubo autocorrelations (write_pressure_tensor_file, write_stress_acf_file).
 !   <dir>/heat_flux_gpu.dat, <dir>/heat_flux_acf_gpu.dat: the heat flux md_simulation_gpu recorded on the device
 !   (ljmd_heatflux_*) and its Green-Kubo autocorrelation (write_heat_flux_file, write_heat_flux_acf_file).
+!   <dir>/van_hove_gpu.dat: the van Hove self-correlation md_simulation_gpu accumulated on the device (ljmd_vanhove_*):
+!   per lag the moments, the non-Gaussian parameter and the counts of |displacement| (write_van_hove_file).
 !==============================================================================
 module md_run_outputs
   use, intrinsic :: iso_c_binding, only: c_int64_t
@@ -21,7 +23,7 @@ module md_run_outputs
   implicit none
   private
   public :: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, write_stress_acf_file
-  public :: write_heat_flux_file, write_heat_flux_acf_file
+  public :: write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file
 
 contains
 
@@ -148,6 +150,36 @@ contains
     end do
     close(iu_tcf)
   end subroutine write_msd_vacf_file
+
+  ! van_hove_gpu.dat: a line with n, nbins, rmax and dr, then per lag with at least one origin: lag, tau = lag *
+  ! output_interval * dt, the origins, <r^2>, <r^4>, alpha_2 = 3 <r^4> / (5 <r^2>^2) - 1 (0 where <r^2> = 0), the count
+  ! of the overflow column (displacements of rmax and beyond) and the nbins counts of the bins [k dr, (k + 1) dr)
+  ! (ljmd_vanhove_read; every row of counts sums, with its overflow, to n origins)
+  subroutine write_van_hove_file(filename, n, max_lag, nbins, rmax, output_interval, dt, counts, r2, r4, hist)
+    character(len=*), intent(in) :: filename
+    integer(kind=int_kind), intent(in) :: n
+    integer, intent(in) :: max_lag, nbins
+    real(kind=dp_kind), intent(in) :: rmax
+    integer(kind=int_kind), intent(in) :: output_interval
+    real(kind=dp_kind), intent(in) :: dt
+    integer(c_int64_t), intent(in) :: counts(0:max_lag)
+    real(kind=dp_kind), intent(in) :: r2(0:max_lag), r4(0:max_lag)
+    integer(c_int64_t), intent(in) :: hist(0:nbins, 0:max_lag)
+    real(kind=dp_kind) :: alpha2
+    integer :: iu_vh, ierr, lag
+    open(newunit=iu_vh, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_van_hove_file(): cannot open van_hove_gpu.dat.'
+    write(iu_vh, '(a,i0,a,i0,2(a,es24.16e3))') '# n = ', n, '  nbins = ', nbins, '  rmax = ', rmax, '  dr = ', rmax / dble(nbins)
+    write(iu_vh, '(a)') '# lag   tau   origins   <r^2>   <r^4>   alpha_2   overflow   counts[nbins]'
+    do lag = 0, max_lag
+      if (counts(lag) <= 0) cycle
+      alpha2 = 0.d0
+      if (r2(lag) /= 0.d0) alpha2 = (3.d0 * r4(lag)) / (5.d0 * (r2(lag) * r2(lag))) - 1.d0
+      write(iu_vh, '(i0,2x,es24.16e3,2x,i0,3(2x,es24.16e3),*(2x,i0))') lag, dble(lag) * dble(output_interval) * dt, &
+        counts(lag), r2(lag), r4(lag), alpha2, hist(nbins, lag), hist(0:nbins - 1, lag)
+    end do
+    close(iu_vh)
+  end subroutine write_van_hove_file
 
   ! pressure_tensor_gpu.dat: per sampling instant its time and p_xx, p_yy, p_zz, p_xy, p_xz, p_yz (ljmd_stress_read: no
   ! tail correction); times(k) is the time of snapshot k

@@ -38,7 +38,13 @@
 ! outputs/one_run/heat_flux_acf_gpu.dat also gets, per lag up to that many sampling instants, lag, tau, the time-origin
 ! averaged <J(0) . J(tau)> / 3 -- ljmd_time_origin_average on the series as the velocity of one particle -- and the
 ! running Green-Kubo thermal conductivity V / <T>^2 times its trapezoid integral; one-rank engines only: with
-! LJMD_GPUS > 1 the program stops before an engine is created; every other output file is the same with and without it).
+! LJMD_GPUS > 1 the program stops before an engine is created; every other output file is the same with and without it),
+! LJMD_VANHOVE_MAX_LAG (default 0 = off; > 0: the van Hove self-correlation of the resident system on the device --
+! ljmd_vanhove_*, over the same sampling instants, every LJMD_VANHOVE_ORIGIN_STRIDE-th of them (default 1) an origin,
+! LJMD_VANHOVE_BINS bins (default 128) up to LJMD_VANHOVE_RMAX (default half the box) -- and
+! outputs/one_run/van_hove_gpu.dat gets, per lag with at least one origin, lag, tau, the number of origins, <r^2>, <r^4>,
+! the non-Gaussian parameter, the overflow count and the row of counts; one-rank engines only: with LJMD_GPUS > 1 the
+! program stops before an engine is created; every other output file is the same with and without it).
 !==============================================================================
 program md_simulation_gpu
   use, intrinsic :: iso_c_binding
@@ -49,7 +55,7 @@ program md_simulation_gpu
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
   use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
-                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file
+                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file
   implicit none
 
   type(sim_params) :: params
@@ -89,6 +95,11 @@ program md_simulation_gpu
   real(c_double), allocatable, target :: heatflux_c(:, :), heatflux_acf(:)
   integer(c_int64_t) :: heatflux_snapshots
   real(kind=dp_kind) :: mean_temp, std_temp
+  integer :: vh_max_lag, vh_stride, vh_bins
+  real(kind=dp_kind) :: vh_rmax
+  real(c_double), allocatable, target :: vh_r2(:), vh_r4(:)                ! [vh_max_lag + 1]
+  integer(c_int64_t), allocatable, target :: vh_counts(:), vh_hist(:, :)   ! [vh_max_lag + 1], [vh_bins + 1, vh_max_lag + 1]
+  integer(c_int64_t) :: vh_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -140,6 +151,21 @@ program md_simulation_gpu
   call get_environment_variable('LJMD_HEATFLUX_MAX_LAG', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) heatflux_max_lag
   if (heatflux_max_lag < 0) stop 'md_simulation: LJMD_HEATFLUX_MAX_LAG must be >= 0.'
+  vh_max_lag = 0
+  call get_environment_variable('LJMD_VANHOVE_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_max_lag
+  if (vh_max_lag < 0) stop 'md_simulation: LJMD_VANHOVE_MAX_LAG must be >= 0.'
+  vh_stride = 1
+  call get_environment_variable('LJMD_VANHOVE_ORIGIN_STRIDE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_stride
+  if (vh_stride < 1) stop 'md_simulation: LJMD_VANHOVE_ORIGIN_STRIDE must be >= 1.'
+  vh_bins = 128
+  call get_environment_variable('LJMD_VANHOVE_BINS', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_bins
+  if (vh_bins < 1) stop 'md_simulation: LJMD_VANHOVE_BINS must be >= 1.'
+  vh_rmax = 0.5d0 * params%box_length
+  call get_environment_variable('LJMD_VANHOVE_RMAX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_rmax
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
@@ -147,6 +173,8 @@ program md_simulation_gpu
     error stop 'md_simulation: LJMD_TCF_MAX_LAG needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1 .and. heatflux_on) &
     error stop 'md_simulation: LJMD_HEATFLUX needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
+  if (n_gpus > 1 .and. vh_max_lag > 0) &
+    error stop 'md_simulation: LJMD_VANHOVE_MAX_LAG needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1) then
     allocate(device_list(n_gpus))
     device_list = [(int(k - 1, c_int32_t), k = 1, n_gpus)]
@@ -169,6 +197,8 @@ program md_simulation_gpu
                                     'ljmd_rdf_configure')
   if (tcf_max_lag > 0) call ljmd_check(ljmd_tcf_configure(engine, int(tcf_max_lag, c_int32_t), int(tcf_stride, c_int32_t)), &
                                        engine, 'ljmd_tcf_configure')
+  if (vh_max_lag > 0) call ljmd_check(ljmd_vanhove_configure(engine, int(vh_max_lag, c_int32_t), int(vh_stride, c_int32_t), &
+                                                             int(vh_bins, c_int32_t), vh_rmax), engine, 'ljmd_vanhove_configure')
   if (stress_on) then
     n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
     if (n_snapshots_expected < 1) stop 'md_simulation: LJMD_STRESS needs at least one sampling instant.'
@@ -228,6 +258,7 @@ program md_simulation_gpu
     ! g(r) of the same instant, on the device, ahead of the next segment in the engine's stream
     if (sample_now .and. rdf_bins > 0) call ljmd_check(ljmd_rdf_accumulate(engine), engine, 'ljmd_rdf_accumulate')
     if (sample_now .and. tcf_max_lag > 0) call ljmd_check(ljmd_tcf_accumulate(engine), engine, 'ljmd_tcf_accumulate')
+    if (sample_now .and. vh_max_lag > 0) call ljmd_check(ljmd_vanhove_accumulate(engine), engine, 'ljmd_vanhove_accumulate')
     if (sample_now .and. stress_on) then
       call ljmd_check(ljmd_stress_accumulate(engine), engine, 'ljmd_stress_accumulate')
       stress_times(num_samples + 1) = time
@@ -265,6 +296,11 @@ program md_simulation_gpu
     call ljmd_check(ljmd_tcf_read(engine, c_loc(tcf_msd), c_loc(tcf_vacf), c_loc(tcf_counts), tcf_snapshots), engine, &
                     'ljmd_tcf_read')
   end if
+  if (vh_max_lag > 0) then
+    allocate(vh_r2(0:vh_max_lag), vh_r4(0:vh_max_lag), vh_counts(0:vh_max_lag), vh_hist(0:vh_bins, 0:vh_max_lag))
+    call ljmd_check(ljmd_vanhove_read(engine, c_loc(vh_hist), c_loc(vh_r2), c_loc(vh_r4), c_loc(vh_counts), vh_snapshots), &
+                    engine, 'ljmd_vanhove_read')
+  end if
   if (stress_on) then
     allocate(stress_p(6, max(num_samples, 1)))
     call ljmd_check(ljmd_stress_read(engine, c_loc(stress_p), stress_snapshots), engine, 'ljmd_stress_read')
@@ -284,6 +320,8 @@ program md_simulation_gpu
                                         rdf_hist, rdf_snapshots)
   if (tcf_max_lag > 0) call write_msd_vacf_file('outputs/one_run/msd_vacf_gpu.dat', tcf_max_lag, output_interval, params%dt, &
                                                 tcf_counts, tcf_msd, tcf_vacf)
+  if (vh_max_lag > 0) call write_van_hove_file('outputs/one_run/van_hove_gpu.dat', params%n, vh_max_lag, vh_bins, vh_rmax, &
+                                               output_interval, params%dt, vh_counts, vh_r2, vh_r4, vh_hist)
   if (stress_on) then
     call write_pressure_tensor_file('outputs/one_run/pressure_tensor_gpu.dat', int(num_samples), stress_times, stress_p)
     if (stress_max_lag > 0 .and. num_samples >= 2) then

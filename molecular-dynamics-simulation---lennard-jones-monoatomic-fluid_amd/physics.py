@@ -432,6 +432,73 @@ class Engine:
         self._ck(self._lib.ljmd_tcf_profile_read(self._h, C.byref(ms), C.byref(live)))
         return {"kernel_ms": ms.value, "origins_live": live.value}
 
+    # -- van Hove self-correlation of the resident system (include/ljmd.h: ljmd_vanhove_*) ----
+    def vanhove_configure(self, max_lag: int, origin_stride: int = 1, nbins: int = 128, rmax=None) -> None:
+        """ljmd_vanhove_configure: the distribution G_s(r, tau) of the displacements behind the MSD, up to lag max_lag
+        (in snapshots), every origin_stride-th snapshot an origin, nbins bins up to rmax (None = half the box) and an
+        overflow column; max_lag = 0 switches the feature off.  Zeroes everything.  One-rank engines only."""
+        for name, val in (("max_lag", max_lag), ("origin_stride", origin_stride), ("nbins", nbins)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise TypeError(f"vanhove_configure: {name} must be an integer, got {val!r}")
+        if rmax is not None and (isinstance(rmax, bool) or not isinstance(rmax, (int, float, np.integer, np.floating))):
+            raise TypeError(f"vanhove_configure: rmax must be a number, got {rmax!r}")
+        r = 0.5 * self.params.box_length if rmax is None else float(rmax)
+        self._ck(self._lib.ljmd_vanhove_configure(self._h, int(max_lag), int(origin_stride), int(nbins), r))
+        self._vanhove_shape = (int(max_lag), int(nbins))
+
+    def vanhove_accumulate(self) -> None:
+        """takes the resident ru as the next snapshot (stream-ordered: no host wait)"""
+        self._ck(self._lib.ljmd_vanhove_accumulate(self._h))
+
+    def _vanhove_rows(self, who: str):
+        max_lag, nbins = getattr(self, "_vanhove_shape", (0, 0))
+        if max_lag < 1:
+            raise ValueError(f"{who}: call vanhove_configure with max_lag >= 1 first")
+        return max_lag + 1, nbins + 1
+
+    def vanhove_read(self):
+        """-> (hist[max_lag + 1, nbins + 1] uint64 with the overflow column last, r2[max_lag + 1], r4[max_lag + 1],
+        counts[max_lag + 1] int64, n_snapshots); nothing is cleared"""
+        rows, cols = self._vanhove_rows("vanhove_read")
+        hist = np.empty((rows, cols), dtype=np.uint64)
+        r2 = np.empty(rows, dtype=np.float64)
+        r4 = np.empty(rows, dtype=np.float64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_vanhove_read(self._h, hist.ctypes.data_as(C.POINTER(C.c_uint64)), r2.ctypes.data_as(c_double_p),
+                                             r4.ctypes.data_as(c_double_p), counts.ctypes.data_as(_lib.c_int64_p),
+                                             C.byref(snaps)))
+        return hist, r2, r4, counts, snaps.value
+
+    def vanhove_read_exact(self, raw: bool = False):
+        """-> (hist, sums, counts, n_snapshots): the counts and the exact integer sums of Q(t) = RNE(t 2^64), sums[kind,
+        lag] with kind 0 = r^2, 1 = r^4, as Python ints in an object array -- or, raw=True, the library's int64 words
+        [2, max_lag + 1, 3] (three little-endian limbs of a signed 192-bit integer)"""
+        rows, cols = self._vanhove_rows("vanhove_read_exact")
+        hist = np.empty((rows, cols), dtype=np.uint64)
+        words = np.empty((2, rows, 3), dtype=np.int64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_vanhove_read_exact(self._h, hist.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                   words.ctypes.data_as(_lib.c_int64_p),
+                                                   counts.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        if raw:
+            return hist, words, counts, snaps.value
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:2], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return hist, sums, counts, snaps.value
+
+    def vanhove_reset(self) -> None:
+        self._ck(self._lib.ljmd_vanhove_reset(self._h))
+
+    def vanhove_profile(self) -> dict:
+        """ljmd_vanhove_profile_read for the most recent vanhove_accumulate -> {'kernel_ms', 'origins_live'}"""
+        ms, live = C.c_double(), C.c_int32()
+        self._ck(self._lib.ljmd_vanhove_profile_read(self._h, C.byref(ms), C.byref(live)))
+        return {"kernel_ms": ms.value, "origins_live": live.value}
+
     # -- pressure tensor of the resident system (include/ljmd.h: ljmd_stress_*) ---------------
     def stress_configure(self, max_snapshots: int) -> None:
         """ljmd_stress_configure: room for max_snapshots snapshots of the pressure tensor on the device; 0 switches the
