@@ -93,6 +93,7 @@ Knobs read_knobs()
     k.inject_failure_at_step = env_int("LJMD_INJECT_FAILURE_AT_STEP", k.inject_failure_at_step);
     k.exchange_alltoall = is("LJMD_FORCE_EXCHANGE", "alltoall");
     k.resort_every = opt_int("LJMD_RESORT_EVERY");
+    k.kd_sort_cub = is("LJMD_KD_SORT", "cub");
     k.n3_row_tiles = env_int("LJMD_N3_ROW_TILES", k.n3_row_tiles);
     k.n3_wg_waves = env_int("LJMD_N3_WG_WAVES", k.n3_wg_waves);
     k.slab_budget_gb = std::max(1, env_int("LJMD_SLAB_BUDGET_GB", k.slab_budget_gb));

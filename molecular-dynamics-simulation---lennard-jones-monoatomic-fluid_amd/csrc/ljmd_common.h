@@ -114,6 +114,7 @@ struct Knobs {
     int inject_failure_at_step = -1;        // LJMD_INJECT_FAILURE_AT_STEP: initial value of ljmd::inject_failure_at (tests)
     bool exchange_alltoall = false;         // LJMD_FORCE_EXCHANGE=alltoall: direct sends + local rank-order sum
     std::optional<int> resort_every;        // LJMD_RESORT_EVERY: steps between two re-sorts (unset: by system size)
+    bool kd_sort_cub = false;               // LJMD_KD_SORT=cub: every k-d level of a re-sort takes the library sort (A/B tests)
     int n3_row_tiles = 0;                   // LJMD_N3_ROW_TILES: tiles per row group (1, 2, 4; else by system size)
     int n3_wg_waves = 0;                    // LJMD_N3_WG_WAVES: row groups per pair-kernel workgroup (1, 2, 4; else by slab size)
     int slab_budget_gb = 64;                // LJMD_SLAB_BUDGET_GB: column slab above which more waves share a workgroup

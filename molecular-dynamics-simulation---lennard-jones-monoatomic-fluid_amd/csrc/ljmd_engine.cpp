@@ -177,34 +177,59 @@ EventSet *next_events(ljmd_t *h)
     return q;
 }
 
-// Spatial re-ordering of the owned shard: keys -> stable radix sort -> gather r, ru, v (+ a when
+// Spatial re-ordering of the owned shard: keys -> stable sort -> gather r, ru, v (+ a when
 // asked) and compose the slot->original permutation.  Performance only (ljmd_sort.hip).
 int resort(ljmd_t *h, bool with_accel)
 {
-    {
-    // recursive median split (ljmd_sort.hip): one composite-key radix sort per level, along the axis
-    // chosen for that level at set_state (longest remaining extent of the shard)
-    LJMD_HIP(h, launch_iota(h->d_idx, h->plan.P, h->stream));
-    LJMD_HIP(h, hipMemcpyAsync(h->d_idx2, h->d_idx, (size_t)h->plan.P * sizeof(int), hipMemcpyDeviceToDevice,
-                               h->stream));   // slots S..P-1 (padding) keep their identity in both buffers
+    if (!launch_kd_finish || !launch_gather_state)
+        return fail(h, LJMD_ERR_HIP, "resort: this build holds no launch_kd_finish / launch_gather_state (ljmd_sort.h)");
+    // recursive median split (ljmd_sort.hip) along the axis chosen for each level at set_state (longest remaining extent
+    // of the shard): one composite-key radix sort of the whole shard per level while a segment is larger than a workgroup
+    // of kd_finish_kernel sorts, then every remaining level in that kernel
+    const int levels = (int)h->plan.kd_level_nseg.size(), from = h->plan.kd_finish_from;
     int *cur = h->d_idx, *nxt = h->d_idx2;
-    for (size_t l = 0; l < h->plan.kd_level_nseg.size(); ++l) {
+    LJMD_HIP(h, launch_iota(cur, h->plan.P, h->stream));
+    if (from > 0) LJMD_HIP(h, launch_iota(nxt, h->plan.P, h->stream));   // slots S..P-1 (padding) keep their identity in both
+    for (int l = 0; l < from; ++l) {
         const double *axis = own_block(h) + (size_t)h->kd_axis[l] * h->plan.P;
         LJMD_HIP(h, kd_level(h->d_cub, h->cub_bytes, axis, h->L, h->d_kd_keys, h->d_kd_keys2, cur, nxt, h->plan.S,
                              h->plan.kd_level_nseg[l], h->d_kd_offsets + h->plan.kd_level_off[l], h->stream));
         std::swap(cur, nxt);
     }
-    if (cur != h->d_idx2)
-        LJMD_HIP(h, hipMemcpyAsync(h->d_idx2, cur, (size_t)h->plan.P * sizeof(int), hipMemcpyDeviceToDevice,
-                                   h->stream));
+    for (int l = from; l < levels; l += kKdFinishMaxLevels) {            // (one launch: 64 tiles halve to one in 6 levels)
+        KdFinishArgs ka;
+        ka.pos = own_block(h);
+        ka.P = h->plan.P;
+        ka.scale = (double)(1u << kCoordBits) / h->L;
+        ka.idx_in = ka.idx_out = cur;
+        ka.offsets = h->d_kd_offsets;
+        ka.nlevels = std::min(kKdFinishMaxLevels, levels - l);
+        for (int k = 0; k < ka.nlevels; ++k) {
+            ka.nseg[k] = h->plan.kd_level_nseg[l + k];
+            ka.off[k] = (int)h->plan.kd_level_off[l + k];
+            ka.axis[k] = h->kd_axis[l + k];
+        }
+        LJMD_HIP(h, launch_kd_finish(ka, h->stream));
     }
-    const size_t bytes3 = 3 * (size_t)h->plan.P * sizeof(double);
-    double *sets[4] = {own_block(h), h->d_ru, h->d_v, h->d_a};
-    for (int k = 0; k < (with_accel ? 4 : 3); ++k) {
-        LJMD_HIP(h, launch_gather3(sets[k], h->d_tmp3, h->d_idx2, h->plan.P, h->stream));
-        LJMD_HIP(h, hipMemcpyAsync(sets[k], h->d_tmp3, bytes3, hipMemcpyDeviceToDevice, h->stream));
+    // everything that follows the permutation in one launch; ru, v, a trade places with their scratch sets, the positions
+    // go back into the exchange buffer, whose block is not the engine's to move
+    GatherStateArgs g;
+    double *sets[4] = {own_block(h), h->d_ru, h->d_v, with_accel ? h->d_a : nullptr};
+    double *outs[4] = {h->d_tmp3, h->d_ru2, h->d_v2, h->d_a2};
+    for (int k = 0; k < 4; ++k) {
+        g.src[k] = sets[k];
+        g.dst[k] = outs[k];
     }
-    LJMD_HIP(h, launch_gather_perm(h->d_perm, h->d_perm2, h->d_idx2, h->plan.P, h->stream));
+    g.perm = h->d_perm;
+    g.perm_out = h->d_perm2;
+    g.idx = cur;
+    g.P = h->plan.P;
+    LJMD_HIP(h, launch_gather_state(g, h->stream));
+    LJMD_HIP(h, hipMemcpyAsync(own_block(h), h->d_tmp3, 3 * (size_t)h->plan.P * sizeof(double), hipMemcpyDeviceToDevice,
+                               h->stream));
+    std::swap(h->d_ru, h->d_ru2);
+    std::swap(h->d_v, h->d_v2);
+    if (with_accel) std::swap(h->d_a, h->d_a2);
     std::swap(h->d_perm, h->d_perm2);
     h->perm_dirty = true;
     h->steps_since_sort = 0;

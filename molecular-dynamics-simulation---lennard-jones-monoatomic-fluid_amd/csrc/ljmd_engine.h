@@ -19,6 +19,7 @@
 
 #include "ljmd_internal.h"
 #include "ljmd_resident.h"
+#include "ljmd_sort.h"
 
 using namespace ljmdk;
 
@@ -59,6 +60,8 @@ struct LaunchPlan {
     std::vector<int> kd_level_nseg;       // segments at level l
     std::vector<size_t> kd_level_off;     // offset of level l's boundaries inside kd_offsets
     std::vector<int> kd_offsets;          // uploaded to d_kd_offsets
+    int kd_finish_from = 0;               // levels below this one take the library sort, it and the later ones
+                                          // kd_finish_kernel (ljmd_sort.h); = number of levels: none does (LJMD_KD_SORT=cub)
     int nslab_g = 1, chunk_g = 0;     // generic kernel: grid (P/256, nslab_g), chunk_g j per slice
     int nslab_t = 1, chunk_t = 0;     // tile kernel:    grid (TB/4, nslab_t), chunk_t column tiles per slice
     // Newton-3 kernel (single rank): NG row groups, offsets 0..Dmax in nslab_n slices of dchunk
@@ -150,6 +153,7 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     // sorting scratch
     int *d_idx = nullptr, *d_idx2 = nullptr, *d_perm = nullptr, *d_perm2 = nullptr;
     double *d_tmp3 = nullptr;     // [3][P]
+    double *d_ru2 = nullptr, *d_v2 = nullptr, *d_a2 = nullptr;   // [3][P]: a re-sort gathers into them and swaps each with its set
     void *d_cub = nullptr;
     size_t cub_bytes = 0;
     std::vector<int> kd_axis;             // k-d ordering: split axis of level l, always the longest remaining extent

@@ -316,8 +316,7 @@ hipError_t launch_migrate_pack(const double *ru, const double *v, const double *
                                double *block, int S, int P, hipStream_t s);
 hipError_t launch_migrate_select(const double *pos_all, const double *mig_all, const int *mine, double *new_pos, double *ru,
                                  double *v, double *a, int *gid0, int S, int P, hipStream_t s);
-hipError_t launch_gather3(const double *src, double *dst, const int *idx, int P, hipStream_t s);
-hipError_t launch_gather_perm(const int *src, int *dst, const int *idx, int P, hipStream_t s);
+// (the launches that finish a re-sort, launch_kd_finish and launch_gather_state: ljmd_sort.h)
 
 // ---- device arithmetic shared by the kernel files ----
 // The device functions whose exact sequence of roundings is part of the documented results, ONE copy each for

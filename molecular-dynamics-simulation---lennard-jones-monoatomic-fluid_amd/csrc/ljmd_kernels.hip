@@ -1591,13 +1591,24 @@ __global__ __launch_bounds__(kBlock) void tile_mask_kernel(GeometryArgs a)
     if (lane == 0) a.mask[(size_t)Il * a.W + w] = word;
 }
 
+// column tiles of the offsets 0 .. NG / 2 of a row group, NG = T / RT row groups in all
+__host__ __device__ constexpr int tile_class_columns(int T, int RT)
+{
+    const int n = ((T / RT) / 2 + 1) * RT;
+    return n < T ? n : T;
+}
+
 template <int RT>
 __global__ __launch_bounds__(kBlock) void tile_class_kernel(GeometryArgs a, double invL, double rc2, int S, unsigned *desc,
                                                             unsigned *desc_far, float *desc2)
 {
-    const int c = blockIdx.x * kBlock + threadIdx.x;           // column tile (global)
+    // the grid covers the column groups the pair kernel can visit from a row group, offsets 0 .. NG / 2 (tile_class's
+    // ownership test, which still decides the tie at NG / 2), not the other half of the row
     const int Al = blockIdx.y;                                 // owned row group
-    if (c >= a.T) return;
+    const int j = blockIdx.x * kBlock + threadIdx.x;           // column tile, counted from the row group's first
+    if (j >= tile_class_columns(a.T, RT)) return;
+    int c = (a.rank * (a.TB / RT) + Al) * RT + j;              // column tile (global)
+    if (c >= a.T) c -= a.T;
     unsigned d = 0;
     if (tile_class<RT>(a, invL, rc2, S, Al, c, d, desc_far, desc2)) desc[(size_t)Al * a.T + c] = d;
 }
@@ -2473,7 +2484,7 @@ hipError_t launch_tile_mask(const GeometryArgs &a, hipStream_t s)
 hipError_t launch_tile_class(const GeometryArgs &a, double invL, double rc2, int S, int NGo, unsigned *desc, unsigned *desc_far,
                              float *desc2, hipStream_t s)
 {
-    const dim3 grid((a.T + kBlock - 1) / kBlock, NGo);
+    const dim3 grid((tile_class_columns(a.T, a.RT) + kBlock - 1) / kBlock, NGo);
     if (a.RT == 1)
         hipLaunchKernelGGL(tile_class_kernel<1>, grid, dim3(kBlock), 0, s, a, invL, rc2, S, desc, desc_far, desc2);
     else if (a.RT == 2)

@@ -58,6 +58,17 @@ int plan_engine(const SimParams &sim, int n, int n_ranks, int precision_mode, co
             next.push_back(tiles);
             bounds.swap(next);
         }
+        // the first level whose largest segment fits one workgroup of kd_finish_kernel: it and the later ones (segments
+        // only shrink) are sorted there, the levels above by the library
+        const int levels = (int)p.kd_level_nseg.size();
+        p.kd_finish_from = levels;
+        for (int l = levels - 1; l >= 0 && !k.kd_sort_cub; --l) {
+            int largest = 0;
+            for (int j = 0; j < p.kd_level_nseg[l]; ++j)
+                largest = std::max(largest, p.kd_offsets[p.kd_level_off[l] + j + 1] - p.kd_offsets[p.kd_level_off[l] + j]);
+            if (largest > kKdFinishCap) break;
+            p.kd_finish_from = l;
+        }
     }
 
     // launch geometry: rows x slices >= kTargetWorkgroups

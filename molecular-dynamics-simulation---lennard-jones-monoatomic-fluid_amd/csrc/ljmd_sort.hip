@@ -9,23 +9,22 @@
 #include <hipcub/hipcub.hpp>
 
 #include "ljmd_internal.h"
+#include "ljmd_sort.h"
 
 namespace ljmdk {
 
-__global__ __launch_bounds__(kBlock) void gather3_kernel(const double *src, double *dst, const int *idx, int P)
+__global__ __launch_bounds__(kBlock) void gather_state_kernel(GatherStateArgs g)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= P) return;
-    const int s = idx[i];
-    dst[i] = src[s];
-    dst[P + i] = src[P + s];
-    dst[2 * (size_t)P + i] = src[2 * (size_t)P + s];
-}
-
-__global__ __launch_bounds__(kBlock) void gather_perm_kernel(const int *src, int *dst, const int *idx, int P)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < P) dst[i] = src[idx[i]];
+    if (i >= g.P) return;
+    const int s = g.idx[i];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (g.src[q] == nullptr) continue;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g.dst[q][(size_t)k * g.P + i] = g.src[q][(size_t)k * g.P + s];
+    }
+    g.perm_out[i] = g.perm[s];
 }
 
 // ---- k-d ordering: recursive median split, exactly 64 particles per leaf ---------------
@@ -37,7 +36,13 @@ __global__ __launch_bounds__(kBlock) void gather_perm_kernel(const int *src, int
 // key = (segment index << 24) | coordinate quantised to 24 bits: ONE ordinary radix sort per level
 // orders every segment along the axis at once.  (A segmented sort of raw doubles gives the same
 // order but is ~20x slower in rocPRIM for thousands of small segments.)
-constexpr int kCoordBits = 24;
+
+// the coordinate part of a key, for every kernel that builds one: scale = 2^kCoordBits / L (ljmd_sort.h)
+__device__ __forceinline__ unsigned long long kd_quant(double coord, double scale)
+{
+    const double x = coord * scale;
+    return (unsigned long long)fmin(fmax(x, 0.0), (double)((1u << kCoordBits) - 1));
+}
 
 __global__ __launch_bounds__(kBlock) void kd_keys_kernel(const double *coord, const int *idx, unsigned long long *keys,
                                                          const int *seg_offsets, int nseg, int S, double scale)
@@ -49,9 +54,7 @@ __global__ __launch_bounds__(kBlock) void kd_keys_kernel(const double *coord, co
         const int mid = (lo + hi) >> 1;
         if (seg_offsets[mid] <= i) lo = mid; else hi = mid;
     }
-    const double x = coord[idx[i]] * scale;             // scale = 2^24 / L
-    const unsigned long long q = (unsigned long long)fmin(fmax(x, 0.0), (double)((1u << kCoordBits) - 1));
-    keys[i] = ((unsigned long long)lo << kCoordBits) | q;
+    keys[i] = ((unsigned long long)lo << kCoordBits) | kd_quant(coord[idx[i]], scale);
 }
 
 __global__ __launch_bounds__(kBlock) void iota_kernel(int *idx, int P)
@@ -89,6 +92,121 @@ hipError_t kd_level(void *temp, size_t temp_bytes, const double *coord_axis, dou
                                               kCoordBits + segbits, s);
 }
 
+// ---- the lower k-d levels in one launch -------------------------------------------------
+// From the first level whose largest segment fits kKdFinishCap slots, one workgroup owns one segment of that level: the
+// segments of every later level lie inside it, so it sorts its slice of the index array level after level in LDS and
+// writes it back once.  A level is the same stable sort as kd_level's: by (segment, quantised coordinate), ties in their
+// current order.  The current position is made part of the sort word, which makes the words distinct, so the order a
+// bitonic network leaves is that stable order and the permutation equals the library sort's for every input.
+// sort word: [63:56] segment of this level inside the slice (< 64), [55:32] kd_quant, [31:16] current position in the
+// slice, [15:0] position the slot had when the kernel started (the index array's slice stays where it was loaded).
+// 48 KB of LDS, 16 waves: one workgroup per CU, 64 of them at n = 262144 (0.17 ms for six levels).
+
+// largest j in [0, n) with b[j] <= x; b ascending, b[0] <= x
+__device__ __forceinline__ int last_at_most(const int *b, int n, int x)
+{
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (b[mid] <= x) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// one compare-exchange of a bitonic network: x before y in the direction `up`
+__device__ __forceinline__ void order_pair(unsigned long long &x, unsigned long long &y, bool up)
+{
+    if ((x > y) == up) {
+        const unsigned long long t = x;
+        x = y;
+        y = t;
+    }
+}
+
+__global__ __launch_bounds__(kKdFinishBlock) void kd_finish_kernel(KdFinishArgs a)
+{
+    constexpr int kMaxSub = kKdFinishCap / kTile;        // segments of a level inside one slice
+    __shared__ unsigned long long s_word[kKdFinishCap];
+    __shared__ int s_idx[kKdFinishCap];
+    __shared__ int s_bound[kKdFinishMaxLevels][kMaxSub + 1];
+    __shared__ int s_first[kKdFinishMaxLevels], s_last[kKdFinishMaxLevels];
+    const int tid = threadIdx.x;
+    const int lo = a.offsets[a.off[0] + blockIdx.x], len = a.offsets[a.off[0] + blockIdx.x + 1] - lo;
+    if (len <= 0 || len > kKdFinishCap) return;          // (the host moves a level here only if every segment fits)
+    int npad = kTile;
+    while (npad < len) npad <<= 1;
+    for (int p = tid; p < len; p += kKdFinishBlock) s_idx[p] = a.idx_in[lo + p];
+    // every level's boundaries inside the slice, relative to lo, up front: the levels nest, so lo and lo + len are among
+    // the boundaries of each (searched by all threads at once: a chain of dependent loads per level costs more)
+    if (tid < kKdFinishMaxLevels) s_first[tid] = s_last[tid] = 0;
+    __syncthreads();
+    for (int l = 0; l < a.nlevels; ++l)
+        for (int j = tid; j <= a.nseg[l]; j += kKdFinishBlock) {
+            const int b = a.offsets[a.off[l] + j];
+            if (b == lo) s_first[l] = j;
+            if (b == lo + len) s_last[l] = j;
+        }
+    __syncthreads();
+    for (int l = 0; l < a.nlevels; ++l) {
+        const int nsub = min(s_last[l] - s_first[l], kMaxSub);
+        if (tid <= nsub) s_bound[l][tid] = a.offsets[a.off[l] + s_first[l] + tid] - lo;
+    }
+    __syncthreads();
+    for (int l = 0; l < a.nlevels; ++l) {
+        const int nsub = min(s_last[l] - s_first[l], kMaxSub);
+        const double *coord = a.pos + (size_t)a.axis[l] * a.P;
+        for (int p = tid; p < npad; p += kKdFinishBlock) {
+            unsigned long long w = ~0ull;                // padding: behind every slot of the slice
+            if (p < len) {
+                const unsigned home = l == 0 ? (unsigned)p : (unsigned)(s_word[p] & 0xffffu);
+                const int sub = last_at_most(s_bound[l], nsub, p);
+                w = ((unsigned long long)sub << 56) | (kd_quant(coord[s_idx[home]], a.scale) << 32) |
+                    ((unsigned long long)p << 16) | home;
+            }
+            s_word[p] = w;
+        }
+        __syncthreads();
+        for (int k = 2; k <= npad; k <<= 1) {
+            int j = k >> 1;
+            for (; j >= 2; j >>= 2) {                    // stages j and j / 2 in one pass over LDS: a thread holds the
+                const int h = j >> 1;                    // four words whose positions differ in those two bits
+                for (int t = tid; t < (npad >> 2); t += kKdFinishBlock) {
+                    const int i = ((t & ~(h - 1)) << 2) | (t & (h - 1));
+                    const bool up = (i & k) == 0;
+                    unsigned long long w0 = s_word[i], w1 = s_word[i | h], w2 = s_word[i | j], w3 = s_word[i | j | h];
+                    order_pair(w0, w2, up);
+                    order_pair(w1, w3, up);
+                    order_pair(w0, w1, up);
+                    order_pair(w2, w3, up);
+                    s_word[i] = w0;
+                    s_word[i | h] = w1;
+                    s_word[i | j] = w2;
+                    s_word[i | j | h] = w3;
+                }
+                __syncthreads();
+            }
+            if (j == 1) {                                // an odd number of stages: the last one alone
+                for (int t = tid; t < (npad >> 1); t += kKdFinishBlock) {
+                    const int i = t << 1;
+                    unsigned long long w0 = s_word[i], w1 = s_word[i | 1];
+                    order_pair(w0, w1, (i & k) == 0);
+                    s_word[i] = w0;
+                    s_word[i | 1] = w1;
+                }
+                __syncthreads();
+            }
+        }
+    }
+    for (int p = tid; p < len; p += kKdFinishBlock) a.idx_out[lo + p] = s_idx[s_word[p] & 0xffffu];
+}
+
+hipError_t launch_kd_finish(const KdFinishArgs &a, hipStream_t s)
+{
+    if (a.nlevels < 1 || a.nlevels > kKdFinishMaxLevels) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kd_finish_kernel, dim3(a.nseg[0]), dim3(kKdFinishBlock), 0, s, a);
+    return hipGetLastError();
+}
+
 // ---- ownership migration (multi-GPU): the particles of ALL ranks dealt out again by position -----------------------
 // Every rank holds all n positions (exchange buffer [G][3][P], real particles in slots 0..S-1 of each block) and, after
 // one all-gather, everybody's ru, v, a and particle ids (migration buffer [G][10][P]).  The deal is a k-d split of the
@@ -114,9 +232,7 @@ __global__ __launch_bounds__(kBlock) void kd_keys_blocked_kernel(const double *p
         if (seg_offsets[mid] <= i) lo = mid; else hi = mid;
     }
     const int st = idx[i], g = st / P, sl = st - g * P;
-    const double x = pos[(size_t)g * 3 * P + (size_t)axis * P + sl] * scale;
-    const unsigned long long q = (unsigned long long)fmin(fmax(x, 0.0), (double)((1u << kCoordBits) - 1));
-    keys[i] = ((unsigned long long)lo << kCoordBits) | q;
+    keys[i] = ((unsigned long long)lo << kCoordBits) | kd_quant(pos[(size_t)g * 3 * P + (size_t)axis * P + sl], scale);
 }
 
 // own block of the migration buffer: ru, v, a and the particle id of every slot (id < 0: padding)
@@ -214,15 +330,9 @@ hipError_t launch_migrate_select(const double *pos_all, const double *mig_all, c
     return hipGetLastError();
 }
 
-hipError_t launch_gather3(const double *src, double *dst, const int *idx, int P, hipStream_t s)
+hipError_t launch_gather_state(const GatherStateArgs &g, hipStream_t s)
 {
-    hipLaunchKernelGGL(gather3_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, src, dst, idx, P);
-    return hipGetLastError();
-}
-
-hipError_t launch_gather_perm(const int *src, int *dst, const int *idx, int P, hipStream_t s)
-{
-    hipLaunchKernelGGL(gather_perm_kernel, dim3((P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, src, dst, idx, P);
+    hipLaunchKernelGGL(gather_state_kernel, dim3((g.P + kBlock - 1) / kBlock), dim3(kBlock), 0, s, g);
     return hipGetLastError();
 }
 

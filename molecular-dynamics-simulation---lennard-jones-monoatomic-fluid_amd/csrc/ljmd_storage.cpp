@@ -16,6 +16,11 @@ int allocate_engine(ljmd_t *h)
     LJMD_HIP(h, hipMalloc(&h->d_v, P3));
     LJMD_HIP(h, hipMalloc(&h->d_a, P3));
     LJMD_HIP(h, hipMalloc(&h->d_tmp3, P3));
+    if (h->plan.sort_enabled) {
+        LJMD_HIP(h, hipMalloc(&h->d_ru2, P3));
+        LJMD_HIP(h, hipMalloc(&h->d_v2, P3));
+        LJMD_HIP(h, hipMalloc(&h->d_a2, P3));
+    }
     LJMD_HIP(h, hipMalloc(&h->d_slab, P3 * h->plan.nslab_max));
     h->wg_part_stride = 2 * (size_t)h->plan.n_wg_max;
     LJMD_HIP(h, hipMalloc(&h->d_wg_part, (h->plan.fuse_tail ? 2 : 1) * h->wg_part_stride * sizeof(double)));
@@ -124,7 +129,7 @@ void release(ljmd_t *h)
         for (auto &e : q.e) (void)hipEventDestroy(e);
     void *dev[] = {h->d_pos, h->d_ru, h->d_v, h->d_a, h->d_slab, h->d_wg_part, h->d_ke_part, h->d_ring,
                    h->d_ring_pos, h->d_bbox, h->d_mask, h->d_idx, h->d_idx2,
-                   h->d_perm, h->d_perm2, h->d_tmp3, h->d_cub, h->d_slab_j, h->d_flag_j, h->d_fpart, h->d_frecv, h->d_fall,
+                   h->d_perm, h->d_perm2, h->d_tmp3, h->d_ru2, h->d_v2, h->d_a2, h->d_cub, h->d_slab_j, h->d_flag_j, h->d_fpart, h->d_frecv, h->d_fall,
                    h->d_kd_offsets, h->d_kd_keys, h->d_kd_keys2, h->d_mask_far, h->d_slab_j2, h->d_flag_j2, h->d_fold, h->d_ticket,
                    h->d_desc, h->d_desc_far, h->d_desc2, h->d_red_part, h->d_ke_tile, h->d_pos_tc, h->d_gid0, h->d_mig, h->d_mig_idx, h->d_mig_idx2, h->d_mig_keys,
                    h->d_mig_keys2, h->d_mig_offsets, h->d_mig_cub, h->d_fslab, h->d_fflag, h->d_fblk, h->d_frec};
