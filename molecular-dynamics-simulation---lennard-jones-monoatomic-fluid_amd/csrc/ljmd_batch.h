@@ -137,6 +137,22 @@ struct BatchTcfArgs {
 };
 hipError_t launch_batch_tcf(const BatchTcfArgs &a, int n_max, int n_blocks, hipStream_t s);
 
+// A series of snapshots of exact integer sums -- the pressure tensor (ljmd_batch_stress.h) and the heat flux
+// (ljmd_batch_heatflux.h): one snapshot of every replica of a launch, the replica's resident wrapped r and v -> its sums
+// in row (row, b) of the series, the workgroup being that row's only writer.  Same launch geometry as launch_batch.
+struct BatchSeriesArgs {
+    const double *state;    // [12][plane]: r = planes 0..2, v = planes 6..8
+    uint64_t *words;        // [rows][B][words of the observable] signed 192-bit, sample-major
+    int32_t *range;         // [B] sticky: set to 1 when a pair or a particle of replica b was out of range
+    const BatchReplica *rep;
+    size_t plane;
+    size_t B;               // replicas of the handle (row stride)
+    int64_t row;            // snapshot this launch writes, 0 <= row < rows
+    int64_t rows;           // snapshots the series holds
+    int g0;
+};
+using BatchSeriesLauncher = hipError_t (*)(const BatchSeriesArgs &a, int n_max, int n_blocks, hipStream_t s);
+
 }  // namespace ljmdb
 
 #endif  // LJMD_BATCH_KERNEL_H

@@ -3,8 +3,8 @@
 // replica of a launch, one workgroup per replica.
 //
 // Per replica b, with its own n, L and rc, exactly the 9 integers of ljmd_heatflux_* (ljmd_heatflux.hip) for one system:
-// the per-pair and per-particle arithmetic is the one copy of ljmd_heatflux_arith.h, the minimum image, Q(t) =
-// RNE(t 2^64), the range rule and the 192-bit sums that of ljmd_stress_arith.h, compiled with -ffp-contract=off
+// the per-pair and per-particle arithmetic is the one copy of ljmd_heatflux_arith.h, the minimum image that of
+// ljmd_stress_arith.h, Q(t) = RNE(t 2^64) and the 192-bit sums that of ljmd_sum192.h, compiled with -ffp-contract=off
 // (csrc/Makefile).  Integer sums depend on no order: not on B, on the replica's slot, on the grouping into launches, on
 // the streams, on the precision mode or on the order of the particles.
 //
@@ -16,28 +16,29 @@
 // planes in LDS, 96 KB for 2048 columns.  The 4096 class therefore walks its columns in two chunks of
 // kBatchHeatfluxChunk with a barrier between, j > i and the wave's start rule applied inside each chunk; the other
 // classes have one chunk and no such barrier.  Six 128-bit accumulators per thread run across its K passes (at most
-// 4 * 4095 terms below 2^104), three more take the particle terms.  Then 192 bits: integer shuffles across the wave, the
-// replica's T / 64 waves through LDS after ONE barrier, and threads 0..8 store the 9 sums into the replica's row of the
-// snapshot, which no other workgroup writes; the range flag is ORed into the replica's own sticky word by a plain store.
+// 4 * 4095 terms below 2^104), three more take the particle terms.  Then 192 bits (ljmd_sum192.h): integer shuffles
+// across the wave, the replica's T / 64 waves through LDS after ONE barrier, and threads 0..8 store the 9 sums into the
+// replica's row of the snapshot, which no other workgroup writes; the range flag is ORed into the replica's own sticky
+// word by a plain store.
 // No global atomics, no floating-point atomics, no spin-waits, no dependency between workgroups.
 #include "ljmd_batch_heatflux.h"
 
 #include "ljmd_heatflux_arith.h"
 #include "ljmd_internal.h"
 #include "ljmd_stress_arith.h"
+#include "ljmd_sum192.h"
 
 namespace ljmdb {
 namespace {
 
-using ljmdk::add192;
 using ljmdk::add_six;
-using ljmdk::from128;
 using ljmdk::heatflux_add_kinetic;
 using ljmdk::heatflux_terms;
 using ljmdk::kHeatfluxKinTerms;
 using ljmdk::kHeatfluxPairTerms;
+using ljmdk::replica_lanes192;
+using ljmdk::replica_rows192;
 using ljmdk::stress_image;
-using ljmdk::wave_sum192;
 
 static_assert(kBatchHeatfluxRows == kHeatfluxKinTerms + kHeatfluxPairTerms, "E[3], then P[3], C[3]");
 static_assert(kBatchHeatfluxWords == kBatchHeatfluxRows * 3, "three limbs a sum");
@@ -105,42 +106,8 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_heatflux_kernel(BatchH
         }
     }
 
-    if (tid < T) {
-        // lanes -> wave, in 192 bits: E[3], then P[3], C[3] with both orders of every pair
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < kBatchHeatfluxRows; ++c) {
-            uint64_t q[3];
-            from128(q, c < kHeatfluxKinTerms ? kin[c] : pair[c - kHeatfluxKinTerms]);
-            if (c >= kHeatfluxKinTerms) {
-                const uint64_t o[3] = {q[0], q[1], q[2]};
-                add192(q, o);
-            }
-            wave_sum192(q);
-            if (lane == 0) {
-                wsum[wave][c][0] = q[0];
-                wsum[wave][c][1] = q[1];
-                wsum[wave][c][2] = q[2];
-            }
-        }
-    }
-    const int any_bad = __syncthreads_or(bad ? 1 : 0);          // the one barrier: wsum is complete behind it
-
-    // waves -> replica: thread c adds sum c over the replica's T / 64 waves into row (a.row, b)
-    if (tid < kBatchHeatfluxRows) {
-        const int c = tid;
-        uint64_t q[3] = {wsum[0][c][0], wsum[0][c][1], wsum[0][c][2]};
-        for (int w = 1; w < T / 64; ++w) {
-            const uint64_t o[3] = {wsum[w][c][0], wsum[w][c][1], wsum[w][c][2]};
-            add192(q, o);
-        }
-        uint64_t *const dst = a.words + (((size_t)a.row * a.B + b) * kBatchHeatfluxRows + c) * 3;
-        dst[0] = q[0];
-        dst[1] = q[1];
-        dst[2] = q[2];
-    } else if (tid == kBatchHeatfluxRows && any_bad) {
-        a.range[b] = 1;
-    }
+    if (tid < T) replica_lanes192(kin, pair, wsum);     // E[3], then P[3], C[3] with both orders of every pair
+    replica_rows192(bad, T, wsum, a.words, a.row, a.B, b, a.range);
 }
 
 }  // namespace

@@ -1,7 +1,8 @@
 // ljmd_batch_host.h -- what the host files of the batch engine share (ljmd_batch.cpp: lifecycle, planning, step loop;
-// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF; ljmd_stress_batch.cpp: pressure tensor;
-// ljmd_heatflux_batch.cpp: heat flux): the handle, the entry guard, the poison and allocation helpers, and the form in
-// which the step loop sees an accumulator.  Host code only; the kernels' side is ljmd_batch.h.
+// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF; ljmd_batch_series.cpp: the one core of the series
+// observables, driven by the descriptors of ljmd_stress_batch.cpp: pressure tensor, and ljmd_heatflux_batch.cpp: heat
+// flux): the handle, the entry guard, the poison and allocation helpers, and the form in which the step loop sees an
+// accumulator.  Host code only; the kernels' side is ljmd_batch.h.
 #ifndef LJMD_BATCH_HOST_H
 #define LJMD_BATCH_HOST_H
 
@@ -71,10 +72,10 @@ struct BatchAccumulator {
 };
 
 // a series of snapshots of exact integer sums -- the pressure tensor's (ljmd_stress_batch.cpp) and the heat flux's
-// (ljmd_heatflux_batch.cpp): off while max_snapshots == 0, and every is 0 then.  Those files are not linked into every
-// program that links ljmd_batch.cpp (tests/batch_trace), so the handle carries their entry into the step loop and their
-// release: ljmd_batch_stress_configure / ljmd_batch_heatflux_configure fill both, and default-constructed means nothing
-// is called
+// (ljmd_heatflux_batch.cpp), both through ljmd_batch_series.cpp: off while max_snapshots == 0, and every is 0 then.
+// Those two files are not linked into every program that links ljmd_batch.cpp (tests/batch_trace), so the handle carries
+// their entry into the step loop and their release: ljmd_batch_stress_configure / ljmd_batch_heatflux_configure fill
+// both, and default-constructed means nothing is called
 struct BatchSeries {
     int32_t max_snapshots = 0, every = 0;
     int64_t count = 0;                // snapshots in the series
@@ -182,6 +183,34 @@ int accumulate_now(ljmd_batch *h, const BatchAccumulator &a, const char *who);
 // frees what ljmd_batch_*_configure allocated and switches the accumulator off (ljmd_batch_destroy)
 void rdf_release(ljmd_batch *h);
 void tcf_release(ljmd_batch *h);
+
+// What ljmd_batch_series.cpp is driven by: one constant per series observable (ljmd_stress_batch.cpp,
+// ljmd_heatflux_batch.cpp).  The core references no launcher itself, so it links into every program that links
+// ljmd_batch*.cpp.  acc and release are what configure leaves in the handle's BatchSeries: the observable's entries into
+// the step loop, which pass this descriptor and its own series on to series_enqueue / series_room / series_release.
+struct BatchSeriesDesc {
+    BatchSeries ljmd_batch::*series;  // &ljmd_batch::stress: the observable's series of a handle
+    BatchAccumulator acc;             // name "pressure tensor", tag "stress", enqueue, ran, room; every = 0
+    void (*release)(ljmd_batch *h);
+    int words;                        // int64 words of one (snapshot, replica)
+    int max_snapshots;                // LJMD_BATCH_*_MAX_SNAPSHOTS
+    unsigned need;                    // kNeedStress
+    BatchSeriesLauncher launch;
+};
+int series_enqueue(ljmd_batch *h, const BatchSeriesDesc &d, const BatchGroup &g, hipStream_t s, int k, int32_t *count,
+                   const char *who);
+int series_room(ljmd_batch *h, const BatchSeriesDesc &d, int snapshots, const char *who);
+void series_release(ljmd_batch *h, const BatchSeriesDesc &d);
+// the bodies of ljmd_batch_<tag>_configure / _accumulate / _read_exact / _reset; `who` = the public name, h may be NULL
+int series_configure(ljmd_batch *h, const BatchSeriesDesc &d, int32_t max_snapshots, int32_t every, const char *who);
+int series_accumulate(ljmd_batch *h, const BatchSeriesDesc &d, const char *who);
+// the guards (a poisoned handle may still be read), the series so far in words -- waits for the device; a set range word
+// fails the call and names the lowest such replica
+int series_fetch(ljmd_batch *h, const BatchSeriesDesc &d, int64_t *words, int64_t *n_snapshots, const char *who);
+// the start of a read in doubles: the guard, then series_fetch into *w, sized here, when `want`
+int series_read_words(ljmd_batch *h, const BatchSeriesDesc &d, bool want, std::vector<int64_t> *w, int64_t *n_snapshots,
+                      const char *who);
+int series_reset(ljmd_batch *h, const BatchSeriesDesc &d, const char *who);
 
 }  // namespace ljmdb
 #endif

@@ -3,34 +3,36 @@
 // replica of a launch, one workgroup per replica.
 //
 // Per replica b, with its own n, L and rc, exactly the 12 integers of ljmd_stress_* (ljmd_stress.hip) for one system:
-// the per-pair arithmetic, Q(t) = RNE(t 2^64) and the range rule are the one copy of ljmd_stress_arith.h, compiled with
-// -ffp-contract=off (csrc/Makefile).  Integer sums depend on no order: not on B, on the replica's slot, on the grouping
-// into launches, on the streams, on the precision mode or on the order of the particles.
+// the per-pair arithmetic and its range rule are the one copy of ljmd_stress_arith.h, Q(t) = RNE(t 2^64) and the 192-bit
+// sums that of ljmd_sum192.h, compiled with -ffp-contract=off (csrc/Makefile).  Integer sums depend on no order: not on
+// B, on the replica's slot, on the grouping into launches, on the streams, on the precision mode or on the order of the
+// particles.
 //
 // Shape: batch_rdf_kernel's (ljmd_batch_rdf.hip).  The replica's positions are loaded once into LDS (SoA, 3 NMAX
 // doubles); a thread tid < T = batch_threads(n) owns particles tid, tid + T, ... (K of them); j is uniform across the
 // wave, so every position read is a broadcast.  Every unordered pair is evaluated once (j > i: a wave starts j behind its
 // first own particle) and the virial sums are doubled as integers, as the one-rank walk of stress_pairs_kernel does.  Six
 // 128-bit accumulators per thread run across its K passes (at most 4 * 4095 terms below 2^104); the same thread adds the
-// six velocity products of its own particles into a second set.  Then 192 bits: integer shuffles across the wave, the
-// replica's T / 64 waves through LDS after ONE barrier, and threads 0..11 store the 12 sums into the replica's row of the
-// snapshot, which no other workgroup writes; the range flag is ORed into the replica's own sticky word by a plain store.
+// six velocity products of its own particles into a second set.  Then 192 bits (ljmd_sum192.h): integer shuffles across
+// the wave, the replica's T / 64 waves through LDS after ONE barrier, and threads 0..11 store the 12 sums into the replica's
+// row of the snapshot, which no other workgroup writes; the range flag is ORed into the replica's own sticky word by a
+// plain store.
 // No global atomics, no floating-point atomics, no spin-waits, no dependency between workgroups.
 #include "ljmd_batch_stress.h"
 
 #include "ljmd_internal.h"
 #include "ljmd_stress_arith.h"
+#include "ljmd_sum192.h"
 
 namespace ljmdb {
 namespace {
 
-using ljmdk::add192;
 using ljmdk::add_six;
-using ljmdk::from128;
 using ljmdk::kStressTerms;
+using ljmdk::replica_lanes192;
+using ljmdk::replica_rows192;
 using ljmdk::stress_image;
 using ljmdk::stress_terms;
-using ljmdk::wave_sum192;
 
 static_assert(kBatchStressWords == 2 * kStressTerms * 3, "K[6][3], then S[6][3]");
 
@@ -80,42 +82,9 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_stress_kernel(BatchStr
                 add_six(kin, t, false, bad);
             }
         }
-
-        // lanes -> wave, in 192 bits: K[6], then S[6] with both orders of every pair
-        const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-        for (int c = 0; c < 2 * kStressTerms; ++c) {
-            uint64_t q[3];
-            from128(q, c < kStressTerms ? kin[c] : vir[c - kStressTerms]);
-            if (c >= kStressTerms) {
-                const uint64_t o[3] = {q[0], q[1], q[2]};
-                add192(q, o);
-            }
-            wave_sum192(q);
-            if (lane == 0) {
-                wsum[wave][c][0] = q[0];
-                wsum[wave][c][1] = q[1];
-                wsum[wave][c][2] = q[2];
-            }
-        }
+        replica_lanes192(kin, vir, wsum);       // K[6], then S[6] with both orders of every pair
     }
-    const int any_bad = __syncthreads_or(bad ? 1 : 0);          // the one barrier: wsum is complete behind it
-
-    // waves -> replica: thread c adds sum c over the replica's T / 64 waves into row (a.row, b)
-    if (tid < 2 * kStressTerms) {
-        const int c = tid;
-        uint64_t q[3] = {wsum[0][c][0], wsum[0][c][1], wsum[0][c][2]};
-        for (int w = 1; w < T / 64; ++w) {
-            const uint64_t o[3] = {wsum[w][c][0], wsum[w][c][1], wsum[w][c][2]};
-            add192(q, o);
-        }
-        uint64_t *const dst = a.words + (((size_t)a.row * a.B + b) * (2 * kStressTerms) + c) * 3;
-        dst[0] = q[0];
-        dst[1] = q[1];
-        dst[2] = q[2];
-    } else if (tid == 2 * kStressTerms && any_bad) {
-        a.range[b] = 1;
-    }
+    replica_rows192(bad, T, wsum, a.words, a.row, a.B, b, a.range);
 }
 
 }  // namespace

@@ -10,6 +10,7 @@
 
 #include "ljmd_internal.h"
 #include "ljmd_rdf.h"
+#include "ljmd_series.h"
 
 namespace ljmdq {
 
@@ -44,24 +45,8 @@ struct HeatfluxPairArgs {
     double rc2_skin;                // rc^2 (1 + 1e-10): a tile pair is skipped only when its bound exceeds this
 };
 
-struct HeatfluxKineticArgs {
-    const double *v;                // [3][P]
-    uint64_t *kpart;                // [blocks][3][3]
-    unsigned *kflag;                // [blocks]
-    int P, blocks;
-};
-
-struct HeatfluxFoldArgs {
-    const uint64_t *part;
-    const unsigned long long *pcount;
-    const unsigned *pflag;
-    const uint64_t *kpart;
-    const unsigned *kflag;
-    int workgroups, blocks;
-    uint64_t *row;                  // [kHeatfluxWords] of the series: this launch is its only writer
-    unsigned long long *count;      // [2] tile pairs of this accumulate
-    int32_t *range;                 // sticky
-};
+using HeatfluxKineticArgs = ljmdk::SeriesKineticArgs;    // kpart [blocks][3][3]
+using HeatfluxFoldArgs = ljmdk::SeriesFoldArgs;          // row [kHeatfluxWords]
 
 hipError_t launch_heatflux_pairs(const HeatfluxPairArgs &a, dim3 grid, hipStream_t s);
 hipError_t launch_heatflux_kinetic(const HeatfluxKineticArgs &a, hipStream_t s);

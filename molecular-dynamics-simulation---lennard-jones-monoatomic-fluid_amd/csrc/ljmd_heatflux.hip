@@ -13,22 +13,24 @@
 // sides: the walk evaluates an unordered pair once and doubles the sums.  Integer sums depend on no order: not on the
 // slot order, the tile walk or the slices of the grid.
 //
-// heatflux_pairs_kernel   stress_pairs_kernel's unordered walk (ljmd_rdf.h): one wave per row tile, lane = own particle
+// heatflux_pairs_kernel   stress_pairs_kernel's unordered walk (ljmd_rdf.h: rdf_walk_tiles): one wave per row tile, lane = own particle
 //                         with its position and velocity in registers, column positions and velocities wave-uniform,
 //                         kHeatfluxColumns at a time; 64 column tiles are tested at a time, lane = column tile, with
 //                         rdf_tile_gap2.  Six 128-bit accumulators per lane (fewer than 2^23 terms below 2^104 each);
 //                         after the walk integer shuffles across the wave, the workgroup's waves through LDS, and ONE
-//                         192-bit partial per component, the range flag and the two tile-pair counts go to the
-//                         workgroup's own rows by plain stores.
-// heatflux_kinetic_kernel the three terms k2 v_a of kHeatfluxKinBlock slots per workgroup, reduced the same way.
-// heatflux_fold_kernel    one workgroup, one wave per output row: adds the partials in 192 bits, writes row s of the
-//                         series (its only writer), the tile-pair counts of this accumulate, and ORs the flags into the
-//                         sticky word.
+//                         192-bit partial per component, the range flag (workgroup_sum192, ljmd_sum192.h) and the two
+//                         tile-pair counts go to the workgroup's own rows by plain stores.
+// heatflux_kinetic_kernel the three terms k2 v_a of kHeatfluxKinBlock slots per workgroup, reduced the same way
+//                         (series_kinetic, ljmd_sum192.h).
+// series_fold_kernel<3, 6> (ljmd_sum192.h)  one workgroup, one wave per output row: adds the partials in 192 bits, writes
+//                         row s of the series (its only writer), the tile-pair counts of this accumulate, and ORs the
+//                         flags into the sticky word.
 // No global atomics, no floating-point atomics, no spin-waits, no dependency between workgroups inside a launch.
 #include "ljmd_heatflux.h"
 
 #include "ljmd_heatflux_arith.h"
 #include "ljmd_internal.h"
+#include "ljmd_sum192.h"
 
 namespace ljmdq {
 namespace {
@@ -37,17 +39,17 @@ static_assert(kHeatfluxPairComponents == ljmdk::kHeatfluxPairTerms && kHeatfluxK
               "the arithmetic header adds six pair terms and three particle terms");
 static_assert(ljmdk::kTile % kHeatfluxColumns == 0, "a tile is a whole number of column batches");
 
-using ljmdk::add192;
+static_assert(kHeatfluxFoldWaves == kHeatfluxKinComponents + kHeatfluxPairComponents + 1, "one wave per row of the fold");
+
 using ljmdk::add_six;
-using ljmdk::from128;
 using ljmdk::heatflux_add_kinetic;
 using ljmdk::heatflux_terms;
 using ljmdk::kTile;
+using ljmdk::series_kinetic;
+using ljmdk::series_kinetic_ok;
 using ljmdk::stress_image;
-using ljmdk::wave_sum192;
-using ljmdr::rdf_tile_gap2;
-using ljmdr::rdf_walk_column;
-using ljmdr::rdf_walk_takes;
+using ljmdk::workgroup_sum192;
+using ljmdr::rdf_walk_tiles;
 
 // the 64 x 64 pairs of one (row tile, column tile); bx / bv: x of the column tile's first slot in pos / vel.  DIAGONAL:
 // column slot > row slot only
@@ -99,161 +101,38 @@ __global__ __launch_bounds__(kRdfWaves * kTile) void heatflux_pairs_kernel(Heatf
         const size_t row = (size_t)I * kTile + lane, P = (size_t)a.P;
         const double xi = a.pos[row], yi = a.pos[P + row], zi = a.pos[2 * P + row];
         const double vxi = a.vel[row], vyi = a.vel[P + row], vzi = a.vel[2 * P + row];
-        const double *bi = a.bbox + (size_t)I * kRdfBoxStride;
         const int u0 = blockIdx.y * a.chunk, u1 = min(u0 + a.chunk, a.U);
-        for (int ub = u0; ub < u1; ub += 64) {
-            // lane = step ub + lane: its column tile, whether the walk takes it from this row, whether the boxes keep it
-            const int u = ub + lane;
-            const int J = rdf_walk_column(I, u, a.T, true);
-            const bool valid = rdf_walk_takes(I, u, u1, a.T, true);
-            bool keep = valid;
-            if (valid && a.skip && J != I) keep = !(rdf_tile_gap2(bi, a.bbox + (size_t)J * kRdfBoxStride, a.L) > a.rc2_skin);
-            uint64_t m = __ballot(keep);
-            considered += (unsigned)__popcll(__ballot(valid));
-            visited += (unsigned)__popcll(m);
-            while (m) {
-                const int b = __builtin_ctzll(m);
-                m &= m - 1;
-                const int Jb = __builtin_amdgcn_readfirstlane(rdf_walk_column(I, ub + b, a.T, true));
-                const double *bx = a.pos + (size_t)Jb * kTile, *bv = a.vel + (size_t)Jb * kTile;
-                if (Jb != I)
-                    tile_pairs<false>(a, bx, bv, xi, yi, zi, vxi, vyi, vzi, lane, acc, bad);
-                else
-                    tile_pairs<true>(a, bx, bv, xi, yi, zi, vxi, vyi, vzi, lane, acc, bad);
-            }
-        }
-    }
-
-    // lanes -> wave: 192 bits from here on (64 lanes of 2^127, doubled, do not fit 128)
-#pragma unroll
-    for (int c = 0; c < kHeatfluxPairComponents; ++c) {
-        uint64_t q[3];
-        from128(q, acc[c]);
-        const uint64_t o[3] = {q[0], q[1], q[2]};               // both orders of every pair
-        add192(q, o);
-        wave_sum192(q);
-        if (lane == 0) {
-            wsum[wave][c][0] = q[0];
-            wsum[wave][c][1] = q[1];
-            wsum[wave][c][2] = q[2];
-        }
+        rdf_walk_tiles(I, u0, u1, a.T, true, a.bbox, a.skip, a.L, a.rc2_skin, visited, considered, [&](int Jb) {
+            const double *bx = a.pos + (size_t)Jb * kTile, *bv = a.vel + (size_t)Jb * kTile;
+            if (Jb != I)
+                tile_pairs<false>(a, bx, bv, xi, yi, zi, vxi, vyi, vzi, lane, acc, bad);
+            else
+                tile_pairs<true>(a, bx, bv, xi, yi, zi, vxi, vyi, vzi, lane, acc, bad);
+        });
     }
     if (lane == 0) {
         wcount[wave][0] = visited;
         wcount[wave][1] = considered;
     }
-    const int any_bad = __syncthreads_or(bad ? 1 : 0);          // the one barrier: wsum and wcount are complete behind it
 
-    // waves -> workgroup: thread c adds component c, thread 6 + k count k, into the workgroup's own rows
+    // the workgroup's own rows: threads 0..5 the sums (both orders of every pair), thread 6 the flag, threads 7 and 8
+    // the two counts -- wcount is complete behind the barrier of workgroup_sum192
     const size_t wg = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    if (threadIdx.x < kHeatfluxPairComponents) {
-        const int c = threadIdx.x;
-        uint64_t q[3] = {wsum[0][c][0], wsum[0][c][1], wsum[0][c][2]};
-        for (int w = 1; w < kRdfWaves; ++w) {
-            const uint64_t o[3] = {wsum[w][c][0], wsum[w][c][1], wsum[w][c][2]};
-            add192(q, o);
-        }
-        uint64_t *dst = a.part + (wg * kHeatfluxPairComponents + c) * 3;
-        dst[0] = q[0];
-        dst[1] = q[1];
-        dst[2] = q[2];
-    } else if (threadIdx.x < kHeatfluxPairComponents + 2) {
-        const int k = threadIdx.x - kHeatfluxPairComponents;
+    workgroup_sum192(acc, true, bad, lane, wave, wsum, a.part, a.pflag, wg);
+    if (threadIdx.x > kHeatfluxPairComponents && threadIdx.x <= kHeatfluxPairComponents + 2) {
+        const int k = threadIdx.x - kHeatfluxPairComponents - 1;
         unsigned long long n = 0;
         for (int w = 0; w < kRdfWaves; ++w) n += wcount[w][k];
         a.pcount[wg * 2 + k] = n;
-    } else if (threadIdx.x == kHeatfluxPairComponents + 2) {
-        a.pflag[wg] = any_bad ? 1u : 0u;
     }
 }
 
 __global__ __launch_bounds__(kHeatfluxKinThreads) void heatflux_kinetic_kernel(HeatfluxKineticArgs a)
 {
-    constexpr int kWaves = kHeatfluxKinThreads / 64;
-    __shared__ uint64_t wsum[kWaves][kHeatfluxKinComponents][3];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __int128 acc[kHeatfluxKinComponents] = {0, 0, 0};
-    bool bad = false;
-    const size_t P = (size_t)a.P;
-    const size_t s0 = (size_t)blockIdx.x * kHeatfluxKinBlock + threadIdx.x;
-#pragma unroll 1
-    for (int k = 0; k < kHeatfluxKinPerThread; ++k) {
-        const size_t s = s0 + (size_t)k * kHeatfluxKinThreads;
-        if (s >= P) break;
-        heatflux_add_kinetic(acc, a.v[s], a.v[P + s], a.v[2 * P + s], bad);      // a padding slot holds 0: Q(0) = 0
-    }
-#pragma unroll
-    for (int c = 0; c < kHeatfluxKinComponents; ++c) {
-        uint64_t q[3];
-        from128(q, acc[c]);
-        wave_sum192(q);
-        if (lane == 0) {
-            wsum[wave][c][0] = q[0];
-            wsum[wave][c][1] = q[1];
-            wsum[wave][c][2] = q[2];
-        }
-    }
-    const int any_bad = __syncthreads_or(bad ? 1 : 0);
-    if (threadIdx.x < kHeatfluxKinComponents) {
-        const int c = threadIdx.x;
-        uint64_t q[3] = {wsum[0][c][0], wsum[0][c][1], wsum[0][c][2]};
-        for (int w = 1; w < kWaves; ++w) {
-            const uint64_t o[3] = {wsum[w][c][0], wsum[w][c][1], wsum[w][c][2]};
-            add192(q, o);
-        }
-        uint64_t *dst = a.kpart + ((size_t)blockIdx.x * kHeatfluxKinComponents + c) * 3;
-        dst[0] = q[0];
-        dst[1] = q[1];
-        dst[2] = q[2];
-    } else if (threadIdx.x == kHeatfluxKinComponents) {
-        a.kflag[blockIdx.x] = any_bad ? 1u : 0u;
-    }
-}
-
-__global__ __launch_bounds__(kHeatfluxFoldWaves * 64) void heatflux_fold_kernel(HeatfluxFoldArgs a)
-{
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // output row of this wave
-    if (w < kHeatfluxRows) {
-        const bool kin = w < kHeatfluxKinComponents;
-        const int c = kin ? w : w - kHeatfluxKinComponents;
-        const int stride = kin ? kHeatfluxKinComponents : kHeatfluxPairComponents;
-        const uint64_t *src = kin ? a.kpart : a.part;
-        const unsigned *flg = kin ? a.kflag : a.pflag;
-        const int rows = kin ? a.blocks : a.workgroups;
-        uint64_t q[3] = {0, 0, 0};
-        unsigned bad = 0;
-        for (int r = lane; r < rows; r += 64) {
-            const uint64_t *p = src + ((size_t)r * stride + c) * 3;
-            const uint64_t o[3] = {p[0], p[1], p[2]};
-            add192(q, o);
-            bad |= flg[r];
-        }
-        wave_sum192(q);
-        const bool any_bad = __any(bad != 0);
-        if (lane == 0) {
-            uint64_t *dst = a.row + (size_t)w * 3;              // E[3][3], then P[3][3], then C[3][3]
-            dst[0] = q[0];
-            dst[1] = q[1];
-            dst[2] = q[2];
-            if (any_bad && c == 0) *a.range = 1;                // every writer stores the same value
-        }
-    } else {
-        unsigned long long n0 = 0, n1 = 0;
-        for (int r = lane; r < a.workgroups; r += 64) {
-            n0 += a.pcount[2 * (size_t)r];
-            n1 += a.pcount[2 * (size_t)r + 1];
-        }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            n0 += __shfl_down(n0, off, 64);
-            n1 += __shfl_down(n1, off, 64);
-        }
-        if (lane == 0) {
-            a.count[0] = n0;
-            a.count[1] = n1;
-        }
-    }
+    series_kinetic<kHeatfluxKinComponents, kHeatfluxKinThreads, kHeatfluxKinPerThread>(
+        a, [](__int128(&acc)[kHeatfluxKinComponents], double vx, double vy, double vz, bool &bad) {
+            heatflux_add_kinetic(acc, vx, vy, vz, bad);
+        });
 }
 
 }  // namespace
@@ -271,20 +150,14 @@ hipError_t launch_heatflux_pairs(const HeatfluxPairArgs &a, dim3 grid, hipStream
 
 hipError_t launch_heatflux_kinetic(const HeatfluxKineticArgs &a, hipStream_t s)
 {
-    if (!a.v || !a.kpart || !a.kflag || a.P < 1 || a.blocks < 1 || (long long)a.blocks * kHeatfluxKinBlock < a.P ||
-        (long long)(a.blocks - 1) * kHeatfluxKinBlock >= a.P)
-        return hipErrorInvalidValue;
+    if (!series_kinetic_ok(a, kHeatfluxKinBlock)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(heatflux_kinetic_kernel, dim3(a.blocks), dim3(kHeatfluxKinThreads), 0, s, a);
     return hipGetLastError();
 }
 
 hipError_t launch_heatflux_fold(const HeatfluxFoldArgs &a, hipStream_t s)
 {
-    if (!a.part || !a.pcount || !a.pflag || !a.kpart || !a.kflag || !a.row || !a.count || !a.range || a.workgroups < 1 ||
-        a.blocks < 1)
-        return hipErrorInvalidValue;
-    hipLaunchKernelGGL(heatflux_fold_kernel, dim3(1), dim3(kHeatfluxFoldWaves * 64), 0, s, a);
-    return hipGetLastError();
+    return ljmdk::launch_series_fold<kHeatfluxKinComponents, kHeatfluxPairComponents>(a, s);   // E[3][3], then P[3][3], C[3][3]
 }
 
 }  // namespace ljmdq

@@ -1,6 +1,6 @@
 // ljmd_heatflux_arith.h -- the device arithmetic of the heat flux (ljmd_heatflux.hip): what a pair within the cutoff
-// adds to the six exact integer sums P[3], C[3], what a particle adds to E[3], and the range rule.  The minimum image,
-// add_six, fixed_out_of_range and wave_sum192 are the pressure tensor's (ljmd_stress_arith.h), included here.
+// adds to the six exact integer sums P[3], C[3], what a particle adds to E[3], and the range rule.  The minimum image is
+// the pressure tensor's (ljmd_stress_arith.h), included here; add_six and the 192-bit sums are ljmd_sum192.h.
 // The definition is include/ljmd.h (ljmd_heatflux_*); compiled with -ffp-contract=off (csrc/Makefile).
 #ifndef LJMD_HEATFLUX_ARITH_H
 #define LJMD_HEATFLUX_ARITH_H
@@ -12,7 +12,7 @@ namespace ljmdk {
 
 constexpr int kHeatfluxPairTerms = 6;           // P x, y, z, then C x, y, z
 constexpr int kHeatfluxKinTerms = 3;            // E x, y, z
-static_assert(kHeatfluxPairTerms == kStressTerms, "add_six adds the six pair terms");
+static_assert(kHeatfluxPairTerms == 6, "add_six (ljmd_sum192.h) adds the six pair terms");
 
 // One pair within the cutoff, from one side, with w = v_i + v_j: its terms phi w_a (potential) and g d_a (collisional)
 // in t; returns whether fx, fy, fz, u6, wx, wy, wz or g is out of range.  add_six(acc, t, <that>, bad) then adds the

@@ -1,5 +1,6 @@
 // ljmd_rdf.h -- g(r) of the system resident on the single / sharded engine (include/ljmd.h: ljmd_rdf_*): argument
-// blocks of the two kernels of ljmd_rdf.hip and the tile-pair bound they skip by.  The host side is ljmd_resident.h.
+// blocks of the two kernels of ljmd_rdf.hip, the tile-pair bound they skip by, and the tile walk itself (rdf_walk_tiles),
+// which the pair kernels of the pressure tensor and the heat flux share.  The host side is ljmd_resident.h.
 //
 // The layout is the engine's (ljmd_internal.h): exchange buffer pos[G][3][P], 64-slot tiles, TB tiles per rank block,
 // T = G TB tiles, NaN on the padding slots.
@@ -75,7 +76,7 @@ __host__ __device__ inline double rdf_tile_gap2(const double *bi, const double *
 }
 
 // The two decisions of the walk, the same for the box test of a lane and for the evaluation after the ballot, in
-// rdf_pairs_kernel and stress_pairs_kernel (tests/rdf_host enumerates them on the host).
+// rdf_walk_tiles below (tests/rdf_host enumerates them on the host).
 // column tile of row tile I at step u (I < T; u <= T / 2 unordered, u < T ordered: one wrap at most)
 __host__ __device__ inline int rdf_walk_column(int I, int u, int T, bool unordered)
 {
@@ -90,6 +91,34 @@ __host__ __device__ inline bool rdf_walk_takes(int I, int u, int u1, int T, bool
 {
     const int half = (unordered && (T & 1) == 0) ? T / 2 : -1;
     return u < u1 && !(u == half && I >= half);
+}
+
+// The one copy of the tile walk of rdf_pairs_kernel, stress_pairs_kernel and heatflux_pairs_kernel: the steps [u0, u1) of
+// row tile I, 64 to a ballot.  Lane = step ub + lane: its column tile, whether the walk takes it from this row
+// (`considered` counts these), whether the boxes keep it -- with `skip` a tile pair other than the own is left out when
+// rdf_tile_gap2 exceeds bound2 (`visited` counts what is kept).  body(Jb) then runs for every kept step in ascending
+// order, the column tile Jb wave-uniform.  The whole wave calls it.
+template <class Body>
+__device__ __forceinline__ void rdf_walk_tiles(int I, int u0, int u1, int T, bool unordered, const double *bbox, int skip, double L,
+                                               double bound2, unsigned &visited, unsigned &considered, Body &&body)
+{
+    const int lane = threadIdx.x & 63;
+    const double *bi = bbox + (size_t)I * kRdfBoxStride;
+    for (int ub = u0; ub < u1; ub += 64) {
+        const int u = ub + lane;
+        const int J = rdf_walk_column(I, u, T, unordered);
+        const bool valid = rdf_walk_takes(I, u, u1, T, unordered);
+        bool keep = valid;
+        if (valid && skip && J != I) keep = !(rdf_tile_gap2(bi, bbox + (size_t)J * kRdfBoxStride, L) > bound2);
+        uint64_t m = __ballot(keep);
+        considered += (unsigned)__popcll(__ballot(valid));
+        visited += (unsigned)__popcll(m);
+        while (m) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1;
+            body(__builtin_amdgcn_readfirstlane(rdf_walk_column(I, ub + b, T, unordered)));
+        }
+    }
 }
 
 hipError_t launch_rdf_boxes(const RdfBoxArgs &a, hipStream_t s);

@@ -16,7 +16,8 @@
 // rdf_pairs_kernel: one wave per row tile (lane = own particle, in registers), kRdfWaves waves per workgroup sharing one
 // LDS histogram; the column particles are wave-uniform, fetched with scalar loads as pair_tiles_kernel does.  The walk
 // and its weights are RdfPairArgs' (ljmd_rdf.h).  A wave tests 64 column tiles at a time, lane = column tile, with
-// rdf_tile_gap2 and visits the survivors.  Nothing here waits for another wave or workgroup.
+// rdf_tile_gap2 and visits the survivors: rdf_walk_tiles (ljmd_rdf.h), the one copy of that loop.  Nothing here waits
+// for another wave or workgroup.
 #include "ljmd_rdf.h"
 #include "ljmd_internal.h"
 
@@ -111,35 +112,20 @@ __global__ __launch_bounds__(kRdfWaves * kTile) void rdf_pairs_kernel(RdfPairArg
         const int row = Il * kTile + lane;
         const double *own = a.pos + (size_t)a.rank * 3 * a.P;
         const double xi = own[row], yi = own[a.P + row], zi = own[2 * (size_t)a.P + row];
-        const double *bi = a.bbox + (size_t)I * kRdfBoxStride;
         const bool unordered = a.G == 1;
         const unsigned weight = unordered ? 2u : 1u;
         const int u0 = blockIdx.y * a.chunk, u1 = min(u0 + a.chunk, a.U);
         unsigned visited = 0, considered = 0;
-        for (int ub = u0; ub < u1; ub += 64) {
-            // lane = step ub + lane: its column tile, whether the walk takes it from this row, whether the boxes keep it
-            const int u = ub + lane;
-            const int J = rdf_walk_column(I, u, a.T, unordered);
-            const bool valid = rdf_walk_takes(I, u, u1, a.T, unordered);
-            bool keep = valid;
-            if (valid && a.skip && J != I) keep = !(rdf_tile_gap2(bi, a.bbox + (size_t)J * kRdfBoxStride, a.L) > a.rmax2_skin);
-            uint64_t m = __ballot(keep);
-            considered += (unsigned)__popcll(__ballot(valid));
-            visited += (unsigned)__popcll(m);
-            while (m) {
-                const int b = __builtin_ctzll(m);
-                m &= m - 1;
-                const int Jb = __builtin_amdgcn_readfirstlane(rdf_walk_column(I, ub + b, a.T, unordered));
-                const int gj = unordered ? 0 : Jb / a.TB;
-                const double *bx = a.pos + (size_t)gj * 3 * a.P + (size_t)(Jb - gj * a.TB) * kTile;
-                if (Jb != I)
-                    tile_pairs<0>(a, bx, xi, yi, zi, lane, weight, lhist);
-                else if (unordered)
-                    tile_pairs<1>(a, bx, xi, yi, zi, lane, weight, lhist);
-                else
-                    tile_pairs<2>(a, bx, xi, yi, zi, lane, weight, lhist);
-            }
-        }
+        rdf_walk_tiles(I, u0, u1, a.T, unordered, a.bbox, a.skip, a.L, a.rmax2_skin, visited, considered, [&](int Jb) {
+            const int gj = unordered ? 0 : Jb / a.TB;
+            const double *bx = a.pos + (size_t)gj * 3 * a.P + (size_t)(Jb - gj * a.TB) * kTile;
+            if (Jb != I)
+                tile_pairs<0>(a, bx, xi, yi, zi, lane, weight, lhist);
+            else if (unordered)
+                tile_pairs<1>(a, bx, xi, yi, zi, lane, weight, lhist);
+            else
+                tile_pairs<2>(a, bx, xi, yi, zi, lane, weight, lhist);
+        });
         if (lane == 0) {
             atomicAdd(&wcount[0], (unsigned long long)visited);
             atomicAdd(&wcount[1], (unsigned long long)considered);

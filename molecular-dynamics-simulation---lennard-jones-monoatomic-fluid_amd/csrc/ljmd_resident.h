@@ -1,8 +1,8 @@
 // ljmd_resident.h -- host side of the five observables of the system resident on the single / sharded engine: g(r)
-// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp), the pressure tensor (ljmd_stress.cpp), the heat flux
-// (ljmd_heatflux.cpp) and the van Hove self-correlation (ljmd_vanhove.cpp).  What the cores share -- the view through
-// which they see an engine, their named device buffers, the timer around one accumulate -- and each core's state and
-// functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host, tests/tcf_host,
+// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp), the pressure tensor (ljmd_stress.cpp) and the heat flux
+// (ljmd_heatflux.cpp), which are two descriptors over the one series core (ljmd_series.cpp), and the van Hove
+// self-correlation (ljmd_vanhove.cpp).  What the cores share -- the view through which they see an engine, their named
+// device buffers, the timer around one accumulate -- and each core's state and functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host, tests/tcf_host,
 // tests/stress_host, tests/heatflux_host, tests/vanhove_host); every C entry point that takes a handle is in
 // ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_tcf.h, ljmd_stress.h, ljmd_heatflux.h and
 // ljmd_vanhove.h.
@@ -190,22 +190,59 @@ void tcf_release(TcfState *st, hipStream_t stream);
 
 }  // namespace ljmdt
 
-namespace ljmds {
+// The series observables -- the pressure tensor and the heat flux: one state, one core (ljmd_series.cpp), and a constant
+// descriptor of each observable (ljmd_stress.cpp, ljmd_heatflux.cpp) that the core is driven by.
+namespace ljmdh {
 
-using ljmdh::ResidentView;
-
-struct StressState {
+struct SeriesState {
     int max_snapshots = 0;          // 0 = not configured
     int workgroups = 0, blocks = 0; // rows of part / kpart
-    uint64_t *d_series = nullptr;   // [max_snapshots][kStressWords]
+    uint64_t *d_series = nullptr;   // [max_snapshots][words of a snapshot]
     uint64_t *d_part = nullptr, *d_kpart = nullptr;
     unsigned long long *d_pcount = nullptr, *d_count = nullptr;
     unsigned *d_pflag = nullptr, *d_kflag = nullptr;
     int32_t *d_range = nullptr;
     double *d_bbox = nullptr;       // [T][kRdfBoxStride]
-    ljmdh::KernelTimer timer;
+    KernelTimer timer;
     int64_t snapshots = 0;
 };
+
+struct SeriesDesc {
+    const char *phrase;             // "pressure tensor": "the pressure tensor is not configured"
+    const char *tag;                // "stress": ljmd_stress_configure, ljmd_stress_reset
+    const char *particle_partials, *particle_flags;     // what a failed allocation calls kpart and kflag
+    int words;                      // int64 words of one snapshot
+    int pair_components, particle_components;
+    int max_snapshots, max_n;
+    int kin_block;                  // slots per workgroup of the kinetic kernel
+    bool one_rank;                  // a pair term needs both velocities: one-rank engines only
+    // the observable's three launches of one accumulate, behind launch_rdf_boxes: fills its pair arguments from the view,
+    // the state and the walk, and passes ka and fa on as they are
+    hipError_t (*launch)(const SeriesState &st, const ResidentView &v, const ljmdr::RdfWalk &w,
+                         const ljmdk::SeriesKineticArgs &ka, const ljmdk::SeriesFoldArgs &fa);
+};
+
+int series_not_configured(const SeriesDesc &d, std::string *err, const char *who);
+int series_configure(const SeriesDesc &d, SeriesState *st, std::string *err, const char *who, const ResidentView &v,
+                     int32_t max_snapshots);
+int series_accumulate(const SeriesDesc &d, SeriesState *st, std::string *err, const char *who, const ResidentView &v);
+// words [snapshots][d.words], either pointer may be NULL; LJMD_ERR_RANGE while the sticky word is set
+int series_fetch(const SeriesDesc &d, SeriesState *st, std::string *err, const char *who, const ResidentView &v, int64_t *words,
+                 int64_t *n_snapshots);
+// the start of a read in doubles: series_fetch into *w, sized here, when `want`
+int series_read_words(const SeriesDesc &d, SeriesState *st, std::string *err, const char *who, const ResidentView &v, bool want,
+                      std::vector<int64_t> *w, int64_t *n_snapshots);
+int series_reset(const SeriesDesc &d, SeriesState *st, std::string *err, const char *who, const ResidentView &v);
+int series_profile_read(const SeriesDesc &d, SeriesState *st, std::string *err, const char *who, const ResidentView &v,
+                        int64_t *visited, int64_t *total, double *kernel_ms);
+void series_release(const SeriesDesc &d, SeriesState *st, hipStream_t stream);
+
+}  // namespace ljmdh
+
+namespace ljmds {
+
+using ljmdh::ResidentView;
+using StressState = ljmdh::SeriesState;
 
 int not_configured(std::string *err, const char *who);
 int stress_configure(StressState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_snapshots);
@@ -223,19 +260,7 @@ void stress_release(StressState *st, hipStream_t stream);
 namespace ljmdq {
 
 using ljmdh::ResidentView;
-
-struct HeatfluxState {
-    int max_snapshots = 0;          // 0 = not configured
-    int workgroups = 0, blocks = 0; // rows of part / kpart
-    uint64_t *d_series = nullptr;   // [max_snapshots][kHeatfluxWords]
-    uint64_t *d_part = nullptr, *d_kpart = nullptr;
-    unsigned long long *d_pcount = nullptr, *d_count = nullptr;
-    unsigned *d_pflag = nullptr, *d_kflag = nullptr;
-    int32_t *d_range = nullptr;
-    double *d_bbox = nullptr;       // [T][kRdfBoxStride]
-    ljmdh::KernelTimer timer;
-    int64_t snapshots = 0;
-};
+using HeatfluxState = ljmdh::SeriesState;
 
 int not_configured(std::string *err, const char *who);
 // refuses a multi-device handle and a rank engine of G > 1 itself
@@ -252,6 +277,7 @@ int heatflux_profile_read(HeatfluxState *st, std::string *err, const char *who, 
 void heatflux_release(HeatfluxState *st, hipStream_t stream);
 
 }  // namespace ljmdq
+
 namespace ljmdv {
 
 using ljmdh::ResidentView;

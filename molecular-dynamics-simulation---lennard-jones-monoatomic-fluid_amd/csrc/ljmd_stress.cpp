@@ -1,13 +1,10 @@
-// ljmd_stress.cpp -- host core of the engine's resident pressure tensor (kernels: ljmd_stress.hip): guards, sizes,
-// argument blocks, launches, reads and resets, and ljmd_stress_from_exact, which needs no engine.  The core sees an
-// engine only through ResidentView and links without anything of struct ljmd (tests/stress_host); the C entry points
-// that take a handle are in ljmd_resident.cpp.
+// ljmd_stress.cpp -- the engine's resident pressure tensor on the host (kernels: ljmd_stress.hip): its descriptor for the
+// series core (ljmd_series.cpp), the arguments of its pair kernel, the conversion to doubles, and ljmd_stress_from_exact,
+// which needs no engine.  Like the core it sees an engine only through ResidentView and links without anything of struct
+// ljmd (tests/stress_host); the C entry points that take a handle are in ljmd_resident.cpp.
 #include "ljmd_resident.h"
 
-#include <algorithm>
 #include <cmath>
-#include <new>
-#include <vector>
 
 using namespace ljmdh;
 
@@ -15,146 +12,55 @@ namespace ljmds {
 
 namespace {
 
-enum { kSeries, kPart, kKpart, kPcount, kCount, kPflag, kKflag, kRange, kBbox, kBuffers };
-
-// the buffers of a state in the order they are allocated; the sizes matter to configure only
-std::array<DeviceBuffer, kBuffers> buffers(StressState *st, int max_snapshots = 0, int workgroups = 0, int blocks = 0, int T = 0)
+hipError_t launch(const StressState &st, const ResidentView &v, const ljmdr::RdfWalk &w, const StressKineticArgs &ka,
+                  const StressFoldArgs &fa)
 {
-    const size_t row = (size_t)kStressComponents * 3 * sizeof(uint64_t);
-    return {{{(void **)&st->d_series, (size_t)max_snapshots * kStressWords * sizeof(uint64_t), "the series"},
-             {(void **)&st->d_part, (size_t)workgroups * row, "the pair partials"},
-             {(void **)&st->d_kpart, (size_t)blocks * row, "the kinetic partials"},
-             {(void **)&st->d_pcount, (size_t)workgroups * 2 * sizeof(unsigned long long), "the tile-pair partials"},
-             {(void **)&st->d_count, 2 * sizeof(unsigned long long), "the tile-pair counters"},
-             {(void **)&st->d_pflag, (size_t)workgroups * sizeof(unsigned), "the pair flags"},
-             {(void **)&st->d_kflag, (size_t)blocks * sizeof(unsigned), "the kinetic flags"},
-             {(void **)&st->d_range, sizeof(int32_t), "the range word"},
-             {(void **)&st->d_bbox, (size_t)T * kRdfBoxStride * sizeof(double), "the tile boxes"}}};
-}
-
-}  // namespace
-
-int not_configured(std::string *err, const char *who)
-{
-    return fail(err, LJMD_ERR_STATE, "%s: the pressure tensor is not configured (call ljmd_stress_configure first)", who);
-}
-
-void stress_release(StressState *st, hipStream_t stream)
-{
-    free_buffers(buffers(st), stream);
-    st->timer.destroy();
-    *st = {};
-}
-
-int stress_configure(StressState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_snapshots)
-{
-    static_assert(kStressMaxSnapshots == LJMD_STRESS_MAX_SNAPSHOTS, "LJMD_STRESS_MAX_SNAPSHOTS out of sync with the core");
-    static_assert(kStressMaxN == ljmdk::kFixedMaxN, "the lane accumulators rest on kFixedMaxN");
-    if (max_snapshots < 0 || max_snapshots > kStressMaxSnapshots)
-        return fail(err, LJMD_ERR_INVALID_ARG, "%s: max_snapshots = %d outside 1..%d (0 switches the pressure tensor off)", who,
-                    max_snapshots, kStressMaxSnapshots);
-    if (max_snapshots > 0 && (v.n < 1 || v.n > kStressMaxN))
-        return fail(err, LJMD_ERR_INVALID_ARG, "%s: n = %d outside 1..%d", who, v.n, kStressMaxN);
-    stress_release(st, v.stream);
-    if (max_snapshots == 0) return LJMD_OK;
-    const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(v.TB, v.T, v.G, v.walk_chunk);
-    const int workgroups = w.row_blocks * w.slices;
-    const int blocks = (v.P + kStressKinBlock - 1) / kStressKinBlock;
-    const auto bufs = buffers(st, max_snapshots, workgroups, blocks, v.T);
-    auto body = [&]() -> int {
-        LJMD_TRY(alloc_buffers(err, who, bufs));
-        LJMD_HIP(err, st->timer.create());
-        // the partials and flags are written before they are read; the rest starts at zero
-        LJMD_HIP(err, hipMemsetAsync(st->d_series, 0, bufs[kSeries].bytes, v.stream));
-        LJMD_HIP(err, hipMemsetAsync(st->d_count, 0, bufs[kCount].bytes, v.stream));
-        LJMD_HIP(err, hipMemsetAsync(st->d_range, 0, bufs[kRange].bytes, v.stream));
-        return LJMD_OK;
-    };
-    const int rc_ = body();
-    if (rc_ != LJMD_OK) {
-        stress_release(st, v.stream);
-        return rc_;
-    }
-    st->max_snapshots = max_snapshots;
-    st->workgroups = workgroups;
-    st->blocks = blocks;
-    return LJMD_OK;
-}
-
-int stress_accumulate(StressState *st, std::string *err, const char *who, const ResidentView &v)
-{
-    if (st->max_snapshots == 0) return not_configured(err, who);
-    if (st->snapshots >= st->max_snapshots)
-        return fail(err, LJMD_ERR_STATE, "%s: the series is full (%d snapshots; read it, then ljmd_stress_reset)", who,
-                    st->max_snapshots);
-    const ljmdr::RdfWalk w = ljmdr::rdf_plan_walk(v.TB, v.T, v.G, v.walk_chunk);
-    const int blocks = (v.P + kStressKinBlock - 1) / kStressKinBlock;
-    if (w.row_blocks * w.slices != st->workgroups || blocks != st->blocks || !v.pos || !v.v)
-        return fail(err, LJMD_ERR_STATE, "%s: the engine is not the one the pressure tensor was configured for", who);
-    ljmdr::RdfBoxArgs ba{};
-    ba.pos = v.pos;
-    ba.bbox = st->d_bbox;
-    ba.P = v.P; ba.TB = v.TB; ba.T = v.T;
     StressPairArgs pa{};
     pa.pos = v.pos;
-    pa.bbox = st->d_bbox;
-    pa.part = st->d_part; pa.pcount = st->d_pcount; pa.pflag = st->d_pflag;
+    pa.bbox = st.d_bbox;
+    pa.part = st.d_part; pa.pcount = st.d_pcount; pa.pflag = st.d_pflag;
     pa.P = v.P; pa.G = v.G; pa.rank = v.rank; pa.TB = v.TB; pa.T = v.T;
     pa.U = w.U; pa.chunk = w.chunk;
     pa.skip = v.compact ? 1 : 0;
     pa.L = v.L; pa.invL = v.invL; pa.rc2 = v.rc2;
     pa.rc2_skin = v.rc2 * (1.0 + 1e-10);
-    StressKineticArgs ka{};
-    ka.v = v.v;
-    ka.kpart = st->d_kpart; ka.kflag = st->d_kflag;
-    ka.P = v.P; ka.blocks = blocks;
-    StressFoldArgs fa{};
-    fa.part = st->d_part; fa.pcount = st->d_pcount; fa.pflag = st->d_pflag;
-    fa.kpart = st->d_kpart; fa.kflag = st->d_kflag;
-    fa.workgroups = st->workgroups; fa.blocks = blocks;
-    fa.row = st->d_series + (size_t)st->snapshots * kStressWords;
-    fa.count = st->d_count;
-    fa.range = st->d_range;
-    LJMD_HIP(err, st->timer.start(v.stream));
-    hipError_t e = ljmdr::launch_rdf_boxes(ba, v.stream);
-    if (e == hipSuccess) e = launch_stress_pairs(pa, dim3(w.row_blocks, w.slices), v.stream);
+    hipError_t e = launch_stress_pairs(pa, dim3(w.row_blocks, w.slices), v.stream);
     if (e == hipSuccess) e = launch_stress_kinetic(ka, v.stream);
     if (e == hipSuccess) e = launch_stress_fold(fa, v.stream);
-    if (e != hipSuccess) return fail(err, LJMD_ERR_HIP, "%s: pressure tensor launch failed: %s", who, hipGetErrorString(e));
-    LJMD_HIP(err, st->timer.stop(v.stream));
-    ++st->snapshots;
-    return LJMD_OK;
+    return e;
+}
+
+static_assert(kStressMaxSnapshots == LJMD_STRESS_MAX_SNAPSHOTS, "LJMD_STRESS_MAX_SNAPSHOTS out of sync with the core");
+static_assert(kStressMaxN == ljmdk::kFixedMaxN, "the lane accumulators rest on kFixedMaxN");
+
+const SeriesDesc kDesc = {"pressure tensor", "stress", "the kinetic partials", "the kinetic flags", kStressWords,
+                          kStressComponents, kStressComponents, kStressMaxSnapshots, kStressMaxN, kStressKinBlock,
+                          false, launch};
+
+}  // namespace
+
+int not_configured(std::string *err, const char *who) { return series_not_configured(kDesc, err, who); }
+void stress_release(StressState *st, hipStream_t stream) { series_release(kDesc, st, stream); }
+
+int stress_configure(StressState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_snapshots)
+{
+    return series_configure(kDesc, st, err, who, v, max_snapshots);
+}
+
+int stress_accumulate(StressState *st, std::string *err, const char *who, const ResidentView &v)
+{
+    return series_accumulate(kDesc, st, err, who, v);
 }
 
 int stress_fetch(StressState *st, std::string *err, const char *who, const ResidentView &v, int64_t *words, int64_t *n_snapshots)
 {
-    if (st->max_snapshots == 0) return not_configured(err, who);
-    int32_t range = 0;
-    LJMD_HIP(err, hipMemcpyAsync(&range, st->d_range, sizeof range, hipMemcpyDeviceToHost, v.stream));
-    if (words && st->snapshots > 0)
-        LJMD_HIP(err, hipMemcpyAsync(words, st->d_series, (size_t)st->snapshots * kStressWords * sizeof(uint64_t),
-                                       hipMemcpyDeviceToHost, v.stream));
-    LJMD_HIP(err, hipStreamSynchronize(v.stream));
-    // the handle is not poisoned: the trajectory itself is sound
-    if (range != 0)
-        return fail(err, LJMD_ERR_RANGE, "%s: a pair's or a particle's pressure tensor terms were not finite or |term| >= 2^40 "
-                                         "and entered as 0; the flag stays until ljmd_stress_reset", who);
-    if (n_snapshots) *n_snapshots = st->snapshots;
-    return LJMD_OK;
+    return series_fetch(kDesc, st, err, who, v, words, n_snapshots);
 }
 
 int stress_read(StressState *st, std::string *err, const char *who, const ResidentView &v, double *p, int64_t *n_snapshots)
 {
-    if (st->max_snapshots == 0) return not_configured(err, who);
     std::vector<int64_t> w;
-    if (p) {
-        try {
-            w.resize((size_t)st->snapshots * kStressWords);
-        } catch (const std::bad_alloc &) {
-            return fail(err, LJMD_ERR_ALLOC, "%s: out of host memory", who);
-        }
-    }
-    LJMD_TRY(stress_fetch(st, err, who, v, p ? w.data() : nullptr, n_snapshots));
+    LJMD_TRY(series_read_words(kDesc, st, err, who, v, p != nullptr, &w, n_snapshots));
     for (int64_t s = 0; p && s < st->snapshots; ++s)
         stress_doubles(w.data() + (size_t)s * kStressWords, v.L, p + (size_t)s * kStressComponents);
     return LJMD_OK;
@@ -162,25 +68,13 @@ int stress_read(StressState *st, std::string *err, const char *who, const Reside
 
 int stress_reset(StressState *st, std::string *err, const char *who, const ResidentView &v)
 {
-    if (st->max_snapshots == 0) return not_configured(err, who);
-    LJMD_HIP(err, hipMemsetAsync(st->d_series, 0, (size_t)st->max_snapshots * kStressWords * sizeof(uint64_t), v.stream));
-    LJMD_HIP(err, hipMemsetAsync(st->d_range, 0, sizeof(int32_t), v.stream));
-    st->snapshots = 0;
-    return LJMD_OK;
+    return series_reset(kDesc, st, err, who, v);
 }
 
 int stress_profile_read(StressState *st, std::string *err, const char *who, const ResidentView &v, int64_t *visited,
                         int64_t *total, double *kernel_ms)
 {
-    if (st->max_snapshots == 0) return not_configured(err, who);
-    unsigned long long c[2] = {0, 0};
-    float ms = 0.0f;
-    if (st->timer.timed) LJMD_HIP(err, hipMemcpyAsync(c, st->d_count, sizeof c, hipMemcpyDeviceToHost, v.stream));
-    LJMD_HIP(err, st->timer.elapsed_ms(v.stream, &ms));
-    if (visited) *visited = (int64_t)c[0];
-    if (total) *total = (int64_t)c[1];
-    if (kernel_ms) *kernel_ms = (double)ms;
-    return LJMD_OK;
+    return series_profile_read(kDesc, st, err, who, v, visited, total, kernel_ms);
 }
 
 }  // namespace ljmds

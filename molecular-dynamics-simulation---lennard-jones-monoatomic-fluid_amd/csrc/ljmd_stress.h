@@ -10,6 +10,7 @@
 
 #include "ljmd_internal.h"
 #include "ljmd_rdf.h"
+#include "ljmd_series.h"
 
 namespace ljmds {
 
@@ -39,24 +40,8 @@ struct StressPairArgs {
     double rc2_skin;                // rc^2 (1 + 1e-10): a tile pair is skipped only when its bound exceeds this
 };
 
-struct StressKineticArgs {
-    const double *v;                // [3][P] of the own block
-    uint64_t *kpart;                // [blocks][6][3]
-    unsigned *kflag;                // [blocks]
-    int P, blocks;
-};
-
-struct StressFoldArgs {
-    const uint64_t *part;
-    const unsigned long long *pcount;
-    const unsigned *pflag;
-    const uint64_t *kpart;
-    const unsigned *kflag;
-    int workgroups, blocks;
-    uint64_t *row;                  // [kStressWords] of the series: this launch is its only writer
-    unsigned long long *count;      // [2] tile pairs of this accumulate
-    int32_t *range;                 // sticky
-};
+using StressKineticArgs = ljmdk::SeriesKineticArgs;      // kpart [blocks][6][3]
+using StressFoldArgs = ljmdk::SeriesFoldArgs;            // row [kStressWords]
 
 hipError_t launch_stress_pairs(const StressPairArgs &a, dim3 grid, hipStream_t s);
 hipError_t launch_stress_kinetic(const StressKineticArgs &a, hipStream_t s);

@@ -1,7 +1,7 @@
 """-m gpu: the tile walk of rdf_pairs_kernel, stress_pairs_kernel and heatflux_pairs_kernel beyond one step per slice.
 
 rdf_plan_walk gives every system below n ~ 16 000 slices of ONE column-tile step, so the 64-lane ballot block of the three
-kernels (each carries its own copy of the loop) runs with one valid lane in every other test that pins them to a
+kernels (one copy, rdf_walk_tiles of csrc/ljmd_rdf.h) runs with one valid lane in every other test that pins them to a
 reference.  LJMD_WALK_CHUNK sets the steps per slice: here the blocks have many live lanes, a slice has a second block, a
 partial last block, the tie step and the wrap of the unordered walk and the own tile of the ordered walk fall into a later
 block -- at sizes whose exact reference is affordable.  Every comparison is integer equality: the g(r) counts with
@@ -131,7 +131,7 @@ def _measure(eng, what, rcut):
     assert words.shape == (1, 12)
     if what == "stress":
         return tuple(words[0]), eng.stress_profile()
-    # the heat flux beside the pressure tensor of the same state at the same rc: the two copies of the walk skip by the
+    # the heat flux beside the pressure tensor of the same state at the same rc: the two kernels' walks skip by the
     # same bound (rc2 (1 + 1e-10), rdf_tile_gap2) on the same boxes, so they visit the same tile pairs
     assert what == "heatflux"
     eng.heatflux_configure(1)
