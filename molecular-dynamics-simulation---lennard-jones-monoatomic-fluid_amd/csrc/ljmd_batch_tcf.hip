@@ -27,9 +27,7 @@ namespace ljmdb {
 namespace {
 
 using ljmdk::add192;
-using ljmdk::entry_add;
-using ljmdk::tcf_add;
-using ljmdk::wave_sum_i64;
+using ljmdk::tcf_origin;
 
 template <int NMAX, int K>
 __global__ __launch_bounds__(kBatchMaxThreads) void batch_tcf_kernel(BatchTcfArgs a)
@@ -60,43 +58,11 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_tcf_kernel(BatchTcfArg
         for (int e = 0; e < n_live; ++e) {
             const double *const o = a.ring + (size_t)slot * 6 * plane + base;
             slot = slot + 1 == a.slots ? 0 : slot + 1;
-            const bool with0 = lag0 && e == n_live - 1;
-            long long m_hi = 0, m_lo = 0, c_hi = 0, c_lo = 0;       // MSD and VACF limbs of this origin
-            long long z_hi = 0, z_lo = 0, w_hi = 0, w_lo = 0;       // ... and of its lag 0
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
+            const auto org = [=](int k, int c) {
                 const int i = tid + k * T;
-                const bool live = i < n;
-                double org[6];
-#pragma unroll
-                for (int c = 0; c < 6; ++c) org[c] = live ? o[(size_t)c * plane + i] : 0.0;
-                const double dx = cur[k][0] - org[0], dy = cur[k][1] - org[1], dz = cur[k][2] - org[2];
-                tcf_add(m_hi, m_lo, (dx * dx + dy * dy) + dz * dz, bad);
-                tcf_add(c_hi, c_lo, (cur[k][3] * org[3] + cur[k][4] * org[4]) + cur[k][5] * org[5], bad);
-                if (with0) {                                         // uniform across the workgroup
-                    const double ex = org[0] - org[0], ey = org[1] - org[1], ez = org[2] - org[2];
-                    tcf_add(z_hi, z_lo, (ex * ex + ey * ey) + ez * ez, bad);
-                    tcf_add(w_hi, w_lo, (org[3] * org[3] + org[4] * org[4]) + org[5] * org[5], bad);
-                }
-            }
-            m_hi = wave_sum_i64(m_hi);
-            m_lo = wave_sum_i64(m_lo);
-            c_hi = wave_sum_i64(c_hi);
-            c_lo = wave_sum_i64(c_lo);
-            if (with0) {
-                z_hi = wave_sum_i64(z_hi);
-                z_lo = wave_sum_i64(z_lo);
-                w_hi = wave_sum_i64(w_hi);
-                w_lo = wave_sum_i64(w_lo);
-            }
-            if (lane == 0) {
-                entry_add(acc + 4 * e, m_hi, m_lo);
-                entry_add(acc + 4 * e + 2, c_hi, c_lo);
-                if (with0) {
-                    entry_add(acc + 4 * n_live, z_hi, z_lo);
-                    entry_add(acc + 4 * n_live + 2, w_hi, w_lo);
-                }
-            }
+                return i < n ? o[(size_t)c * plane + i] : 0.0;
+            };
+            tcf_origin(cur, org, lag0 && e == n_live - 1, lane, acc + 4 * e, acc + 4 * n_live, bad);
         }
         // the snapshot becomes an origin: the slot's lag would be slots * stride > max_lag, so it was not read above,
         // and a thread touches only its own particles' elements

@@ -1,11 +1,12 @@
 // ljmd_resident.h -- host side of the five observables of the system resident on the single / sharded engine: g(r)
-// (ljmd_rdf.cpp), MSD / VACF (ljmd_tcf.cpp), the pressure tensor (ljmd_stress.cpp) and the heat flux
-// (ljmd_heatflux.cpp), which are two descriptors over the one series core (ljmd_series.cpp), and the van Hove
-// self-correlation (ljmd_vanhove.cpp).  What the cores share -- the view through which they see an engine, their named
-// device buffers, the timer around one accumulate -- and each core's state and functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host, tests/tcf_host,
-// tests/stress_host, tests/heatflux_host, tests/vanhove_host); every C entry point that takes a handle is in
-// ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_tcf.h, ljmd_stress.h, ljmd_heatflux.h and
-// ljmd_vanhove.h.
+// (ljmd_rdf.cpp); the pressure tensor (ljmd_stress.cpp) and the heat flux (ljmd_heatflux.cpp), which are two descriptors
+// over the one series core (ljmd_series.cpp); MSD / VACF (ljmd_tcf.cpp) and the van Hove self-correlation
+// (ljmd_vanhove.cpp), which are two descriptors over the one time-origin core (ljmd_origins.cpp).  What the cores share
+// -- the view through which they see an engine, their named device buffers, the timer around one accumulate -- and each
+// core's state and functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host,
+// tests/tcf_host, tests/stress_host, tests/heatflux_host, tests/vanhove_host); every C entry point that takes a handle
+// is in ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_stress.h, ljmd_heatflux.h, ljmd_tcf.h
+// and ljmd_vanhove.h, the latter two over ljmd_origins.h.
 #ifndef LJMD_RESIDENT_H
 #define LJMD_RESIDENT_H
 
@@ -14,6 +15,7 @@
 #include "ljmd_rdf.h"
 #include "ljmd_stress.h"
 #include "ljmd_tcf.h"
+#include "ljmd_tcf_host.h"
 #include "ljmd_vanhove.h"
 
 #include <array>
@@ -44,9 +46,9 @@ struct DeviceBuffer {
     const char *name;
 };
 
-// allocates in the order of the array; the buffer that fails stays NULL: "<who>: out of device memory for <name>"
-template <size_t N>
-int alloc_buffers(std::string *err, const char *who, const std::array<DeviceBuffer, N> &bufs)
+// allocates in the order of the list; the buffer that fails stays NULL: "<who>: out of device memory for <name>"
+template <class Buffers>
+int alloc_buffers(std::string *err, const char *who, const Buffers &bufs)
 {
     for (const DeviceBuffer &b : bufs)
         if (hipMalloc(b.p, b.bytes) != hipSuccess) {
@@ -58,8 +60,8 @@ int alloc_buffers(std::string *err, const char *who, const std::array<DeviceBuff
 }
 
 // frees what exists, after what may still use it on `stream`
-template <size_t N>
-void free_buffers(const std::array<DeviceBuffer, N> &bufs, hipStream_t stream)
+template <class Buffers>
+void free_buffers(const Buffers &bufs, hipStream_t stream)
 {
     bool any = false;
     for (const DeviceBuffer &b : bufs) any = any || *b.p;
@@ -139,44 +141,95 @@ void rdf_release(RdfState *st, hipStream_t stream);
 
 }  // namespace ljmdr
 
-namespace ljmdt {
+// The time-origin observables -- MSD / VACF and the van Hove self-correlation: one state, one core (ljmd_origins.cpp), and
+// a constant descriptor of each observable (ljmd_tcf.cpp, ljmd_vanhove.cpp) that the core is driven by.  Snapshot
+// numbering, window, counts and quotient are ljmd_tcf_host.h's.  The histogram fields are 0 / NULL without a histogram.
+namespace ljmdh {
 
-using ljmdh::ResidentView;
-
-// sizes of one configuration, all in size_t: the ring of n = 262 144 with 512 slots has 6.4e9 bytes
-struct TcfSizes {
+// sizes of one configuration, all in size_t: the ring of n = 262 144 with 512 slots and 6 components has 6.4e9 bytes
+struct OriginSizes {
     int slots = 0, ents = 0, nblk = 0;  // ents = slots + 1 entries per row of the partials
     size_t n_pad = 0;
-    size_t cur_bytes = 0, ring_bytes = 0, part_bytes = 0, flag_bytes = 0, sums_bytes = 0;
+    size_t cur_bytes = 0, ring_bytes = 0, part_bytes = 0, flag_bytes = 0, sums_bytes = 0, hist_bytes = 0;
 };
-TcfSizes tcf_sizes(int n, int max_lag, int stride);
 
 // the grid of the terms kernel for n_live >= 1 live origins: (nblk, slices), chunk origins per slice
-struct TcfSlices {
+struct OriginSlices {
     int chunk = 0, slices = 0;
 };
-TcfSlices tcf_plan_slices(int nblk, int n_live);
 
-struct TcfState {
+struct OriginState {
     int max_lag = 0;                // 0 = not configured
-    int stride = 0, n = 0;
-    TcfSizes sz;
+    int stride = 0, n = 0, nbins = 0;
+    double rmax = 0, dr = 0, inv_dr = 0;
+    OriginSizes sz;
     double *d_cur = nullptr, *d_ring = nullptr;
-    unsigned long long *d_part = nullptr;
+    unsigned long long *d_hist = nullptr, *d_part = nullptr;
     int32_t *d_flag = nullptr, *d_range = nullptr;
     uint64_t *d_sums = nullptr;
-    ljmdh::KernelTimer timer;
+    KernelTimer timer;
     int last_live = 0;              // live origins the most recent accumulate visited
     int64_t s = 0;                  // number of the next snapshot of this trajectory
     int64_t snapshots = 0;
     std::vector<int64_t> counts;    // [max_lag + 1] origins that contributed to each lag
 };
 
-int not_configured(std::string *err, const char *who);
+struct OriginDesc {
+    const char *phrase;             // "the van Hove function": "the van Hove function is not configured"
+    const char *brief;              // "van Hove": "van Hove launch failed"
+    const char *tag;                // "vanhove": ljmd_vanhove_configure, ljmd_vanhove_reset
+    const char *limits;             // "VANHOVE": LJMD_VANHOVE_MAX_ORIGINS
+    const char *range;              // what LJMD_ERR_RANGE says happened, up to "; the flag stays until ..."
+    int components;                 // per particle: 6 = ru xyz, v xyz; 3 = ru xyz
+    bool needs_v;
+    int max_lag, max_origins;
+    size_t max_n;
+    int max_bins;                   // 0: no histogram, and configure looks at neither nbins nor rmax
+    bool chunk_override;            // ResidentView::vanhove_chunk applies
+    // the observable's launches of one accumulate: the gather with ga as it is, and for w.n_live > 0 its terms kernel,
+    // the arguments filled from the state, the window and the slices, and the fold with fa as it is
+    hipError_t (*launch)(const OriginState &st, const ResidentView &v, const TcfWindow &w, const OriginSlices &p,
+                         const ljmdk::OriginGatherArgs &ga, const ljmdk::OriginFoldArgs &fa);
+};
+
+OriginSizes origin_sizes(const OriginDesc &d, int n, int max_lag, int stride, int nbins);
+// chunk unset: origins per slice by kOriginTargetWorkgroups; set: that many, clamped to [1, min(n_live, kOriginMaxChunk)]
+OriginSlices origin_plan_slices(int nblk, int n_live, std::optional<int> chunk = std::nullopt);
+
+int origin_not_configured(const OriginDesc &d, std::string *err, const char *who);
 // refuses a multi-device handle and a rank engine of G > 1 itself
+int origin_configure(const OriginDesc &d, OriginState *st, std::string *err, const char *who, const ResidentView &v,
+                     int32_t max_lag, int32_t origin_stride, int32_t nbins, double rmax);
+int origin_accumulate(const OriginDesc &d, OriginState *st, std::string *err, const char *who, const ResidentView &v);
+// waits for the device; LJMD_ERR_RANGE while the sticky word is set; hist [max_lag + 1][nbins + 1] or NULL, words
+// [2][max_lag + 1][3] or NULL
+int origin_fetch(const OriginDesc &d, OriginState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *hist,
+                 uint64_t *words, int64_t *counts, int64_t *n_snapshots);
+// the two kinds of sums as quotients (tcf_quotient), each [max_lag + 1] or NULL
+int origin_read(const OriginDesc &d, OriginState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *hist,
+                double *kind0, double *kind1, int64_t *counts, int64_t *n_snapshots);
+int origin_reset(const OriginDesc &d, OriginState *st, std::string *err, const char *who, const ResidentView &v);
+int origin_profile_read(const OriginDesc &d, OriginState *st, std::string *err, const char *who, const ResidentView &v,
+                        double *kernel_ms, int32_t *origins_live);
+// ljmd_set_state: the stored origins are dropped and the numbering restarts; histogram, sums and counts stay
+void origin_new_trajectory(OriginState *st);
+void origin_release(OriginState *st, hipStream_t stream);
+
+}  // namespace ljmdh
+
+namespace ljmdt {
+
+using ljmdh::ResidentView;
+using TcfSizes = ljmdh::OriginSizes;
+using TcfSlices = ljmdh::OriginSlices;
+using TcfState = ljmdh::OriginState;
+
+TcfSizes tcf_sizes(int n, int max_lag, int stride);
+TcfSlices tcf_plan_slices(int nblk, int n_live);
+
+int not_configured(std::string *err, const char *who);
 int tcf_configure(TcfState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_lag, int32_t origin_stride);
 int tcf_accumulate(TcfState *st, std::string *err, const char *who, const ResidentView &v);
-// waits for the device; LJMD_ERR_RANGE while the sticky word is set; words [2][max_lag + 1][3] or NULL
 int tcf_fetch(TcfState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *words, int64_t *counts,
               int64_t *n_snapshots);
 int tcf_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *msd, double *vacf, int64_t *counts,
@@ -184,7 +237,6 @@ int tcf_read(TcfState *st, std::string *err, const char *who, const ResidentView
 int tcf_reset(TcfState *st, std::string *err, const char *who, const ResidentView &v);
 int tcf_profile_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms,
                      int32_t *origins_live);
-// ljmd_set_state: the stored origins are dropped and the numbering restarts; sums and counts stay
 void tcf_new_trajectory(TcfState *st);
 void tcf_release(TcfState *st, hipStream_t stream);
 
@@ -281,45 +333,18 @@ void heatflux_release(HeatfluxState *st, hipStream_t stream);
 namespace ljmdv {
 
 using ljmdh::ResidentView;
+using VhSizes = ljmdh::OriginSizes;
+using VhSlices = ljmdh::OriginSlices;
+using VanHoveState = ljmdh::OriginState;
 
-// sizes of one configuration, all in size_t: the ring of n = 262 144 with 512 slots has 3.2e9 bytes
-struct VhSizes {
-    int slots = 0, ents = 0, nblk = 0;  // ents = slots + 1 entries per row of the partials
-    size_t n_pad = 0;
-    size_t cur_bytes = 0, ring_bytes = 0, part_bytes = 0, flag_bytes = 0, sums_bytes = 0, hist_bytes = 0;
-};
 VhSizes vanhove_sizes(int n, int max_lag, int stride, int nbins);
-
-// the grid of the terms kernel for n_live >= 1 live origins: (nblk, slices), chunk origins per slice
-struct VhSlices {
-    int chunk = 0, slices = 0;
-};
-// chunk unset: origins per slice by kVhTargetWorkgroups; set: that many, clamped to [1, min(n_live, kVhMaxChunk)] (tests)
+// chunk: LJMD_VANHOVE_CHUNK (tests)
 VhSlices vanhove_plan_slices(int nblk, int n_live, std::optional<int> chunk = std::nullopt);
 
-struct VanHoveState {
-    int max_lag = 0;                // 0 = not configured
-    int stride = 0, n = 0, nbins = 0;
-    double rmax = 0, dr = 0, inv_dr = 0;
-    VhSizes sz;
-    double *d_cur = nullptr, *d_ring = nullptr;
-    unsigned long long *d_hist = nullptr, *d_part = nullptr;
-    int32_t *d_flag = nullptr, *d_range = nullptr;
-    uint64_t *d_sums = nullptr;
-    ljmdh::KernelTimer timer;
-    int last_live = 0;              // live origins the most recent accumulate visited
-    int64_t s = 0;                  // number of the next snapshot of this trajectory
-    int64_t snapshots = 0;
-    std::vector<int64_t> counts;    // [max_lag + 1] origins that contributed to each lag
-};
-
 int not_configured(std::string *err, const char *who);
-// refuses a multi-device handle and a rank engine of G > 1 itself
 int vanhove_configure(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_lag,
                       int32_t origin_stride, int32_t nbins, double rmax);
 int vanhove_accumulate(VanHoveState *st, std::string *err, const char *who, const ResidentView &v);
-// waits for the device; LJMD_ERR_RANGE while the sticky word is set; hist [max_lag + 1][nbins + 1] or NULL, words
-// [2][max_lag + 1][3] or NULL
 int vanhove_fetch(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *hist, uint64_t *words,
                   int64_t *counts, int64_t *n_snapshots);
 int vanhove_read(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *hist, double *r2,
@@ -327,7 +352,6 @@ int vanhove_read(VanHoveState *st, std::string *err, const char *who, const Resi
 int vanhove_reset(VanHoveState *st, std::string *err, const char *who, const ResidentView &v);
 int vanhove_profile_read(VanHoveState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms,
                          int32_t *origins_live);
-// ljmd_set_state: the stored origins are dropped and the numbering restarts; histogram, sums and counts stay
 void vanhove_new_trajectory(VanHoveState *st);
 void vanhove_release(VanHoveState *st, hipStream_t stream);
 

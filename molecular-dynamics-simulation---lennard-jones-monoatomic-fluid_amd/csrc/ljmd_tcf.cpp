@@ -1,12 +1,7 @@
-// ljmd_tcf.cpp -- host core of the MSD / VACF accumulation of the system resident on a one-rank engine (kernels:
-// ljmd_tcf.hip): guards, sizes, argument blocks, launches, reads and resets.  It sees an engine only through ResidentView
-// and links without anything of struct ljmd (tests/tcf_host); the C entry points are in ljmd_resident.cpp.
+// ljmd_tcf.cpp -- the engine's resident MSD / VACF on the host (kernels: ljmd_tcf.hip): its descriptor for the time-origin
+// core (ljmd_origins.cpp) and the arguments of its terms kernel.  Like the core it sees an engine only through
+// ResidentView and links without anything of struct ljmd (tests/tcf_host); the C entry points are in ljmd_resident.cpp.
 #include "ljmd_resident.h"
-#include "ljmd_tcf_host.h"
-
-#include <algorithm>
-#include <cstdio>
-#include <new>
 
 using namespace ljmdh;
 
@@ -14,205 +9,67 @@ namespace ljmdt {
 
 namespace {
 
-// the buffers of a state in the order they are allocated; the sizes and the ring's name matter to configure only
-std::array<DeviceBuffer, 6> buffers(TcfState *st, const TcfSizes &z = {}, const char *ring = "")
+hipError_t launch(const TcfState &st, const ResidentView &v, const TcfWindow &w, const TcfSlices &p, const TcfGatherArgs &ga,
+                  const TcfFoldArgs &fa)
 {
-    return {{{(void **)&st->d_sums, z.sums_bytes, "the sums"},
-             {(void **)&st->d_range, sizeof(int32_t), "the range word"},
-             {(void **)&st->d_cur, z.cur_bytes, "the current snapshot"},
-             {(void **)&st->d_part, z.part_bytes, "the partial sums"},
-             {(void **)&st->d_flag, z.flag_bytes, "the range flags"},
-             {(void **)&st->d_ring, z.ring_bytes, ring}}};
+    hipError_t e = launch_tcf_gather(ga, v.stream);
+    if (e != hipSuccess || w.n_live == 0) return e;
+    TcfTermsArgs ta{};
+    ta.cur = st.d_cur; ta.ring = st.d_ring; ta.part = st.d_part; ta.flag = st.d_flag;
+    ta.n_pad = st.sz.n_pad;
+    ta.nblk = st.sz.nblk; ta.slots = st.sz.slots; ta.ents = st.sz.ents; ta.stride = st.stride;
+    ta.n_live = w.n_live; ta.lag_first = w.lag_first; ta.slot_first = w.slot_first;
+    ta.chunk = p.chunk; ta.slices = p.slices;
+    e = launch_tcf_terms(ta, v.stream);
+    return e != hipSuccess ? e : launch_tcf_fold(fa, v.stream);
 }
+
+static_assert(kTcfMaxLag == LJMD_TCF_MAX_LAG && kTcfMaxOrigins == LJMD_TCF_MAX_ORIGINS,
+              "MSD / VACF limits out of sync with include/ljmd.h");
+
+const OriginDesc kDesc = {"MSD / VACF", "MSD / VACF", "tcf", "TCF",
+                          "an MSD or VACF term was not finite or |term| >= 2^40 and entered as 0",
+                          6, true, kTcfMaxLag, kTcfMaxOrigins, kTcfMaxN, 0, false, launch};
 
 }  // namespace
 
-int not_configured(std::string *err, const char *who)
-{
-    return fail(err, LJMD_ERR_STATE, "%s: MSD / VACF is not configured (call ljmd_tcf_configure first)", who);
-}
-
-TcfSizes tcf_sizes(int n, int max_lag, int stride)
-{
-    TcfSizes z;
-    z.slots = max_lag / stride + 1;
-    z.ents = z.slots + 1;
-    z.n_pad = ((size_t)n + kTcfBlock - 1) / kTcfBlock * kTcfBlock;
-    z.nblk = (int)(z.n_pad / kTcfBlock);
-    z.cur_bytes = 6 * z.n_pad * sizeof(double);
-    z.ring_bytes = (size_t)z.slots * 6 * z.n_pad * sizeof(double);
-    z.part_bytes = (size_t)z.nblk * (size_t)z.ents * 4 * sizeof(unsigned long long);
-    z.flag_bytes = (size_t)z.nblk * (size_t)z.slots * sizeof(int32_t);
-    z.sums_bytes = 2 * ((size_t)max_lag + 1) * 3 * sizeof(uint64_t);
-    return z;
-}
-
-TcfSlices tcf_plan_slices(int nblk, int n_live)
-{
-    const int want = (kTcfTargetWorkgroups + nblk - 1) / nblk;                 // slices that fill the grid ...
-    const int need = (n_live + kTcfMaxChunk - 1) / kTcfMaxChunk;               // ... and slices the LDS budget asks for
-    const int slices = std::min(n_live, std::max(want, need));
-    TcfSlices p;
-    p.chunk = (n_live + slices - 1) / slices;
-    p.slices = (n_live + p.chunk - 1) / p.chunk;
-    return p;
-}
-
-void tcf_release(TcfState *st, hipStream_t stream)
-{
-    free_buffers(buffers(st), stream);
-    st->timer.destroy();
-    *st = {};
-}
-
-void tcf_new_trajectory(TcfState *st) { st->s = 0; }     // the window of a snapshot follows from s: no origin is live
+int not_configured(std::string *err, const char *who) { return origin_not_configured(kDesc, err, who); }
+TcfSizes tcf_sizes(int n, int max_lag, int stride) { return origin_sizes(kDesc, n, max_lag, stride, 0); }
+TcfSlices tcf_plan_slices(int nblk, int n_live) { return origin_plan_slices(nblk, n_live); }
+void tcf_release(TcfState *st, hipStream_t stream) { origin_release(st, stream); }
+void tcf_new_trajectory(TcfState *st) { origin_new_trajectory(st); }
 
 int tcf_configure(TcfState *st, std::string *err, const char *who, const ResidentView &v, int32_t max_lag, int32_t origin_stride)
 {
-    static_assert(kTcfMaxLag == LJMD_TCF_MAX_LAG && kTcfMaxOrigins == LJMD_TCF_MAX_ORIGINS,
-                  "MSD / VACF limits out of sync with include/ljmd.h");
-    if (max_lag < 0 || max_lag > kTcfMaxLag)
-        return fail(err, LJMD_ERR_INVALID_ARG, "%s: max_lag = %d outside 1..%d (0 switches MSD / VACF off)", who, max_lag,
-                    kTcfMaxLag);
-    if (max_lag > 0 && origin_stride < 1) return fail(err, LJMD_ERR_INVALID_ARG, "%s: origin_stride must be >= 1", who);
-    if (max_lag > 0 && max_lag / origin_stride + 1 > kTcfMaxOrigins)
-        return fail(err, LJMD_ERR_INVALID_ARG, "%s: max_lag / origin_stride + 1 = %d exceeds LJMD_TCF_MAX_ORIGINS (%d)", who,
-                    max_lag / origin_stride + 1, kTcfMaxOrigins);
-    if (max_lag > 0 && (v.multi || v.G != 1))
-        return fail(err, LJMD_ERR_INVALID_ARG, "%s: n_ranks = %d%s: MSD / VACF of the resident system needs a one-rank "
-                                               "engine (ljmd_create with n_ranks = 1)", who, v.G,
-                    v.multi ? " (multi-device handle)" : "");
-    if (max_lag > 0 && (v.n < 1 || (size_t)v.n > kTcfMaxN || v.P < v.n))
-        return fail(err, LJMD_ERR_INVALID_ARG, "%s: n = %d outside 1..%zu", who, v.n, kTcfMaxN);
-    tcf_release(st, v.stream);
-    if (max_lag == 0) return LJMD_OK;
-    const TcfSizes z = tcf_sizes(v.n, max_lag, origin_stride);
-    char ring[48];
-    std::snprintf(ring, sizeof ring, "the origin ring (%d slots)", z.slots);
-    const auto bufs = buffers(st, z, ring);
-    auto body = [&]() -> int {
-        try {
-            st->counts.assign((size_t)max_lag + 1, 0);
-        } catch (const std::bad_alloc &) {
-            return fail(err, LJMD_ERR_ALLOC, "%s: out of host memory for the counts", who);
-        }
-        LJMD_TRY(alloc_buffers(err, who, bufs));
-        LJMD_HIP(err, st->timer.create());
-        // the padding of cur and of the ring is zeroed here and never written; part and flag are written before read
-        for (const DeviceBuffer &b : bufs) LJMD_HIP(err, hipMemsetAsync(*b.p, 0, b.bytes, v.stream));
-        return LJMD_OK;
-    };
-    const int rc_ = body();
-    if (rc_ != LJMD_OK) {
-        tcf_release(st, v.stream);
-        return rc_;
-    }
-    st->max_lag = max_lag;
-    st->stride = origin_stride;
-    st->n = v.n;
-    st->sz = z;
-    return LJMD_OK;
+    return origin_configure(kDesc, st, err, who, v, max_lag, origin_stride, 0, 0.0);
 }
 
 int tcf_accumulate(TcfState *st, std::string *err, const char *who, const ResidentView &v)
 {
-    if (st->max_lag == 0) return not_configured(err, who);
-    if (v.n != st->n || !v.ru || !v.v || !v.perm)
-        return fail(err, LJMD_ERR_STATE, "%s: the engine is not the one MSD / VACF was configured for", who);
-    const TcfWindow w = tcf_window(st->s, st->max_lag, st->stride, st->sz.slots);
-    TcfGatherArgs ga{};
-    ga.ru = v.ru; ga.v = v.v; ga.perm = v.perm;
-    ga.cur = st->d_cur;
-    ga.store = w.store_slot >= 0 ? st->d_ring + (size_t)w.store_slot * 6 * st->sz.n_pad : nullptr;
-    ga.n = v.n; ga.P = v.P; ga.n_pad = st->sz.n_pad;
-    LJMD_HIP(err, st->timer.start(v.stream));
-    hipError_t e = launch_tcf_gather(ga, v.stream);
-    if (e == hipSuccess && w.n_live > 0) {
-        const TcfSlices p = tcf_plan_slices(st->sz.nblk, w.n_live);
-        TcfTermsArgs ta{};
-        ta.cur = st->d_cur; ta.ring = st->d_ring; ta.part = st->d_part; ta.flag = st->d_flag;
-        ta.n_pad = st->sz.n_pad;
-        ta.nblk = st->sz.nblk; ta.slots = st->sz.slots; ta.ents = st->sz.ents; ta.stride = st->stride;
-        ta.n_live = w.n_live; ta.lag_first = w.lag_first; ta.slot_first = w.slot_first;
-        ta.chunk = p.chunk; ta.slices = p.slices;
-        TcfFoldArgs fa{};
-        fa.part = st->d_part; fa.flag = st->d_flag; fa.sums = st->d_sums; fa.range = st->d_range;
-        fa.nblk = st->sz.nblk; fa.slots = st->sz.slots; fa.ents = st->sz.ents; fa.stride = st->stride; fa.max_lag = st->max_lag;
-        fa.n_live = w.n_live; fa.lag_first = w.lag_first;
-        fa.chunk = p.chunk; fa.slices = p.slices;
-        e = launch_tcf_terms(ta, v.stream);
-        if (e == hipSuccess) e = launch_tcf_fold(fa, v.stream);
-    }
-    if (e != hipSuccess) return fail(err, LJMD_ERR_HIP, "%s: MSD / VACF launch failed: %s", who, hipGetErrorString(e));
-    LJMD_HIP(err, st->timer.stop(v.stream));
-    st->last_live = w.n_live;
-    tcf_count(w, st->stride, st->counts.data());
-    ++st->s;
-    ++st->snapshots;
-    return LJMD_OK;
+    return origin_accumulate(kDesc, st, err, who, v);
 }
 
 int tcf_fetch(TcfState *st, std::string *err, const char *who, const ResidentView &v, uint64_t *words, int64_t *counts,
               int64_t *n_snapshots)
 {
-    if (st->max_lag == 0) return not_configured(err, who);
-    int32_t range = 0;
-    LJMD_HIP(err, hipMemcpyAsync(&range, st->d_range, sizeof range, hipMemcpyDeviceToHost, v.stream));
-    if (words) LJMD_HIP(err, hipMemcpyAsync(words, st->d_sums, st->sz.sums_bytes, hipMemcpyDeviceToHost, v.stream));
-    LJMD_HIP(err, hipStreamSynchronize(v.stream));
-    // the handle is not poisoned: the trajectory itself is sound
-    if (range != 0)
-        return fail(err, LJMD_ERR_RANGE, "%s: an MSD or VACF term was not finite or |term| >= 2^40 and entered as 0; the "
-                                         "flag stays until ljmd_tcf_reset", who);
-    if (counts) std::copy(st->counts.begin(), st->counts.end(), counts);
-    if (n_snapshots) *n_snapshots = st->snapshots;
-    return LJMD_OK;
+    return origin_fetch(kDesc, st, err, who, v, nullptr, words, counts, n_snapshots);
 }
 
 int tcf_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *msd, double *vacf, int64_t *counts,
              int64_t *n_snapshots)
 {
-    if (st->max_lag == 0) return not_configured(err, who);
-    std::vector<uint64_t> w;
-    if (msd || vacf) {
-        try {
-            w.resize(st->sz.sums_bytes / sizeof(uint64_t));
-        } catch (const std::bad_alloc &) {
-            return fail(err, LJMD_ERR_ALLOC, "%s: out of host memory", who);
-        }
-    }
-    LJMD_TRY(tcf_fetch(st, err, who, v, w.empty() ? nullptr : w.data(), counts, n_snapshots));
-    const size_t rows = (size_t)st->max_lag + 1;
-    double *const dst[2] = {msd, vacf};
-    for (int kind = 0; kind < 2; ++kind)
-        for (size_t l = 0; dst[kind] && l < rows; ++l) {
-            const uint64_t *x = w.data() + ((size_t)kind * rows + l) * 3;
-            const uint64_t x3[3] = {x[0], x[1], x[2]};
-            dst[kind][l] = tcf_quotient(x3, st->n, st->counts[l]);
-        }
-    return LJMD_OK;
+    return origin_read(kDesc, st, err, who, v, nullptr, msd, vacf, counts, n_snapshots);
 }
 
 int tcf_reset(TcfState *st, std::string *err, const char *who, const ResidentView &v)
 {
-    if (st->max_lag == 0) return not_configured(err, who);
-    LJMD_HIP(err, hipMemsetAsync(st->d_sums, 0, st->sz.sums_bytes, v.stream));
-    LJMD_HIP(err, hipMemsetAsync(st->d_range, 0, sizeof(int32_t), v.stream));
-    std::fill(st->counts.begin(), st->counts.end(), 0);
-    st->s = 0;
-    st->snapshots = 0;
-    return LJMD_OK;
+    return origin_reset(kDesc, st, err, who, v);
 }
 
 int tcf_profile_read(TcfState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms,
                      int32_t *origins_live)
 {
-    if (st->max_lag == 0) return not_configured(err, who);
-    float ms = 0.0f;
-    LJMD_HIP(err, st->timer.elapsed_ms(v.stream, &ms));
-    if (kernel_ms) *kernel_ms = (double)ms;
-    if (origins_live) *origins_live = st->timer.timed ? st->last_live : 0;
-    return LJMD_OK;
+    return origin_profile_read(kDesc, st, err, who, v, kernel_ms, origins_live);
 }
 
 }  // namespace ljmdt

@@ -1,7 +1,8 @@
 // ljmd_tcf_arith.h -- the one copy of the device arithmetic of the MSD / VACF accumulation, shared by the batch engine's
 // kernel (ljmd_batch_tcf.hip) and the single engine's (ljmd_tcf.hip): a term enters an exact integer sum as
 // Q(t) = RNE(t 2^64), split into two int64 limbs that a wave sums by integer shuffles and lane 0 adds, as one 128-bit
-// integer, into an LDS entry.
+// integer, into an LDS entry; and the two terms of one origin for the particles of a thread (tcf_origin).  The van Hove
+// kernel (ljmd_vanhove.hip) uses the limbs and the entries.
 #ifndef LJMD_TCF_ARITH_H
 #define LJMD_TCF_ARITH_H
 
@@ -35,6 +36,50 @@ __device__ __forceinline__ void entry_add(unsigned long long *entry, long long h
     const unsigned long long old = atomicAdd(&entry[0], x0);
     const unsigned long long carry = (unsigned long long)(old + x0 < old);
     atomicAdd(&entry[1], x1 + carry);
+}
+
+// One origin against the current snapshot, for the K particles of a thread: the MSD and the VACF term of each, summed
+// over the wave and added by lane 0 into entry[2 kinds][2 words]; `with0` (uniform across the workgroup): the origin is
+// at lag 1, and its lag-0 terms -- the origin against itself -- go to entry0 the same way.  org_of(k, c) loads
+// component c of the origin of particle k.
+template <int K, class Org>
+__device__ __forceinline__ void tcf_origin(const double (&cur)[K][6], Org &&org_of, bool with0, int lane,
+                                           unsigned long long *entry, unsigned long long *entry0, bool &bad)
+{
+    long long m_hi = 0, m_lo = 0, c_hi = 0, c_lo = 0;       // MSD and VACF limbs of this origin
+    long long z_hi = 0, z_lo = 0, w_hi = 0, w_lo = 0;       // ... and of its lag 0
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double org[6];
+#pragma unroll
+        for (int c = 0; c < 6; ++c) org[c] = org_of(k, c);
+        const double dx = cur[k][0] - org[0], dy = cur[k][1] - org[1], dz = cur[k][2] - org[2];
+        tcf_add(m_hi, m_lo, (dx * dx + dy * dy) + dz * dz, bad);
+        tcf_add(c_hi, c_lo, (cur[k][3] * org[3] + cur[k][4] * org[4]) + cur[k][5] * org[5], bad);
+        if (with0) {
+            const double ex = org[0] - org[0], ey = org[1] - org[1], ez = org[2] - org[2];
+            tcf_add(z_hi, z_lo, (ex * ex + ey * ey) + ez * ez, bad);
+            tcf_add(w_hi, w_lo, (org[3] * org[3] + org[4] * org[4]) + org[5] * org[5], bad);
+        }
+    }
+    m_hi = wave_sum_i64(m_hi);
+    m_lo = wave_sum_i64(m_lo);
+    c_hi = wave_sum_i64(c_hi);
+    c_lo = wave_sum_i64(c_lo);
+    if (with0) {
+        z_hi = wave_sum_i64(z_hi);
+        z_lo = wave_sum_i64(z_lo);
+        w_hi = wave_sum_i64(w_hi);
+        w_lo = wave_sum_i64(w_lo);
+    }
+    if (lane == 0) {
+        entry_add(entry, m_hi, m_lo);
+        entry_add(entry + 2, c_hi, c_lo);
+        if (with0) {
+            entry_add(entry0, z_hi, z_lo);
+            entry_add(entry0 + 2, w_hi, w_lo);
+        }
+    }
 }
 
 }  // namespace ljmdk

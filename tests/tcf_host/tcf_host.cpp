@@ -444,6 +444,14 @@ void sizes_and_slices()
             if (!ok) std::printf("slices of nblk = %d, n_live = %d: chunk %d slices %d\n", nblk, n_live, p.chunk, p.slices);
             check(ok, "slice plan");
         }
+    // the premise of test_gpu_tcf_resident.py::test_slices_of_more_than_one_origin (n = 33000: nblk = 33, max_lag = 37)
+    check(tcf_plan_slices(33, 32).chunk == 1, "nblk 33: 32 live origins still have slices of one origin");
+    const int want_slices[] = {17, 17, 18, 18, 19};
+    for (int l = 33; l <= 37; ++l) {
+        const TcfSlices p = tcf_plan_slices(33, l);
+        if (p.chunk != 2 || p.slices != want_slices[l - 33]) std::printf("nblk 33, n_live %d: chunk %d slices %d\n", l, p.chunk, p.slices);
+        check(p.chunk == 2 && p.slices == want_slices[l - 33], "nblk 33: from 33 live origins on, slices of two origins");
+    }
 }
 
 }  // namespace

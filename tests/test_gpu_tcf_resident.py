@@ -166,6 +166,26 @@ def test_ring_wrap_and_many_slices(n, max_lag, n_snap):
     assert np.array_equal(counts, tcf_model.reference_counts(n_snap, max_lag, 1))
 
 
+def test_slices_of_more_than_one_origin():
+    """n = 33000 pads to 33 particle blocks, so the planner wants 32 slices and, from 33 live origins on, cuts them two to
+    a slice (tests/tcf_host pins this): the terms kernel walks more than one origin of a slice, 33 and 35 live origins
+    leave a last slice of one origin, 34, 36 and 37 full ones, and the lag-0 entry lies behind either.  Every smaller
+    system of this file has slices of one origin."""
+    n, max_lag, n_snap = 33000, 37, 41
+    p, r, v = synthetic.make_config(n, seed=62)
+    m = tcf_model.TcfModel(max_lag, 1)
+    with Engine(p) as eng:
+        _start(eng, r, v)
+        eng.tcf_configure(max_lag, 1)
+        for s in range(n_snap):
+            if s:
+                eng.verlet_steps(1)
+            _take(eng, m)
+        _, counts, _, _ = _assert_equals_model(eng, m, n)
+        assert eng.tcf_profile()["origins_live"] == max_lag
+    assert np.array_equal(counts, tcf_model.reference_counts(n_snap, max_lag, 1))
+
+
 # ---- 5. trajectories -------------------------------------------------------------------------------------------------
 def test_trajectories_reset_reconfigure_off_and_destroy():
     n, max_lag, stride = 500, 3, 1
