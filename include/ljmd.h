@@ -786,8 +786,9 @@ int ljmd_batch_set_tail_corrections(ljmd_batch_t *h, int32_t on);
  * Setting the mode the handle already has changes nothing.  Works on both kinds of handle. */
 int ljmd_batch_set_precision(ljmd_batch_t *h, int32_t precision_mode);
 /* Kernel time (HIP events, ms) and launch count of the last ljmd_batch_steps call; either pointer may be NULL.
- * Both include the g(r), MSD / VACF, pressure tensor and heat flux launches of that call (ljmd_batch_rdf_configure /
- * ljmd_batch_tcf_configure / ljmd_batch_stress_configure / ljmd_batch_heatflux_configure with every > 0).
+ * Both include the g(r), MSD / VACF, pressure tensor, heat flux and van Hove launches of that call
+ * (ljmd_batch_rdf_configure / ljmd_batch_tcf_configure / ljmd_batch_stress_configure / ljmd_batch_heatflux_configure /
+ * ljmd_batch_vanhove_configure with every > 0).
  * Replicas of different kernel classes (n <= 128, 512, 1024, 2048, 4096) run as separate groups of launches, by
  * default each on a stream of its own (LJMD_BATCH_GROUP_STREAMS=0: one after another on the handle's stream); the
  * kernel time is then the span from the first group's first launch to the last group's end, not a sum over groups,
@@ -942,6 +943,65 @@ int ljmd_batch_heatflux_accumulate(ljmd_batch_t *h);
 int ljmd_batch_heatflux_read_exact(ljmd_batch_t *h, int64_t *words /* [n][B][9][3] */, int64_t *n_snapshots);
 int ljmd_batch_heatflux_read(ljmd_batch_t *h, double *j /* [n][B][3] */, double *parts /* [n][B][3][3], may be NULL */, int64_t *n_snapshots);
 int ljmd_batch_heatflux_reset(ljmd_batch_t *h);
+/*
+ * Van Hove self-correlation G_s(r, tau) of every replica, time-origin averaged, on the device (ljmd_batch_vanhove_*):
+ * per replica, integer for integer, what ljmd_vanhove_* above is for B = 1.
+ *
+ * Definition.  Snapshots, their numbering s, the origin rule, the ring slot (s / origin_stride) % slots with slots =
+ * max_lag / origin_stride + 1 <= LJMD_BATCH_VANHOVE_MAX_ORIGINS, the lag-0 row added when the next snapshot arrives and
+ * count[l] on the host, the same for all replicas, are those of ljmd_batch_tcf_* above; a snapshot here is the resident
+ * ru of every replica only, and the ring is the feature's own.  dr_b = rmax[b] / nbins.  Per replica b, particle i,
+ * origin t0 and lag l, unfused and left to right:
+ *   d = ru(t0 + l) - ru(t0) per axis ;  r2 = (dx*dx + dy*dy) + dz*dz     (the MSD term of ljmd_batch_tcf_*, bit for bit)
+ *   r4 = r2 * r2 ;  r = sqrt(r2) (correctly rounded) ;  bin = int(r / dr_b) exactly (the true quotient, truncated)
+ *   H[b][l][min(bin, nbins)] += 1 (column nbins is the overflow column); H is [B][max_lag + 1][nbins + 1] uint64
+ *   S2[b][l] += Q(r2), S4[b][l] += Q(r4), Q(t) = RNE(t 2^64): signed 192-bit integers of three int64 limbs, least
+ *   significant first
+ * Range: when r2 or r4 is not finite or r4 >= 2^40 the particle counts in the overflow column, enters both sums as 0
+ * and sets the replica's sticky range word (an arithmetic flag: nothing wraps, nothing faults, and no float-to-int
+ * conversion sees such a value).  Invariants: every row H[b][l][.] sums to n_b count[l]; S2 equals the MSD words of
+ * ljmd_batch_tcf_* configured with the same (max_lag, origin_stride) on the same handle, word for word.  The integers do
+ * not depend on B, the replica's slot, the other replicas, launch grouping, group streams, precision mode (given the same
+ * ru) or the order of the particles.  r2[b][l] = ljmd_tcf_from_exact(S2[b][l], n_b, count[l]) and r4[b][l] likewise: one
+ * rounding, one division, 0 where count[l] == 0.  The non-Gaussian parameter is alpha2 = 3 r4 / (5 r2^2) - 1.
+ * configure: the guards of ljmd_batch_tcf_configure in their order (max_lag in 0..LJMD_BATCH_VANHOVE_MAX_LAG, every >= 0,
+ * origin_stride >= 1, the origin count), then 1 <= nbins <= LJMD_BATCH_VANHOVE_MAX_BINS, rmax not NULL, every rmax[b]
+ * finite and > 0 with rmax[b] / nbins a normal number ("replica <b>").  max_lag = 0 switches the feature off and frees
+ * everything (the arguments after it but `every` are then ignored); otherwise allocates and zeroes H, the sums, the
+ * range words, dr_b and 1 / dr_b, and the origin ring (slots x 3 planes of offsets[B] doubles), every size computed in
+ * size_t; calling it again reconfigures and zeroes.  A failed guard returns LJMD_ERR_INVALID_ARG and leaves the earlier
+ * configuration in place; a failed allocation LJMD_ERR_ALLOC with the feature off, the message naming the buffer and its
+ * byte count.  every > 0: ljmd_batch_steps takes the snapshots after steps every, 2 every, ... of each call; its nsteps
+ * must then be a multiple of every (LJMD_ERR_INVALID_ARG before anything is launched); with other accumulators' every
+ * set, a launch ends at the multiples of any of them, and the van Hove launch of a group is the last of a step.  r, ru,
+ * v, a, the sampled scalars and the other four observables stay bitwise what they are without the feature;
+ * ljmd_batch_profile_read counts the new launches and their time.  Off: no launch, no allocation, nothing else changes.
+ * accumulate: the resident ru is the next snapshot, stream-ordered (no host wait).  LJMD_ERR_STATE before configure,
+ * before ljmd_batch_set_state or on a poisoned handle.
+ * read / read_exact: wait for the device; hist[B][max_lag + 1][nbins + 1], r2[B][max_lag + 1], r4[B][max_lag + 1] (read)
+ * or words[B][2][max_lag + 1][3], S2 then S4 (read_exact), counts[max_lag + 1], the number of snapshots since configure /
+ * reset -- any pointer may be NULL; they clear nothing, and a poisoned handle may still be read.  While any replica's
+ * range word is set they fill the arrays all the same and then return LJMD_ERR_RANGE, the message naming the lowest such
+ * replica ("replica <b>"), until ljmd_batch_vanhove_reset; the handle is not poisoned and stepping goes on.
+ * reset: zeroes the histogram, sums, counts, snapshot numbering and range words.  read, read_exact and reset return
+ * LJMD_ERR_STATE before configure.
+ * ljmd_batch_set_state and ljmd_batch_prepare start a new trajectory: the stored origins are dropped and the numbering
+ * restarts at 0; histogram, sums and counts stay.  The other setters and the other observables' calls leave everything
+ * alone.  If a call that takes snapshots fails half-way (a poisoned handle), histogram, sums and counts are unspecified
+ * until ljmd_batch_vanhove_reset.
+ */
+#define LJMD_BATCH_VANHOVE_MAX_LAG 4096
+#define LJMD_BATCH_VANHOVE_MAX_ORIGINS 512
+#define LJMD_BATCH_VANHOVE_MAX_BINS 1024
+int ljmd_batch_vanhove_configure(ljmd_batch_t *h, int32_t max_lag, int32_t origin_stride, int32_t nbins,
+                                 const double *rmax /* [B] */, int32_t every);
+int ljmd_batch_vanhove_accumulate(ljmd_batch_t *h);
+int ljmd_batch_vanhove_read(ljmd_batch_t *h, uint64_t *hist /* [B][max_lag+1][nbins+1] */,
+                            double *r2 /* [B][max_lag+1] */, double *r4 /* [B][max_lag+1] */,
+                            int64_t *counts /* [max_lag+1] */, int64_t *n_snapshots);
+int ljmd_batch_vanhove_read_exact(ljmd_batch_t *h, uint64_t *hist, int64_t *words /* [B][2][max_lag+1][3]: S2 then S4 */,
+                                  int64_t *counts, int64_t *n_snapshots);
+int ljmd_batch_vanhove_reset(ljmd_batch_t *h);
 
 /*
  * Independent initial configurations on the device (ljmd_batch_prepare): per replica b, with n = n_b, L = L_b and k the

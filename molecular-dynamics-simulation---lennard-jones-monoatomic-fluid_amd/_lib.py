@@ -176,6 +176,11 @@ PROTOTYPES = {
     "ljmd_batch_heatflux_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
     "ljmd_batch_heatflux_read": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_int64_p]),
     "ljmd_batch_heatflux_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_vanhove_configure": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_double_p, C.c_int32]),
+    "ljmd_batch_vanhove_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_vanhove_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_double_p, c_double_p, c_int64_p, c_int64_p]),
+    "ljmd_batch_vanhove_read_exact": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p, c_int64_p, c_int64_p]),
+    "ljmd_batch_vanhove_reset": (C.c_int, [C.c_void_p]),
     "ljmd_batch_prepare": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
     "ljmd_tcf_from_exact": (C.c_int, [c_int64_p, C.c_int32, C.c_int64, c_double_p]),
 }
@@ -188,6 +193,9 @@ TCF_MAX_ORIGINS = 512
 VANHOVE_MAX_LAG = 4096
 VANHOVE_MAX_ORIGINS = 512
 VANHOVE_MAX_BINS = 4096
+BATCH_VANHOVE_MAX_LAG = 4096
+BATCH_VANHOVE_MAX_ORIGINS = 512
+BATCH_VANHOVE_MAX_BINS = 1024
 STRESS_MAX_SNAPSHOTS = 262144
 HEATFLUX_MAX_SNAPSHOTS = 262144
 BATCH_STRESS_MAX_SNAPSHOTS = 262144

@@ -230,3 +230,24 @@ def non_gaussian_parameter(r2, r4):
     out = np.zeros(np.broadcast(r2, r4).shape)
     np.divide(3.0 * r4, 5.0 * (r2 * r2), out=out, where=r2 != 0.0)
     return np.where(r2 != 0.0, out - 1.0, 0.0)
+
+
+def van_hove_self_ensemble(hist, counts, n: int, dr: float):
+    """hist [B, max_lag + 1, nbins + 1]: the histograms of a batch of B identical replicas (BatchEngine.vanhove_read),
+    counts [max_lag + 1] -> (r_centers[nbins], mean[max_lag + 1, nbins], stderr[max_lag + 1, nbins],
+    overflow[max_lag + 1]): per (lag, bin) the mean over the replicas of van_hove_self(hist[b], counts, n, dr) and its
+    standard error, the sample standard deviation (ddof = 1) over sqrt(B); with B = 1 the error is not defined (NaN).
+    overflow is the replica mean of the fraction beyond rmax.  The replicas are taken as independent runs of one state
+    point: the error falls as 1 / sqrt(B)."""
+    hist = np.asarray(hist)
+    if hist.ndim != 3 or hist.shape[0] < 1:
+        raise ValueError(f"van_hove_self_ensemble: hist must have shape (B, max_lag + 1, nbins + 1) with B >= 1, got "
+                         f"{hist.shape}")
+    B = hist.shape[0]
+    per = [van_hove_self(hist[b], counts, n, dr) for b in range(B)]
+    g = np.stack([p[1] for p in per])
+    overflow = np.stack([p[2] for p in per]).mean(axis=0)
+    mean = g.mean(axis=0)
+    if B < 2:
+        return per[0][0], mean, np.full_like(mean, np.nan), overflow
+    return per[0][0], mean, g.std(axis=0, ddof=1) / np.sqrt(B), overflow

@@ -4,7 +4,8 @@
 // loop and the combination of the per-replica step records, in the fp64 mode and in the reproducible mode (exact integer
 // records, a sticky range flag per replica: ljmd_batch_fixed.hip).  The accumulators the step loop serves are
 // ljmd_batch_rdf.cpp (g(r)), ljmd_batch_tcf.cpp (MSD / VACF) and, through the handle alone, ljmd_stress_batch.cpp (the
-// pressure tensor) and ljmd_heatflux_batch.cpp (the heat flux); ljmd_batch_host.h is what these files share.
+// pressure tensor), ljmd_heatflux_batch.cpp (the heat flux) and ljmd_vanhove_batch.cpp (the van Hove function);
+// ljmd_batch_host.h is what these files share.
 #include "ljmd_batch_host.h"
 
 using namespace ljmdb;
@@ -17,6 +18,7 @@ int ljmdb::enter(ljmd_batch *h, const char *who, unsigned need)
     if ((need & kNeedTcf) && h->tcf.max_lag == 0) return state("call ljmd_batch_tcf_configure first");
     if ((need & kNeedStress) && h->stress.max_snapshots == 0) return state("call ljmd_batch_stress_configure first");
     if ((need & kNeedHeatflux) && h->heatflux.max_snapshots == 0) return state("call ljmd_batch_heatflux_configure first");
+    if ((need & kNeedVanhove) && h->vanhove.max_lag == 0) return state("call ljmd_batch_vanhove_configure first");
     if ((need & kNeedState) && !h->have_state) return state("no state has been set");
     if ((need & kNeedAccel) && !h->have_accel)
         return state("no valid accelerations; call ljmd_batch_compute_forces or ljmd_batch_set_accel first");
@@ -383,6 +385,7 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
     tcf_release(h);
     if (h->stress.release) h->stress.release(h);
     if (h->heatflux.release) h->heatflux.release(h);
+    if (h->vanhove.release) h->vanhove.release(h);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);
@@ -435,6 +438,7 @@ int ljmd_batch_set_state(ljmd_batch_t *h, const double *rx, const double *ry, co
     h->have_state = true;
     h->have_accel = false;
     h->tcf.s = 0;                     // a new trajectory: no stored origin is live; the sums and counts stay
+    h->vanhove.s = 0;
     return LJMD_OK;
 }
 

@@ -1,7 +1,7 @@
 // ljmd_batch_host.h -- what the host files of the batch engine share (ljmd_batch.cpp: lifecycle, planning, step loop;
 // ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF; ljmd_batch_series.cpp: the one core of the series
 // observables, driven by the descriptors of ljmd_stress_batch.cpp: pressure tensor, and ljmd_heatflux_batch.cpp: heat
-// flux): the handle, the entry guard, the poison and allocation helpers, and the form in which the step loop sees an
+// flux; ljmd_vanhove_batch.cpp: van Hove): the handle, the entry guard, the poison and allocation helpers, and the form in which the step loop sees an
 // accumulator.  Host code only; the kernels' side is ljmd_batch.h.
 #ifndef LJMD_BATCH_HOST_H
 #define LJMD_BATCH_HOST_H
@@ -87,6 +87,24 @@ struct BatchSeries {
 using BatchStress = BatchSeries;
 using BatchHeatflux = BatchSeries;
 
+// van Hove self-correlation (ljmd_vanhove_batch.cpp): off while max_lag == 0, and every is 0 then.  Numbering, ring
+// slots and counts are BatchTcf's; the ring is its own and holds ru alone.  ljmd_vanhove_batch.cpp is not linked into
+// every program that links ljmd_batch.cpp either: ljmd_batch_vanhove_configure fills acc and release, and
+// default-constructed means nothing is called
+struct BatchVanhove {
+    int32_t max_lag = 0, stride = 1, every = 0, slots = 0, nbins = 0;
+    int64_t s = 0;                    // number of the next snapshot of this trajectory (0 after ljmd_batch_set_state)
+    int64_t snapshots = 0;            // snapshots since configure / reset, over all trajectories
+    std::vector<int64_t> counts;      // [max_lag + 1] origins that contributed to each lag: the same for all replicas
+    unsigned long long *d_hist = nullptr;   // [B][max_lag + 1][nbins + 1]
+    uint64_t *d_sums = nullptr;       // [B][2][max_lag + 1][3] signed 192-bit: S2 then S4
+    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_vanhove_reset
+    double *d_dr = nullptr;           // [2][B]: dr_b = rmax[b] / nbins, then 1 / dr_b
+    double *d_ring = nullptr;         // [slots][3][offsets[B]]: ru of the stored origins
+    BatchAccumulator acc;
+    void (*release)(ljmd_batch *h) = nullptr;
+};
+
 }  // namespace ljmdb
 
 struct ljmd_batch {
@@ -117,6 +135,7 @@ struct ljmd_batch {
     ljmdb::BatchTcf tcf;
     ljmdb::BatchStress stress;
     ljmdb::BatchHeatflux heatflux;
+    ljmdb::BatchVanhove vanhove;
     std::string err;
 };
 
@@ -128,10 +147,10 @@ inline bool reproducible(const ljmd_batch *h) { return h->mode == LJMD_PRECISION
 inline double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
 
 // What an entry point requires before it starts, checked in this order after the NULL handle: configured g(r),
-// configured MSD / VACF, configured pressure tensor, configured heat flux, a state, valid accelerations, no poison
-// (LJMD_ERR_STATE each); kNeedDevice: the handle's device is then made current (ljmd_batch.cpp)
+// configured MSD / VACF, configured pressure tensor, configured heat flux, configured van Hove, a state, valid
+// accelerations, no poison (LJMD_ERR_STATE each); kNeedDevice: the handle's device is then made current (ljmd_batch.cpp)
 enum BatchNeed : unsigned { kNeedRdf = 1, kNeedTcf = 2, kNeedState = 4, kNeedAccel = 8, kNeedSound = 16, kNeedDevice = 32,
-                         kNeedStress = 64, kNeedHeatflux = 128 };
+                         kNeedStress = 64, kNeedHeatflux = 128, kNeedVanhove = 256 };
 int enter(ljmd_batch *h, const char *who, unsigned need);
 
 // fails the call as fail() does and poisons the handle: LJMD_ERR_STATE from the guarded calls until ljmd_batch_set_state
@@ -168,13 +187,14 @@ int host_alloc(const ljmd_batch *h, const char *who, F &&grow)
 
 BatchAccumulator rdf_accumulator(const ljmd_batch *h);    // ljmd_batch_rdf.cpp
 BatchAccumulator tcf_accumulator(const ljmd_batch *h);    // ljmd_batch_tcf.cpp
-using BatchAccumulators = std::array<BatchAccumulator, 4>;
-inline BatchAccumulators accumulators(const ljmd_batch *h)
+using BatchAccumulators = std::array<BatchAccumulator, 5>;
+inline BatchAccumulators accumulators(const ljmd_batch *h)     // van Hove last: the earlier launch sequences are unchanged
 {
-    BatchAccumulator stress = h->stress.acc, heatflux = h->heatflux.acc;
+    BatchAccumulator stress = h->stress.acc, heatflux = h->heatflux.acc, vanhove = h->vanhove.acc;
     stress.every = h->stress.every;
     heatflux.every = h->heatflux.every;
-    return {rdf_accumulator(h), tcf_accumulator(h), stress, heatflux};
+    vanhove.every = h->vanhove.every;
+    return {rdf_accumulator(h), tcf_accumulator(h), stress, heatflux, vanhove};
 }
 
 // one snapshot of the resident state outside ljmd_batch_steps, on the handle's stream (ljmd_batch_*_accumulate)

@@ -102,6 +102,7 @@ extern "C" int ljmd_batch_prepare(ljmd_batch_t *h, const int32_t *seeds, const d
     h->have_state = true;
     h->have_accel = false;
     h->tcf.s = 0;                            // a new trajectory, as after ljmd_batch_set_state
+    h->vanhove.s = 0;
 
     // d: the energies of this state in the handle's mode, the scale factors in IEEE doubles on the host
     LJMD_TRY(ljmd_batch_compute_forces(h, epot.data(), nullptr, nullptr));

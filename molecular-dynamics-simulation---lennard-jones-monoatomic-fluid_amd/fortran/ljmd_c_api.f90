@@ -41,6 +41,8 @@ module ljmd_c_api
   public :: ljmd_batch_stress_reset
   public :: ljmd_batch_heatflux_configure, ljmd_batch_heatflux_accumulate, ljmd_batch_heatflux_read
   public :: ljmd_batch_heatflux_read_exact, ljmd_batch_heatflux_reset
+  public :: ljmd_batch_vanhove_configure, ljmd_batch_vanhove_accumulate, ljmd_batch_vanhove_read
+  public :: ljmd_batch_vanhove_read_exact, ljmd_batch_vanhove_reset
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -53,6 +55,9 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_VANHOVE_MAX_LAG = 4096
   integer(c_int32_t), parameter, public :: LJMD_VANHOVE_MAX_ORIGINS = 512
   integer(c_int32_t), parameter, public :: LJMD_VANHOVE_MAX_BINS = 4096
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_VANHOVE_MAX_LAG = 4096
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_VANHOVE_MAX_ORIGINS = 512
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_VANHOVE_MAX_BINS = 1024
   integer(c_int32_t), parameter, public :: LJMD_STRESS_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_STRESS_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
@@ -657,6 +662,47 @@ module ljmd_c_api
     end function
 
     function ljmd_batch_tcf_reset(handle) bind(C, name="ljmd_batch_tcf_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    ! van Hove self-correlation of every replica of a batch handle (ljmd.h: ljmd_batch_vanhove_*); rmax = c_loc of B
+    ! doubles; hist = c_loc of [nbins + 1, max_lag + 1, B] 64-bit counts in Fortran order (the overflow column last), r2,
+    ! r4 [max_lag + 1, B], counts [max_lag + 1], words [3, max_lag + 1, 2, B]; c_null_ptr skips an output
+    function ljmd_batch_vanhove_configure(handle, max_lag, origin_stride, nbins, rmax, every) &
+        bind(C, name="ljmd_batch_vanhove_configure") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: max_lag, origin_stride, nbins
+      type(c_ptr), value :: rmax
+      integer(c_int32_t), value :: every
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_vanhove_accumulate(handle) bind(C, name="ljmd_batch_vanhove_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_vanhove_read(handle, hist, r2, r4, counts, n_snapshots) bind(C, name="ljmd_batch_vanhove_read") &
+        result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, hist, r2, r4, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_vanhove_read_exact(handle, hist, words, counts, n_snapshots) &
+        bind(C, name="ljmd_batch_vanhove_read_exact") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, hist, words, counts
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_vanhove_reset(handle) bind(C, name="ljmd_batch_vanhove_reset") result(status)
       import :: c_int, c_ptr
       type(c_ptr), value :: handle
       integer(c_int) :: status

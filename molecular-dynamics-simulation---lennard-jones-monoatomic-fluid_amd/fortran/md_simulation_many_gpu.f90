@@ -38,6 +38,11 @@
 ! J_z and the nine parts, and with LJMD_HEATFLUX_MAX_LAG > 0 outputs/run_NNNN/heat_flux_acf_gpu.dat the autocorrelation
 ! and running Green-Kubo thermal conductivity of the run -- the files and formats of md_simulation_gpu; every other file
 ! stays byte-identical),
+! LJMD_VANHOVE_MAX_LAG (default 0 = off; > 0: the van Hove self-correlation of every run on the device,
+! ljmd_batch_vanhove_*, over the sampling instants that write an rva.dat record -- those of MSD / VACF -- every
+! LJMD_VANHOVE_ORIGIN_STRIDE-th of them (default 1) an origin, LJMD_VANHOVE_BINS bins (default 128) up to
+! LJMD_VANHOVE_RMAX (default half of each run's box); outputs/run_NNNN/van_hove_gpu.dat is the file of md_simulation_gpu
+! (md_run_outputs: write_van_hove_file); every other file stays byte-identical),
 ! LJMD_SEED_BASE (unset: the rv_init.dat files above are read; s >= 1: NO rv_init.dat is read -- run i is prepared on the
 ! device, ljmd_batch_prepare, with seed s + i - 1: the reference's FCC lattice, its generator's velocities, centre of
 ! mass removed, scaled to the target_total_energy of the run's own or the shared input file, then that file's
@@ -56,7 +61,7 @@ program md_simulation_many_gpu
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
   use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
-                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file
+                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file
   implicit none
 
   character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
@@ -102,6 +107,13 @@ program md_simulation_many_gpu
   real(c_double), allocatable, target :: heatflux_j(:, :, :), heatflux_parts(:, :, :, :)   ! [3, n_runs, snapshots], [3, 3, ...]
   real(c_double), allocatable :: heatflux_times(:, :)           ! [snapshots, n_runs]
   integer(c_int64_t) :: heatflux_snapshots
+  integer :: vh_max_lag, vh_stride, vh_bins
+  logical :: vh_rmax_given
+  real(kind=dp_kind) :: vh_rmax_env
+  real(c_double), allocatable, target :: vh_rmax(:)                         ! [n_runs]
+  real(c_double), allocatable, target :: vh_r2(:, :), vh_r4(:, :)           ! [vh_max_lag + 1, n_runs]
+  integer(c_int64_t), allocatable, target :: vh_counts(:), vh_hist(:, :, :) ! [vh_max_lag + 1], [vh_bins + 1, vh_max_lag + 1, n_runs]
+  integer(c_int64_t) :: vh_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -144,6 +156,25 @@ program md_simulation_many_gpu
   call get_environment_variable('LJMD_HEATFLUX_MAX_LAG', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) heatflux_max_lag
   if (heatflux_max_lag < 0) stop 'md_simulation_many: LJMD_HEATFLUX_MAX_LAG must be >= 0.'
+  vh_max_lag = 0
+  call get_environment_variable('LJMD_VANHOVE_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_max_lag
+  if (vh_max_lag < 0) stop 'md_simulation_many: LJMD_VANHOVE_MAX_LAG must be >= 0.'
+  vh_stride = 1
+  call get_environment_variable('LJMD_VANHOVE_ORIGIN_STRIDE', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_stride
+  if (vh_stride < 1) stop 'md_simulation_many: LJMD_VANHOVE_ORIGIN_STRIDE must be >= 1.'
+  vh_bins = 128
+  call get_environment_variable('LJMD_VANHOVE_BINS', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_bins
+  if (vh_bins < 1) stop 'md_simulation_many: LJMD_VANHOVE_BINS must be >= 1.'
+  vh_rmax_given = .false.
+  vh_rmax_env = 0.d0
+  call get_environment_variable('LJMD_VANHOVE_RMAX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) then
+    read(env, *) vh_rmax_env
+    vh_rmax_given = .true.
+  end if
 
   seed_base = 0
   call get_environment_variable('LJMD_SEED_BASE', env, status=ios)
@@ -208,6 +239,15 @@ program md_simulation_many_gpu
   if (tcf_max_lag > 0) call ljmd_batch_check(ljmd_batch_tcf_configure(batch, int(tcf_max_lag, c_int32_t), &
                                                                       int(tcf_stride, c_int32_t), 0_c_int32_t), batch, &
                                              'ljmd_batch_tcf_configure')
+  if (vh_max_lag > 0) then
+    allocate(vh_rmax(n_runs))
+    do i = 1, n_runs
+      vh_rmax(i) = merge(vh_rmax_env, 0.5d0 * rparams(i)%box_length, vh_rmax_given)
+    end do
+    call ljmd_batch_check(ljmd_batch_vanhove_configure(batch, int(vh_max_lag, c_int32_t), int(vh_stride, c_int32_t), &
+                                                       int(vh_bins, c_int32_t), c_loc(vh_rmax), 0_c_int32_t), batch, &
+                          'ljmd_batch_vanhove_configure')
+  end if
   ! t = 0 forces and energies of every run (:236-243)
   call ljmd_batch_check(ljmd_batch_compute_forces(batch, c_loc(s_epot), c_loc(s_depot), c_loc(s_ddepot)), batch, &
                         'ljmd_batch_compute_forces')
@@ -263,6 +303,7 @@ program md_simulation_many_gpu
     num_samples = num_samples + 1
     if (rdf_bins > 0) call ljmd_batch_check(ljmd_batch_rdf_accumulate(batch), batch, 'ljmd_batch_rdf_accumulate')
     if (tcf_max_lag > 0) call ljmd_batch_check(ljmd_batch_tcf_accumulate(batch), batch, 'ljmd_batch_tcf_accumulate')
+    if (vh_max_lag > 0) call ljmd_batch_check(ljmd_batch_vanhove_accumulate(batch), batch, 'ljmd_batch_vanhove_accumulate')
     if (stress_on) then
       call ljmd_batch_check(ljmd_batch_stress_accumulate(batch), batch, 'ljmd_batch_stress_accumulate')
       stress_times(num_samples, :) = time_run
@@ -311,6 +352,12 @@ program md_simulation_many_gpu
                           batch, 'ljmd_batch_heatflux_read')
     if (heatflux_snapshots /= num_samples) stop 'md_simulation_many: the heat flux series and the samples disagree.'
   end if
+  if (vh_max_lag > 0) then
+    allocate(vh_r2(0:vh_max_lag, n_runs), vh_r4(0:vh_max_lag, n_runs), vh_counts(0:vh_max_lag), &
+             vh_hist(0:vh_bins, 0:vh_max_lag, n_runs))
+    call ljmd_batch_check(ljmd_batch_vanhove_read(batch, c_loc(vh_hist), c_loc(vh_r2), c_loc(vh_r4), c_loc(vh_counts), &
+                                                  vh_snapshots), batch, 'ljmd_batch_vanhove_read')
+  end if
   call ljmd_batch_destroy(batch)
   do i = 1, n_runs
     close(iu_out(i))
@@ -346,6 +393,12 @@ program md_simulation_many_gpu
   if (heatflux_on) then
     do i = 1, n_runs
       call write_heat_flux(i)
+    end do
+  end if
+  if (vh_max_lag > 0) then
+    do i = 1, n_runs
+      call write_van_hove_file(trim(run_dir(i)) // '/van_hove_gpu.dat', rparams(i)%n, vh_max_lag, vh_bins, vh_rmax(i), &
+                               output_interval, rparams(i)%dt, vh_counts, vh_r2(:, i), vh_r4(:, i), vh_hist(:, :, i))
     end do
   end if
   if (any_own) then

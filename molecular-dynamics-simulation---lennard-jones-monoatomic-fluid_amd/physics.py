@@ -1001,6 +1001,93 @@ class BatchEngine:
     def heatflux_reset(self) -> None:
         self._ck(self._lib.ljmd_batch_heatflux_reset(self._h))
 
+    # -- van Hove self-correlation on the device (include/ljmd.h: ljmd_batch_vanhove_*) ----
+    def vanhove_configure(self, max_lag: int, origin_stride: int = 1, nbins: int = 128, rmax=None, every: int = 0) -> None:
+        """ljmd_batch_vanhove_configure: G_s(r, tau) of every replica up to lag max_lag (in snapshots), every
+        origin_stride-th snapshot an origin, nbins bins up to rmax (a scalar, B values, or None = 0.5 L of each replica)
+        and an overflow column; every > 0: steps() takes the snapshots after steps every, 2 every, ... by itself.
+        max_lag = 0 switches the feature off.  Zeroes everything."""
+        for name, val in (("max_lag", max_lag), ("origin_stride", origin_stride), ("nbins", nbins), ("every", every)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise TypeError(f"vanhove_configure: {name} must be an integer, got {val!r}")
+            if not -2 ** 31 <= int(val) <= 2 ** 31 - 1:
+                raise ValueError(f"vanhove_configure: {name} must lie within the int32 range")
+        B = self.n_replicas
+        if rmax is None:
+            ps = self.params if isinstance(self.params, (list, tuple)) else [self.params] * B
+            arr = np.array([0.5 * p.box_length for p in ps], dtype=np.float64)
+        else:
+            r = np.asarray(rmax)
+            if r.dtype == np.bool_ or not (np.issubdtype(r.dtype, np.floating) or np.issubdtype(r.dtype, np.integer)):
+                raise TypeError(f"vanhove_configure: rmax must be real numbers, got dtype {r.dtype}")
+            if r.shape not in ((), (B,)):
+                raise ValueError(f"vanhove_configure: rmax must be a scalar or have shape ({B},), got {r.shape}")
+            arr = np.ascontiguousarray(np.broadcast_to(r, (B,)), dtype=np.float64)
+        self._ck(self._lib.ljmd_batch_vanhove_configure(self._h, int(max_lag), int(origin_stride), int(nbins), _ptr(arr),
+                                                        int(every)))
+        self._vanhove_shape = (int(max_lag), int(nbins))
+
+    def vanhove_accumulate(self) -> None:
+        """takes every replica's resident ru as the next snapshot (no host wait)"""
+        self._ck(self._lib.ljmd_batch_vanhove_accumulate(self._h))
+
+    def _vanhove_rows(self, who: str):
+        max_lag, nbins = getattr(self, "_vanhove_shape", (0, 0))
+        if max_lag < 1:
+            raise ValueError(f"{who}: call vanhove_configure with max_lag >= 1 first")
+        return max_lag + 1, nbins + 1
+
+    def _vanhove_ck(self, status: int, result):
+        """as _ck; a range error (LJMD_ERR_RANGE) carries the arrays, which the library has filled, in its `result`"""
+        try:
+            self._ck(status)
+        except _lib.LjmdError as e:
+            if e.code == _lib.LJMD_ERR_RANGE:
+                e.result = result()
+            raise
+        return result()
+
+    def vanhove_read(self):
+        """-> (hist[B, max_lag + 1, nbins + 1] uint64 with the overflow column last, r2[B, max_lag + 1],
+        r4[B, max_lag + 1], counts[max_lag + 1] int64, n_snapshots); nothing is cleared"""
+        rows, cols = self._vanhove_rows("vanhove_read")
+        B = self.n_replicas
+        hist = np.empty((B, rows, cols), dtype=np.uint64)
+        r2 = np.empty((B, rows), dtype=np.float64)
+        r4 = np.empty((B, rows), dtype=np.float64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        st = self._lib.ljmd_batch_vanhove_read(self._h, hist.ctypes.data_as(C.POINTER(C.c_uint64)), _ptr(r2), _ptr(r4),
+                                               counts.ctypes.data_as(_lib.c_int64_p), C.byref(snaps))
+        return self._vanhove_ck(st, lambda: (hist, r2, r4, counts, snaps.value))
+
+    def vanhove_read_exact(self, raw: bool = False):
+        """-> (hist, sums, counts, n_snapshots): the counts and the exact integer sums of Q(t) = RNE(t 2^64),
+        sums[b, kind, lag] with kind 0 = r^2, 1 = r^4, as Python ints in an object array -- or, raw=True, the library's
+        int64 words [B, 2, max_lag + 1, 3] (three little-endian limbs of a signed 192-bit integer)"""
+        rows, cols = self._vanhove_rows("vanhove_read_exact")
+        B = self.n_replicas
+        hist = np.empty((B, rows, cols), dtype=np.uint64)
+        words = np.empty((B, 2, rows, 3), dtype=np.int64)
+        counts = np.empty(rows, dtype=np.int64)
+        snaps = C.c_int64()
+        st = self._lib.ljmd_batch_vanhove_read_exact(self._h, hist.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                     words.ctypes.data_as(_lib.c_int64_p),
+                                                     counts.ctypes.data_as(_lib.c_int64_p), C.byref(snaps))
+
+        def result():
+            if raw:
+                return hist, words, counts, snaps.value
+            u = words.view(np.uint64)
+            sums = np.empty(words.shape[:3], dtype=object)
+            for idx in np.ndindex(*sums.shape):
+                sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+            return hist, sums, counts, snaps.value
+        return self._vanhove_ck(st, result)
+
+    def vanhove_reset(self) -> None:
+        self._ck(self._lib.ljmd_batch_vanhove_reset(self._h))
+
     @staticmethod
     def per_replica(params_list, device: int = 0,
                     precision_mode: int = _lib.PRECISION_FP64) -> "PerReplicaBatchEngine":
