@@ -114,19 +114,17 @@ struct BatchRdfArgs {
 };
 hipError_t launch_batch_rdf(const BatchRdfArgs &a, int n_max, int n_blocks, hipStream_t s);
 
-// MSD / VACF accumulation (ljmd_batch_tcf.hip): one snapshot -- every replica's resident ru and v -- against the live
-// origins of the ring, the exact integer sums of Q(term) added to the replica's rows of sums; the snapshot is then stored
-// as an origin when its number is a multiple of the origin stride.  Same launch geometry as launch_batch.  The host
-// derives the live origins from the snapshot number s: origin e = 0 .. n_live - 1 is the snapshot t0 = t0_first +
-// e * stride, at lag s - t0 = lag_first - e * stride (1 <= lag <= max_lag), in ring slot (slot_first + e) % slots.  When
-// the newest origin is at lag 1 its lag-0 terms are added too.
-constexpr int kBatchTcfMaxLag = 4096;                  // LJMD_BATCH_TCF_MAX_LAG
-constexpr int kBatchTcfMaxOrigins = 512;               // LJMD_BATCH_TCF_MAX_ORIGINS: ring slots = max_lag / stride + 1
-struct BatchTcfArgs {
+// The time-origin observables, MSD / VACF (ljmd_batch_tcf.hip) and van Hove (ljmd_batch_vanhove.h): one snapshot -- every
+// replica's resident state -- against the live origins of the ring, the exact integer sums of Q(term) added to the
+// replica's rows of sums; the snapshot is then stored as an origin when its number is a multiple of the origin stride.
+// Same launch geometry as launch_batch.  The host derives the live origins from the snapshot number s: origin e = 0 ..
+// n_live - 1 is the snapshot t0 = t0_first + e * stride, at lag s - t0 = lag_first - e * stride (1 <= lag <= max_lag), in
+// ring slot (slot_first + e) % slots; with the newest origin at lag 1 its lag-0 terms are added too.
+struct BatchOriginArgs {
     const double *state;    // [12][plane]: ru = planes 3..5, v = planes 6..8
-    double *ring;           // [slots][6][plane]: ru (3 planes) and v (3 planes) of the stored origins
-    uint64_t *sums;         // [B][2][max_lag + 1][3] signed 192-bit: kind 0 = MSD, 1 = VACF; replica b's rows are
-                            // written by its workgroup alone
+    double *ring;           // [slots][C][plane]: the C components of the stored origins -- 6: ru and v, 3: ru alone
+    uint64_t *sums;         // [B][2][max_lag + 1][3] signed 192-bit, two kinds; replica b's rows are written by its
+                            // workgroup alone
     int32_t *range;         // [B] sticky: set to 1 when a term of replica b was out of range
     const BatchReplica *rep;
     size_t plane;
@@ -135,6 +133,20 @@ struct BatchTcfArgs {
     int n_live, lag_first, slot_first;
     int store_slot;         // ring slot that takes this snapshot, or -1: not an origin
 };
+
+// the checks a launch makes of its window, against the observable's limits
+inline bool batch_origin_window_ok(const BatchOriginArgs &a, int max_lag, int max_origins)
+{
+    if (a.max_lag < 1 || a.max_lag > max_lag || a.stride < 1 || a.slots < 1 || a.slots > max_origins || a.n_live < 0 ||
+        a.n_live > a.slots || a.slot_first < 0 || a.slot_first >= a.slots || a.store_slot >= a.slots)
+        return false;
+    return a.n_live == 0 || (a.lag_first <= a.max_lag && a.lag_first - (a.n_live - 1) * a.stride >= 1);
+}
+
+// MSD / VACF: the ring holds ru and v, kind 0 = MSD, 1 = VACF
+constexpr int kBatchTcfMaxLag = 4096;                  // LJMD_BATCH_TCF_MAX_LAG
+constexpr int kBatchTcfMaxOrigins = 512;               // LJMD_BATCH_TCF_MAX_ORIGINS: ring slots = max_lag / stride + 1
+using BatchTcfArgs = BatchOriginArgs;
 hipError_t launch_batch_tcf(const BatchTcfArgs &a, int n_max, int n_blocks, hipStream_t s);
 
 // A series of snapshots of exact integer sums -- the pressure tensor (ljmd_batch_stress.h) and the heat flux

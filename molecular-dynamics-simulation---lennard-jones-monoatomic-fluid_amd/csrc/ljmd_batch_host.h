@@ -1,8 +1,9 @@
 // ljmd_batch_host.h -- what the host files of the batch engine share (ljmd_batch.cpp: lifecycle, planning, step loop;
-// ljmd_batch_rdf.cpp: g(r); ljmd_batch_tcf.cpp: MSD / VACF; ljmd_batch_series.cpp: the one core of the series
-// observables, driven by the descriptors of ljmd_stress_batch.cpp: pressure tensor, and ljmd_heatflux_batch.cpp: heat
-// flux; ljmd_vanhove_batch.cpp: van Hove): the handle, the entry guard, the poison and allocation helpers, and the form in which the step loop sees an
-// accumulator.  Host code only; the kernels' side is ljmd_batch.h.
+// ljmd_batch_rdf.cpp: g(r); ljmd_batch_origins.cpp: the one core of the time-origin observables, driven by the
+// descriptors of ljmd_batch_tcf.cpp: MSD / VACF, and ljmd_vanhove_batch.cpp: van Hove; ljmd_batch_series.cpp: the one
+// core of the series observables, driven by the descriptors of ljmd_stress_batch.cpp: pressure tensor, and
+// ljmd_heatflux_batch.cpp: heat flux): the handle, the entry guard, the poison and allocation helpers, and the form in
+// which the step loop sees an accumulator.  Host code only; the kernels' side is ljmd_batch.h.
 #ifndef LJMD_BATCH_HOST_H
 #define LJMD_BATCH_HOST_H
 
@@ -47,17 +48,6 @@ struct BatchRdf {
     BatchRdfReplica *d_table = nullptr;     // [B], replica order
 };
 
-// MSD / VACF accumulation (ljmd_batch_tcf.cpp): off while max_lag == 0, and every is 0 then
-struct BatchTcf {
-    int32_t max_lag = 0, stride = 1, every = 0, slots = 0;
-    int64_t s = 0;                    // number of the next snapshot of this trajectory (0 after ljmd_batch_set_state)
-    int64_t snapshots = 0;            // snapshots since configure / reset, over all trajectories
-    std::vector<int64_t> counts;      // [max_lag + 1] origins that contributed to each lag: the same for all replicas
-    uint64_t *d_sums = nullptr;       // [B][2][max_lag + 1][3] signed 192-bit
-    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_tcf_reset
-    double *d_ring = nullptr;         // [slots][6][offsets[B]]: ru and v of the stored origins
-};
-
 // An accumulator as the step loop sees it (run_groups, ljmd_batch_steps): a launch ends at the steps every, 2 every, ...
 // of the call, the group's enqueue follows it on the same stream, and ran() does the host's share after the whole call.
 struct BatchAccumulator {
@@ -87,23 +77,25 @@ struct BatchSeries {
 using BatchStress = BatchSeries;
 using BatchHeatflux = BatchSeries;
 
-// van Hove self-correlation (ljmd_vanhove_batch.cpp): off while max_lag == 0, and every is 0 then.  Numbering, ring
-// slots and counts are BatchTcf's; the ring is its own and holds ru alone.  ljmd_vanhove_batch.cpp is not linked into
-// every program that links ljmd_batch.cpp either: ljmd_batch_vanhove_configure fills acc and release, and
-// default-constructed means nothing is called
-struct BatchVanhove {
+// A time-origin observable -- MSD / VACF (ljmd_batch_tcf.cpp) and van Hove (ljmd_vanhove_batch.cpp), both through
+// ljmd_batch_origins.cpp: off while max_lag == 0, and every is 0 then.  Without a histogram (MSD / VACF) nbins stays 0 and
+// d_hist and d_dr NULL.  acc and release (default-constructed: nothing is called) are how the step loop and
+// ljmd_batch_destroy reach van Hove, whose file is not linked everywhere; MSD / VACF: tcf_accumulator, tcf_release.
+struct BatchOrigins {
     int32_t max_lag = 0, stride = 1, every = 0, slots = 0, nbins = 0;
     int64_t s = 0;                    // number of the next snapshot of this trajectory (0 after ljmd_batch_set_state)
     int64_t snapshots = 0;            // snapshots since configure / reset, over all trajectories
     std::vector<int64_t> counts;      // [max_lag + 1] origins that contributed to each lag: the same for all replicas
     unsigned long long *d_hist = nullptr;   // [B][max_lag + 1][nbins + 1]
-    uint64_t *d_sums = nullptr;       // [B][2][max_lag + 1][3] signed 192-bit: S2 then S4
-    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_vanhove_reset
+    uint64_t *d_sums = nullptr;       // [B][2][max_lag + 1][3] signed 192-bit: MSD then VACF, or S2 then S4
+    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_tcf_reset / ljmd_batch_vanhove_reset
     double *d_dr = nullptr;           // [2][B]: dr_b = rmax[b] / nbins, then 1 / dr_b
-    double *d_ring = nullptr;         // [slots][3][offsets[B]]: ru of the stored origins
+    double *d_ring = nullptr;         // [slots][6 or 3][offsets[B]]: the stored origins
     BatchAccumulator acc;
     void (*release)(ljmd_batch *h) = nullptr;
 };
+using BatchTcf = BatchOrigins;
+using BatchVanhove = BatchOrigins;
 
 }  // namespace ljmdb
 
@@ -231,6 +223,43 @@ int series_fetch(ljmd_batch *h, const BatchSeriesDesc &d, int64_t *words, int64_
 int series_read_words(ljmd_batch *h, const BatchSeriesDesc &d, bool want, std::vector<int64_t> *w, int64_t *n_snapshots,
                       const char *who);
 int series_reset(ljmd_batch *h, const BatchSeriesDesc &d, const char *who);
+
+
+// What ljmd_batch_origins.cpp is driven by: one constant per time-origin observable.  The core references no launcher
+// itself, so it links into every program that links ljmd_batch*.cpp.  acc and release pass this descriptor on to
+// origins_enqueue / origins_ran / origins_release; configure leaves them in the handle's BatchOrigins.
+struct BatchOriginDesc {
+    BatchOrigins ljmd_batch::*state;  // &ljmd_batch::tcf: the observable's state of a handle
+    unsigned need;                    // kNeedTcf
+    int components;                   // of a ring slot: 6 (ru and v) or 3 (ru alone)
+    int max_lag, max_origins, max_bins;   // LJMD_BATCH_*_MAX_LAG, _MAX_ORIGINS, _MAX_BINS; max_bins == 0: no histogram
+    const char *phrase;               // "MSD / VACF": "(0 switches MSD / VACF off)"
+    const char *limits;               // "TCF": "exceeds LJMD_BATCH_TCF_MAX_ORIGINS"
+    const char *range;                // what a set range word means: "replica 1: <range>; the flag stays until ..."
+    bool range_first;                 // a set range word fails a read before anything is written, not after everything is
+    BatchAccumulator acc;             // name "MSD / VACF", tag "tcf", enqueue, ran; every = 0
+    void (*release)(ljmd_batch *h);
+    // the observable's own launcher on the common block `a` of the state `q`
+    hipError_t (*launch)(const ljmd_batch *h, const BatchOrigins &q, const BatchOriginArgs &a, int n_max, int n_blocks,
+                         hipStream_t s);
+};
+int origins_enqueue(ljmd_batch *h, const BatchOriginDesc &d, const BatchGroup &g, hipStream_t s, int k, int32_t *count,
+                    const char *who);
+void origins_ran(ljmd_batch *h, const BatchOriginDesc &d, int snapshots);
+void origins_release(ljmd_batch *h, const BatchOriginDesc &d);
+// ljmd_batch_<tag>_configure in two parts (`who` = the public name, h may be NULL): the entry and the shared guards; then,
+// behind the observable's own guards, the device, the release and the buffers.  dr: the [2][B] bin widths with a histogram
+int origins_configure_guards(ljmd_batch *h, const BatchOriginDesc &d, int32_t max_lag, int32_t origin_stride, int32_t every,
+                             const char *who);
+int origins_configure(ljmd_batch *h, const BatchOriginDesc &d, int32_t max_lag, int32_t origin_stride, int32_t every,
+                      int32_t nbins, const double *dr, const char *who);
+// the bodies of ljmd_batch_<tag>_accumulate / _read / _read_exact / _reset; hist is NULL without a histogram
+int origins_accumulate(ljmd_batch *h, const BatchOriginDesc &d, const char *who);
+int origins_read(ljmd_batch *h, const BatchOriginDesc &d, uint64_t *hist, double *kind0, double *kind1, int64_t *counts,
+                 int64_t *n_snapshots, const char *who);
+int origins_read_exact(ljmd_batch *h, const BatchOriginDesc &d, uint64_t *hist, int64_t *words, int64_t *counts,
+                       int64_t *n_snapshots, const char *who);
+int origins_reset(ljmd_batch *h, const BatchOriginDesc &d, const char *who);
 
 }  // namespace ljmdb
 #endif

@@ -19,92 +19,55 @@
 // 192-bit sums with plain loads, add192 and stores: it is the rows' only writer, and launches on one stream follow
 // one another.  No global atomics, no floating-point atomics.  LDS: 32 bytes per live origin, one entry more for the
 // lag-0 terms: at most 513 * 32 = 16416 bytes.
-#include "ljmd_batch.h"
-#include "ljmd_internal.h"
+// Frame, current snapshot, ring walk, store of the snapshot and the closing addition into the rows are shared with
+// batch_vanhove_kernel (ljmd_batch_origins_dev.h, BatchOriginArgs); tcf_origin and the one-barrier loop are this kernel's.
+#include "ljmd_batch_origins_dev.h"
 #include "ljmd_tcf_arith.h"
 
 namespace ljmdb {
 namespace {
 
-using ljmdk::add192;
 using ljmdk::tcf_origin;
 
 template <int NMAX, int K>
 __global__ __launch_bounds__(kBatchMaxThreads) void batch_tcf_kernel(BatchTcfArgs a)
 {
     extern __shared__ unsigned long long acc[];     // [n_live (+ 1)][2 kinds][2 words]
-    const BatchReplica &rp = a.rep[a.g0 + blockIdx.x];
-    const int n = rp.n, T = rp.threads, tid = threadIdx.x;
-    const size_t plane = a.plane, base = rp.off;
-    const int n_live = a.n_live;
-    const bool lag0 = n_live > 0 && a.lag_first - (n_live - 1) * a.stride == 1;   // the newest origin is at lag 1
-    const int n_ent = n_live + (lag0 ? 1 : 0);
-
-    for (int k = tid; k < 4 * n_ent; k += blockDim.x) acc[k] = 0ull;
+    const BatchOriginFrame f = batch_origin_frame(a, acc);
+    const int n = f.n, T = f.T, tid = threadIdx.x;
+    const size_t plane = a.plane;
     __syncthreads();
 
     bool bad = false;
     if (tid < T) {     // wave-uniform (T is a multiple of 64); the waves from T on own nothing
         const int lane = tid & 63;
         double cur[K][6];
+        #pragma unroll
+        for (int k = 0; k < K; ++k)
 #pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int i = tid + k * T;
-#pragma unroll
-            for (int c = 0; c < 6; ++c) cur[k][c] = i < n ? a.state[(size_t)(3 + c) * plane + base + i] : 0.0;
-        }
+            for (int c = 0; c < 6; ++c) cur[k][c] = batch_origin_current(a, f, true, k, c);
         int slot = a.slot_first;
 #pragma unroll 1
-        for (int e = 0; e < n_live; ++e) {
-            const double *const o = a.ring + (size_t)slot * 6 * plane + base;
-            slot = slot + 1 == a.slots ? 0 : slot + 1;
+        for (int e = 0; e < f.n_live; ++e) {
+            const double *const o = batch_origin_next<6>(a, f, slot);
             const auto org = [=](int k, int c) {
                 const int i = tid + k * T;
                 return i < n ? o[(size_t)c * plane + i] : 0.0;
             };
-            tcf_origin(cur, org, lag0 && e == n_live - 1, lane, acc + 4 * e, acc + 4 * n_live, bad);
+            tcf_origin(cur, org, f.lag0 && e == f.n_live - 1, lane, acc + 4 * e, acc + 4 * f.n_live, bad);
         }
-        // the snapshot becomes an origin: the slot's lag would be slots * stride > max_lag, so it was not read above,
-        // and a thread touches only its own particles' elements
-        if (a.store_slot >= 0) {
-            double *const o = a.ring + (size_t)a.store_slot * 6 * plane + base;
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const int i = tid + k * T;
-                if (i < n)
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) o[(size_t)c * plane + i] = cur[k][c];
-            }
-        }
+        batch_origin_store(a, f, cur);
     }
-    if (bad) a.range[rp.b] = 1;
+    if (bad) a.range[f.b] = 1;
     __syncthreads();
-
-    const int rows = a.max_lag + 1;
-    for (int k = tid; k < 2 * n_ent; k += blockDim.x) {
-        const int e = k >> 1, kind = k & 1;
-        const int lag = e < n_live ? a.lag_first - e * a.stride : 0;
-        if (lag < 0 || lag >= rows) continue;     // cannot happen with the host's arguments
-        const unsigned long long x0 = acc[4 * e + 2 * kind], x1 = acc[4 * e + 2 * kind + 1];
-        const uint64_t add[3] = {x0, x1, (long long)x1 < 0 ? ~0ull : 0ull};
-        uint64_t *const row = a.sums + (((size_t)rp.b * 2 + kind) * rows + lag) * 3;
-        uint64_t sum[3] = {row[0], row[1], row[2]};
-        add192(sum, add);
-        row[0] = sum[0];
-        row[1] = sum[1];
-        row[2] = sum[2];
-    }
+    batch_origin_add_rows(a, f, acc);
 }
 
 }  // namespace
 
 hipError_t launch_batch_tcf(const BatchTcfArgs &a, int n_max, int n_blocks, hipStream_t s)
 {
-    if (a.max_lag < 1 || a.max_lag > kBatchTcfMaxLag || a.stride < 1 || a.slots < 1 || a.slots > kBatchTcfMaxOrigins ||
-        a.n_live < 0 || a.n_live > a.slots || a.slot_first < 0 || a.slot_first >= a.slots || a.store_slot >= a.slots)
-        return hipErrorInvalidValue;
-    if (a.n_live > 0 && (a.lag_first > a.max_lag || a.lag_first - (a.n_live - 1) * a.stride < 1))
-        return hipErrorInvalidValue;
+    if (!batch_origin_window_ok(a, kBatchTcfMaxLag, kBatchTcfMaxOrigins)) return hipErrorInvalidValue;
     return dispatch_class(n_max, n_blocks, [&](auto nmax, auto k) {
         static_assert((kBatchTcfMaxOrigins + 1) * 32 <= 24 * 1024, "LDS budget of the accumulators");
         hipLaunchKernelGGL((batch_tcf_kernel<nmax(), k()>), dim3(n_blocks), dim3(batch_threads(n_max)),

@@ -24,8 +24,10 @@
 // floating-point atomics, no spin-waits.  A 32-bit LDS bin holds at most n <= 4096 between two clears.
 // LDS: 32 bytes per live origin, one entry more for the lag-0 terms, and 4 (nbins + 1) bytes of bins: at most
 // 513 * 32 + 1025 * 4 = 20516 bytes.
+// Frame, current snapshot, ring walk, store of the snapshot and the closing addition into the rows are shared with
+// batch_tcf_kernel (ljmd_batch_origins_dev.h); the per-particle body, the bins and the two-barrier loop are this kernel's.
+#include "ljmd_batch_origins_dev.h"
 #include "ljmd_batch_vanhove.h"
-#include "ljmd_internal.h"
 #include "ljmd_tcf_arith.h"
 
 namespace ljmdb {
@@ -37,36 +39,30 @@ template <int NMAX, int K>
 __global__ __launch_bounds__(kBatchMaxThreads) void batch_vanhove_kernel(BatchVanhoveArgs a)
 {
     extern __shared__ unsigned long long acc[];     // [n_live + 1][2 kinds][2 words], then the bins
-    const BatchReplica &rp = a.rep[a.g0 + blockIdx.x];
-    const int n = rp.n, T = rp.threads, tid = threadIdx.x, lane = tid & 63;
-    const size_t plane = a.plane, base = rp.off;
+    const BatchOriginFrame f = batch_origin_frame(a, acc);
+    const int n = f.n, T = f.T, tid = threadIdx.x, lane = tid & 63;
+    const size_t plane = a.plane;
     const int n_live = a.n_live, cols = a.nbins + 1, rows = a.max_lag + 1;
-    const bool lag0 = n_live > 0 && a.lag_first - (n_live - 1) * a.stride == 1;   // the newest origin is at lag 1
-    const int n_ent = n_live + (lag0 ? 1 : 0);
     unsigned *const lhist = reinterpret_cast<unsigned *>(acc + 4 * (n_live + 1));  // [nbins + 1]
-    const double dr = a.dr[rp.b], inv_dr = a.inv_dr[rp.b];
+    const double dr = a.dr[f.b], inv_dr = a.inv_dr[f.b];
 
-    for (int k = tid; k < 4 * n_ent; k += blockDim.x) acc[k] = 0ull;
     for (int k = tid; k < cols; k += blockDim.x) lhist[k] = 0u;
     __syncthreads();
 
     const bool own = tid < T;           // wave-uniform (T is a multiple of 64); the waves from T on own nothing
     double cur[K][3];
+    #pragma unroll
+    for (int k = 0; k < K; ++k)
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        const int i = tid + k * T;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) cur[k][c] = own && i < n ? a.state[(size_t)(3 + c) * plane + base + i] : 0.0;
-    }
+        for (int c = 0; c < 3; ++c) cur[k][c] = batch_origin_current(a, f, own, k, c);
 
     bool bad = false;
     int slot = a.slot_first;
 #pragma unroll 1
-    for (int e = 0; e < n_ent; ++e) {   // uniform across the workgroup: every thread meets both barriers
+    for (int e = 0; e < f.n_ent; ++e) { // uniform across the workgroup: every thread meets both barriers
         const bool zero = e == n_live;  // the lag-0 pass: the newest origin against itself
         if (zero) slot = slot == 0 ? a.slots - 1 : slot - 1;
-        const double *const o = a.ring + (size_t)slot * 3 * plane + base;
-        slot = slot + 1 == a.slots ? 0 : slot + 1;
+        const double *const o = batch_origin_next<3>(a, f, slot);
         const int lag = zero ? 0 : a.lag_first - e * a.stride;
         if (own) {
             long long s_hi = 0, s_lo = 0, q_hi = 0, q_lo = 0;       // limbs of Q(r2) and Q(r4) of this origin
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_vanhove_kernel(BatchVa
         }
         __syncthreads();                            // the origin's histogram is complete
         if (lag >= 0 && lag < rows) {               // always, with the host's arguments
-            unsigned long long *const hrow = a.hist + ((size_t)rp.b * rows + lag) * cols;
+            unsigned long long *const hrow = a.hist + ((size_t)f.b * rows + lag) * cols;
             for (int k = tid; k < cols; k += blockDim.x) {
                 const unsigned c = lhist[k];
                 if (c) {
@@ -114,34 +110,10 @@ __global__ __launch_bounds__(kBatchMaxThreads) void batch_vanhove_kernel(BatchVa
         }
         __syncthreads();                            // cleared before the next origin increments
     }
-    // the snapshot becomes an origin: the slot's lag would be slots * stride > max_lag, so it was not read above, and a
-    // thread touches only its own particles' elements
-    if (own && a.store_slot >= 0) {
-        double *const o = a.ring + (size_t)a.store_slot * 3 * plane + base;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const int i = tid + k * T;
-            if (i < n)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) o[(size_t)c * plane + i] = cur[k][c];
-        }
-    }
-    if (bad) a.range[rp.b] = 1;
+    if (own) batch_origin_store(a, f, cur);
+    if (bad) a.range[f.b] = 1;
     // the entries are complete: the last entry_add lies before the loop's barriers
-
-    for (int k = tid; k < 2 * n_ent; k += blockDim.x) {
-        const int e = k >> 1, kind = k & 1;
-        const int lag = e < n_live ? a.lag_first - e * a.stride : 0;
-        if (lag < 0 || lag >= rows) continue;     // cannot happen with the host's arguments
-        const unsigned long long x0 = acc[4 * e + 2 * kind], x1 = acc[4 * e + 2 * kind + 1];
-        const uint64_t add[3] = {x0, x1, (long long)x1 < 0 ? ~0ull : 0ull};
-        uint64_t *const row = a.sums + (((size_t)rp.b * 2 + kind) * rows + lag) * 3;
-        uint64_t sum[3] = {row[0], row[1], row[2]};
-        add192(sum, add);
-        row[0] = sum[0];
-        row[1] = sum[1];
-        row[2] = sum[2];
-    }
+    batch_origin_add_rows(a, f, acc);
 }
 
 }  // namespace
@@ -151,12 +123,7 @@ hipError_t launch_batch_vanhove(const BatchVanhoveArgs &a, int n_max, int n_bloc
     if (!a.state || !a.ring || !a.hist || !a.sums || !a.range || !a.dr || !a.inv_dr || !a.rep || a.g0 < 0 ||
         a.nbins < 1 || a.nbins > kBatchVanhoveMaxBins)
         return hipErrorInvalidValue;
-    if (a.max_lag < 1 || a.max_lag > kBatchVanhoveMaxLag || a.stride < 1 || a.slots < 1 ||
-        a.slots > kBatchVanhoveMaxOrigins || a.n_live < 0 || a.n_live > a.slots || a.slot_first < 0 ||
-        a.slot_first >= a.slots || a.store_slot >= a.slots)
-        return hipErrorInvalidValue;
-    if (a.n_live > 0 && (a.lag_first > a.max_lag || a.lag_first - (a.n_live - 1) * a.stride < 1))
-        return hipErrorInvalidValue;
+    if (!batch_origin_window_ok(a, kBatchVanhoveMaxLag, kBatchVanhoveMaxOrigins)) return hipErrorInvalidValue;
     return dispatch_class(n_max, n_blocks, [&](auto nmax, auto k) {
         static_assert((kBatchVanhoveMaxOrigins + 1) * 32 + (kBatchVanhoveMaxBins + 1) * 4 <= 24 * 1024,
                       "LDS budget of the entries and the bins");

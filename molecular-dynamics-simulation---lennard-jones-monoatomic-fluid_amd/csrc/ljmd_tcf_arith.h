@@ -2,7 +2,9 @@
 // kernel (ljmd_batch_tcf.hip) and the single engine's (ljmd_tcf.hip): a term enters an exact integer sum as
 // Q(t) = RNE(t 2^64), split into two int64 limbs that a wave sums by integer shuffles and lane 0 adds, as one 128-bit
 // integer, into an LDS entry; and the two terms of one origin for the particles of a thread (tcf_origin).  The van Hove
-// kernel (ljmd_vanhove.hip) uses the limbs and the entries.
+// kernels (ljmd_vanhove.hip, ljmd_batch_vanhove.hip) use the limbs and the entries.  What surrounds the arithmetic -- the
+// frame of a workgroup, the ring walk, the rows it writes -- is ljmd_origins_dev.h for the single engine's kernels and
+// ljmd_batch_origins_dev.h for the batch engine's.
 #ifndef LJMD_TCF_ARITH_H
 #define LJMD_TCF_ARITH_H
 

@@ -5,7 +5,8 @@
 // -- and the step launcher moves every ru by an exactly representable amount per step, so that the C ABI can be checked
 // against a brute-force loop over stored snapshots: several (max_lag, stride, nbins), per-replica n and rmax, ring wrap, a
 // new trajectory, `every` inside ljmd_batch_steps, an injected launch failure, every guard's code and message, the
-// arguments of every launch and the byte counts of configure.  hipMalloc and hipFree of the fake runtime are wrapped at
+// arguments of every launch and the byte counts of configure; and, for MSD / VACF beside it, that a set range word fails
+// a read before anything is written.  hipMalloc and hipFree of the fake runtime are wrapped at
 // link time (-Wl,--wrap) so that the program sees the allocations.  It checks itself, prints one line per check that
 // fails and "batch_vanhove_host: ok" when none did.  tests/test_batch_vanhove_host.py runs it under ASan and UBSan.
 #include "ljmd.h"
@@ -54,6 +55,7 @@ struct Launch {
 };
 std::vector<Launch> g_log;
 int g_fail_vanhove = 0;                    // k > 0: the k-th van Hove launch from now returns hipErrorLaunchFailure
+int g_tcf_flags = -1;                      // >= 0: an MSD / VACF launch sets the range word of this replica
 
 // Q(t) = RNE(t 2^64) as an integer; |t| < 2^40
 __int128 Q(double t) { return (__int128)std::rint(t * 0x1p64); }
@@ -138,6 +140,7 @@ hipError_t launch_batch_rdf(const BatchRdfArgs &a, int n_max, int n_blocks, hipS
 hipError_t launch_batch_tcf(const BatchTcfArgs &a, int n_max, int n_blocks, hipStream_t s)
 {
     g_log.push_back({'T', a.g0, n_max, n_blocks, s, 0, 0, 0, 0, 0, 0});
+    if (g_tcf_flags >= 0) a.range[g_tcf_flags] = 1;
     return hipSuccess;
 }
 
@@ -549,6 +552,49 @@ void inside_steps()
     check(g_live == 0, "destroy frees everything (three accumulators on)");
 }
 
+// 4. MSD / VACF, the other observable of the same ring rules: a set range word fails its reads BEFORE anything is written
+// to the caller's arrays, counts or n_snapshots -- where the van Hove reads above fill everything and then fail
+void tcf_read_on_range()
+{
+    const int32_t n[kB] = {8, 8, 8};
+    ljmd_batch_t *h = nullptr;
+    check(ljmd_batch_create_per_replica(&h, kB, n, kL, kDt, kRc, LJMD_PRECISION_FP64, 0) == LJMD_OK && h, "create (n = 8)");
+    if (!h) return;
+    check(set_grid_state(h, 0) == LJMD_OK && ljmd_batch_tcf_configure(h, 2, 1, 0) == LJMD_OK, "state, MSD / VACF configured");
+    g_tcf_flags = 1;
+    g_log.clear();
+    check(ljmd_batch_tcf_accumulate(h) == LJMD_OK && only('T').size() == 1, "one snapshot, whose launch sets replica 1's range word");
+    g_tcf_flags = -1;
+    const size_t rows = 3;
+    const double sd = -7.0;
+    const int64_t si = 99;
+    std::vector<double> msd(kB * rows, sd), vacf(kB * rows, sd);
+    std::vector<int64_t> words(kB * 2 * rows * 3, si), counts(rows, si);
+    int64_t n_snap = si;
+    auto untouched = [&] {
+        bool ok = n_snap == si;
+        for (double x : msd) ok = ok && x == sd;
+        for (double x : vacf) ok = ok && x == sd;
+        for (int64_t x : words) ok = ok && x == si;
+        for (int64_t x : counts) ok = ok && x == si;
+        return ok;
+    };
+    check(ljmd_batch_tcf_read(h, msd.data(), vacf.data(), counts.data(), &n_snap) == LJMD_ERR_RANGE &&
+              message_has(h, "ljmd_batch_tcf_read: replica 1: an MSD or VACF term") && message_has(h, "until ljmd_batch_tcf_reset") &&
+              !h->poisoned, "ljmd_batch_tcf_read: LJMD_ERR_RANGE names replica 1; no poison");
+    check(untouched(), "... with msd, vacf, counts and n_snapshots untouched");
+    check(ljmd_batch_tcf_read_exact(h, words.data(), counts.data(), &n_snap) == LJMD_ERR_RANGE &&
+              message_has(h, "ljmd_batch_tcf_read_exact: replica 1: an MSD or VACF term") && !h->poisoned,
+          "ljmd_batch_tcf_read_exact: LJMD_ERR_RANGE names replica 1; no poison");
+    check(untouched(), "... with words, counts and n_snapshots untouched");
+    check(ljmd_batch_tcf_reset(h) == LJMD_OK && ljmd_batch_tcf_read(h, msd.data(), vacf.data(), counts.data(), &n_snap) == LJMD_OK &&
+              n_snap == 0 && counts[0] == 0 && msd[0] == 0.0 && vacf[kB * rows - 1] == 0.0 &&
+              ljmd_batch_tcf_read_exact(h, words.data(), counts.data(), &n_snap) == LJMD_OK && words[0] == 0,
+          "after ljmd_batch_tcf_reset the reads succeed and fill their arrays");
+    ljmd_batch_destroy(h);
+    check(g_live == 0, "destroy frees everything (MSD / VACF alone)");
+}
+
 }  // namespace
 
 int main()
@@ -558,6 +604,7 @@ int main()
     guards();
     against_brute_force();
     inside_steps();
+    tcf_read_on_range();
     if (g_failures == 0) std::printf("batch_vanhove_host: ok\n");
     return g_failures == 0 ? 0 : 1;
 }
