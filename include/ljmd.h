@@ -677,6 +677,83 @@ int ljmd_heatflux_reset(ljmd_t *h);
 int ljmd_heatflux_profile_read(ljmd_t *h, int64_t *tile_pairs_visited, int64_t *tile_pairs_total, double *kernel_ms);
 int ljmd_heatflux_from_exact(const int64_t *words /* [9][3] */, double box_length, double *j3, double *parts9 /* may be NULL */);
 
+/*
+ * Collective density modes of the resident system, rho_k(t) = sum_j exp(i k . r_j(t)) with k = (2 pi / L) (n_x, n_y, n_z)
+ * for a list of integer triples n, one snapshot per call, recorded where r lives (ljmd_rhok_*): no snapshot leaves the
+ * device.  S(k) = <|rho_k|^2> / N and the coherent intermediate scattering function F(k, tau) = <Re rho_k(t0 + tau)
+ * rho_k*(t0)> / N follow from this one series (analysis.static_structure_factor, analysis.intermediate_scattering).
+ * One-rank engines only (ljmd_create with n_ranks = 1); n <= 2^23.  Sign convention: rho_k = sum (cos k.r, + sin k.r).
+ *
+ * Definition.  One snapshot is, per mode of the list in list order, two signed 192-bit integers Re then Im, each three
+ * int64 limbs, least significant first (the layout of ljmd_stress_read_exact): 48 bytes per mode.  Everything is fp64
+ * with separate roundings, no fused multiply-add anywhere; rint is round-half-even.  Per particle and mode, with x, y, z
+ * the positions that ljmd_get_state returns as r (the exchange buffer) and n the mode's triple converted to double:
+ *     t_a  = x_a / L ;  t_a = t_a - rint(t_a)                 (a = x, y, z; IEEE division; the subtraction is exact)
+ *     phi  = (n_x*t_x + n_y*t_y) + n_z*t_z                     (each product and each sum rounded once)
+ *     f    = phi - rint(phi)                                   (exact, |f| <= 1/2)
+ *     q    = rint(4*f) ;  g = f - 0.25*q                       (exact, |g| <= 1/8; q in -2 .. 2)
+ *     th   = g * 0x1.921fb54442d18p+2 ;  zz = th*th
+ *     ps   = S15 ; ps = ps*zz + S13 ; ... ; ps = ps*zz + S3 ;  s = th + th*(zz*ps)
+ *     pc   = C16 ; pc = pc*zz + C14 ; ... ; pc = pc*zz + C2 ;  c = 1.0 + zz*pc
+ *     (q & 3) = 0: (C, S) = (c, s)    1: (-s, c)    2: (-c, -s)    3: (s, -c)
+ *     Re[m] += Q(C) ;  Im[m] += Q(S)                           with Q(t) = RNE(t 2^64)
+ *   The coefficients are the correctly rounded doubles of (-1)^j / (2j+1)! and (-1)^j / (2j)!:
+ *     S3 = -0x1.5555555555555p-3    S5 = 0x1.1111111111111p-7     S7 = -0x1.a01a01a01a01ap-13   S9 = 0x1.71de3a556c734p-19
+ *     S11 = -0x1.ae64567f544e4p-26  S13 = 0x1.6124613a86d09p-33   S15 = -0x1.ae7f3e733b81fp-41
+ *     C2 = -0x1p-1                  C4 = 0x1.5555555555555p-5     C6 = -0x1.6c16c16c16c17p-10   C8 = 0x1.a01a01a01a01ap-16
+ *     C10 = -0x1.27e4fb7789f5cp-22  C12 = 0x1.1eed8eff8d898p-29   C14 = -0x1.93974a8c07c9dp-37  C16 = 0x1.ae7f3e733b81fp-45
+ *   Given f, C and S are within 1.4 2^-53 of cos 2 pi f and sin 2 pi f; the whole term is within
+ *   2 pi 2^-53 sum_a |n_a| (|x_a| / L + 1.5) + 2^-51 of the true cos / sin of k . r.
+ *   Range: a term is out of range when C or S is not finite, which happens with a coordinate or an L that is not; it
+ *   then enters as two zeros and sets a sticky word.  An arithmetic flag: nothing wraps, nothing faults.
+ *   Padding slots of the engine's layout are not particles: they add nothing and set no flag.
+ *   Symmetry: the arithmetic is odd / even symmetric, so mode -n has the same Re words and exactly negated Im words;
+ *   mode (0, 0, 0) has Re = n 2^64 and Im = 0.
+ *   Doubles: rho[m] = (R(Re[m]), R(Im[m])) with R(x) = RNE(x) 2^-64, ONE rounding of each integer.
+ * The integers depend on the positions and the mode list alone: not on slot order, re-sorts, grid shape, precision mode
+ * or knobs; a mode's words do not depend on the rest of the list.
+ * select_modes: pure host code without a handle, the list the drivers use.  The triples of the half-space (n_x > 0, or
+ * n_x = 0 and n_y > 0, or n_x = n_y = 0 and n_z > 0) with 1 <= |n|^2 <= n2_max <= LJMD_RHOK_MAX_INDEX^2, grouped by |n|^2
+ * ascending, within a shell lexicographic in (n_x, n_y, n_z); a shell with count > per_shell members keeps the members
+ * at indices floor(j count / per_shell), j = 0 .. per_shell - 1.  *n_modes receives the number of modes; with capacity
+ * too small the call returns LJMD_ERR_INVALID_ARG with the needed count in *n_modes (modes may then be NULL for
+ * capacity = 0).
+ * configure: 1 <= n_modes <= LJMD_RHOK_MAX_MODES triples of |n_a| <= LJMD_RHOK_MAX_INDEX -- (0, 0, 0), negatives and
+ * duplicates included -- 1 <= max_snapshots <= LJMD_RHOK_MAX_SNAPSHOTS, max_snapshots * n_modes <= LJMD_RHOK_MAX_ENTRIES
+ * and n <= 2^23; copies the list to the device, allocates and zeroes the series there; calling it again reconfigures
+ * and zeroes; max_snapshots = 0 switches the feature off and frees everything, whatever the other arguments.  A failed
+ * guard returns LJMD_ERR_INVALID_ARG and leaves the earlier configuration in place; a failed allocation LJMD_ERR_ALLOC
+ * with the feature off.  Works with or without a state.  On a rank engine (n_ranks > 1) or a multi-device handle
+ * (ljmd_create_multi) configure with max_snapshots > 0 returns LJMD_ERR_INVALID_ARG ("... n_ranks = <G>: a rank holds
+ * only its own particles ..."), and the other calls LJMD_ERR_STATE ("not configured").  The setters, ljmd_migrate and
+ * the other five observables leave configuration and series alone, and it leaves theirs alone.
+ * accumulate: appends one snapshot, stream-ordered on the engine's stream behind everything enqueued so far
+ * (ljmd_enqueue_steps* included), no host wait.  It needs a state but no accelerations: LJMD_ERR_STATE before
+ * configure, without a state, on a poisoned handle and between ljmd_step_begin and ljmd_step_finish; then
+ * LJMD_ERR_STATE when the series is full, before anything is launched.  It reads the exchange buffer and the slot
+ * permutation and writes only buffers of its own: r, ru, v, a, the step records, the other five observables and every
+ * later result stay bitwise what they are without the call.  Switched off it launches nothing, and no existing kernel
+ * knows of it.
+ * read_exact / read: wait for the device; words[n][n_modes][2][3] (read_exact) or rho[n][n_modes][2] (read) for the n
+ * snapshots taken since configure / reset, and n -- any pointer may be NULL; they clear nothing.  While the sticky word
+ * is set they return LJMD_ERR_RANGE, until ljmd_rhok_reset; the handle is not poisoned and stepping is unaffected.
+ * reset: empties the series and clears the sticky word.
+ * profile_read, for the most recent accumulate (zero before the first): the time of its launches from HIP events; the
+ * pointer may be NULL; waits for the device.
+ * read_exact, read, reset and profile_read return LJMD_ERR_STATE before configure.
+ */
+#define LJMD_RHOK_MAX_MODES 4096
+#define LJMD_RHOK_MAX_INDEX 1023            /* |n_a| of a mode */
+#define LJMD_RHOK_MAX_SNAPSHOTS 262144
+#define LJMD_RHOK_MAX_ENTRIES (1 << 24)     /* max_snapshots * n_modes: 805 MB of series */
+int ljmd_rhok_select_modes(int32_t n2_max, int32_t per_shell, int32_t capacity, int32_t *modes /* [capacity][3] */, int32_t *n_modes);
+int ljmd_rhok_configure(ljmd_t *h, int32_t n_modes, const int32_t *modes /* [n_modes][3] */, int32_t max_snapshots);
+int ljmd_rhok_accumulate(ljmd_t *h);
+int ljmd_rhok_read_exact(ljmd_t *h, int64_t *words /* [n][n_modes][2][3]: Re then Im */, int64_t *n_snapshots);
+int ljmd_rhok_read(ljmd_t *h, double *rho /* [n][n_modes][2] */, int64_t *n_snapshots);
+int ljmd_rhok_reset(ljmd_t *h);
+int ljmd_rhok_profile_read(ljmd_t *h, double *kernel_ms);
+
 /* ---- batch engine: many independent small systems on one device ------------------------------------------------
  *
  * One ljmd_batch_t holds B replicas on one device -- the ensemble runs of the reference's run-many framework

@@ -157,6 +157,13 @@ PROTOTYPES = {
     "ljmd_heatflux_reset": (C.c_int, [C.c_void_p]),
     "ljmd_heatflux_profile_read": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p, c_double_p]),
     "ljmd_heatflux_from_exact": (C.c_int, [c_int64_p, C.c_double, c_double_p, c_double_p]),
+    "ljmd_rhok_select_modes": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_int32_p, c_int32_p]),
+    "ljmd_rhok_configure": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32]),
+    "ljmd_rhok_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_rhok_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ljmd_rhok_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
+    "ljmd_rhok_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_rhok_profile_read": (C.c_int, [C.c_void_p, c_double_p]),
     "ljmd_batch_rdf_configure": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     "ljmd_batch_rdf_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_batch_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
@@ -198,6 +205,10 @@ BATCH_VANHOVE_MAX_ORIGINS = 512
 BATCH_VANHOVE_MAX_BINS = 1024
 STRESS_MAX_SNAPSHOTS = 262144
 HEATFLUX_MAX_SNAPSHOTS = 262144
+RHOK_MAX_MODES = 4096
+RHOK_MAX_INDEX = 1023
+RHOK_MAX_SNAPSHOTS = 262144
+RHOK_MAX_ENTRIES = 1 << 24
 BATCH_STRESS_MAX_SNAPSHOTS = 262144
 BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
 

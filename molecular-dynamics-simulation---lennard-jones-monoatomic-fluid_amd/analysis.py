@@ -188,6 +188,58 @@ def thermal_conductivity_green_kubo(acf, dt_sample: float, V: float, T: float) -
     return (V / (T * T)) * run
 
 
+# -- collective density modes (Engine.rhok_read: rho[n_snap, n_modes] complex, modes[n_modes, 3] integer triples) ------
+def rhok_shells(modes):
+    """modes [n_modes, 3] -> (n2[n_shells], members): the distinct |n|^2 of the list in ascending order and, per shell,
+    the indices of its modes in list order."""
+    modes = np.asarray(modes)
+    if modes.ndim != 2 or modes.shape[1] != 3 or modes.shape[0] < 1:
+        raise ValueError(f"density modes: modes must have shape (n_modes, 3) with n_modes >= 1, got {modes.shape}")
+    n2 = (modes.astype(np.int64) ** 2).sum(axis=1)
+    shells = np.unique(n2)
+    return shells, [np.flatnonzero(n2 == s) for s in shells]
+
+
+def _rhok_series(rho, modes, who: str):
+    rho = np.asarray(rho, dtype=np.complex128)
+    shells, members = rhok_shells(modes)
+    if rho.ndim != 2 or rho.shape[0] < 1 or rho.shape[1] != np.asarray(modes).shape[0]:
+        raise ValueError(f"{who}: rho must have shape (n_snap >= 1, n_modes = {np.asarray(modes).shape[0]}), got {rho.shape}")
+    return rho, shells, members
+
+
+def static_structure_factor(rho, n: int, modes, L: float):
+    """rho [n_snap, n_modes]: a series of density modes of n particles in a box of side L -> (k, S, stderr, n_modes_of),
+    one entry per shell of equal |n|^2 in ascending order: k = 2 pi sqrt(|n|^2) / L, S(k) = <|rho_k|^2> / n over the
+    snapshots and the shell's modes, the standard error of that mean over the snapshots (each snapshot's value the mean
+    over the shell's modes; sample standard deviation, ddof = 1, over sqrt(n_snap); NaN with one snapshot), and the
+    number of modes of the shell."""
+    rho, shells, members = _rhok_series(rho, modes, "static_structure_factor")
+    if n < 1 or not L > 0.0:
+        raise ValueError("static_structure_factor: n >= 1 and L > 0")
+    n_snap = rho.shape[0]
+    per_snap = np.stack([(rho[:, m].real ** 2 + rho[:, m].imag ** 2).mean(axis=1) / n for m in members], axis=1)
+    S = per_snap.mean(axis=0)
+    err = per_snap.std(axis=0, ddof=1) / np.sqrt(n_snap) if n_snap > 1 else np.full_like(S, np.nan)
+    k = 2.0 * np.pi * np.sqrt(shells.astype(np.float64)) / L
+    return k, S, err, np.array([len(m) for m in members], dtype=np.int64)
+
+
+def intermediate_scattering(rho, n: int, modes, max_lag=None, origin_stride: int = 1) -> np.ndarray:
+    """rho [n_snap, n_modes] -> F[n_shells, max_lag + 1]: the coherent intermediate scattering function F(k, tau) =
+    <Re rho_k(t0 + tau) rho_k*(t0)> / n over the time origins and the shell's modes, the shells in the order of
+    static_structure_factor.  Formula, origin convention and counts are those of compute_vacf_tau_timeorig with the
+    shell's modes as the particles and (Re, Im, 0) as the velocity; F(k, 0) is S(k) over the origins used."""
+    rho, _shells, members = _rhok_series(rho, modes, "intermediate_scattering")
+    if n < 1:
+        raise ValueError("intermediate_scattering: n >= 1")
+    rows = []
+    for m in members:
+        re, im = np.ascontiguousarray(rho[:, m].real), np.ascontiguousarray(rho[:, m].imag)
+        rows.append(compute_vacf_tau_timeorig(re, im, np.zeros_like(re), max_lag, origin_stride) / n)
+    return np.stack(rows)
+
+
 # -- van Hove self-correlation (Engine.vanhove_read: hist[max_lag + 1, nbins + 1] with the overflow column last) --------
 def _vanhove_rows(hist, counts, n: int):
     """-> (inside [rows, nbins] float64, overflow fraction [rows], 1 / (n count) [rows], 0 where count == 0)"""

@@ -1,18 +1,20 @@
-// ljmd_resident.h -- host side of the five observables of the system resident on the single / sharded engine: g(r)
+// ljmd_resident.h -- host side of the six observables of the system resident on the single / sharded engine: g(r)
 // (ljmd_rdf.cpp); the pressure tensor (ljmd_stress.cpp) and the heat flux (ljmd_heatflux.cpp), which are two descriptors
 // over the one series core (ljmd_series.cpp); MSD / VACF (ljmd_tcf.cpp) and the van Hove self-correlation
-// (ljmd_vanhove.cpp), which are two descriptors over the one time-origin core (ljmd_origins.cpp).  What the cores share
+// (ljmd_vanhove.cpp), which are two descriptors over the one time-origin core (ljmd_origins.cpp); the density modes
+// (ljmd_rhok.cpp).  What the cores share
 // -- the view through which they see an engine, their named device buffers, the timer around one accumulate -- and each
 // core's state and functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host,
-// tests/tcf_host, tests/stress_host, tests/heatflux_host, tests/vanhove_host); every C entry point that takes a handle
-// is in ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_stress.h, ljmd_heatflux.h, ljmd_tcf.h
-// and ljmd_vanhove.h, the latter two over ljmd_origins.h.
+// tests/tcf_host, tests/stress_host, tests/heatflux_host, tests/vanhove_host, tests/rhok_host); every C entry point that
+// takes a handle is in ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_stress.h,
+// ljmd_heatflux.h, ljmd_rhok.h, ljmd_tcf.h and ljmd_vanhove.h, the latter two over ljmd_origins.h.
 #ifndef LJMD_RESIDENT_H
 #define LJMD_RESIDENT_H
 
 #include "ljmd_common.h"
 #include "ljmd_heatflux.h"
 #include "ljmd_rdf.h"
+#include "ljmd_rhok.h"
 #include "ljmd_stress.h"
 #include "ljmd_tcf.h"
 #include "ljmd_tcf_host.h"
@@ -356,4 +358,38 @@ void vanhove_new_trajectory(VanHoveState *st);
 void vanhove_release(VanHoveState *st, hipStream_t stream);
 
 }  // namespace ljmdv
+
+// The density modes (ljmd_rhok.cpp): a series like the pressure tensor's, of n_modes rows of six words per snapshot, with
+// a core of its own -- a mode list on the device, no pair part.
+namespace ljmdc {
+
+using ljmdh::ResidentView;
+
+struct RhokState {
+    int max_snapshots = 0;          // 0 = not configured
+    int n_modes = 0, n = 0, T = 0;  // the list's length, and the engine configure saw
+    RhokPlan plan;
+    uint64_t *d_series = nullptr;   // [max_snapshots][n_modes][kRhokRowWords]
+    int32_t *d_modes = nullptr;     // [n_modes][3]
+    uint64_t *d_part = nullptr;     // [pchunks][mchunks 64][kRhokRowWords]
+    unsigned *d_flag = nullptr;     // [pchunks][mchunks]
+    int32_t *d_range = nullptr;
+    ljmdh::KernelTimer timer;
+    int64_t snapshots = 0;
+};
+
+int not_configured(std::string *err, const char *who);
+// refuses a multi-device handle and a rank engine of G > 1 itself; copies the list to the device before it returns
+int rhok_configure(RhokState *st, std::string *err, const char *who, const ResidentView &v, int32_t n_modes,
+                   const int32_t *modes, int32_t max_snapshots);
+int rhok_accumulate(RhokState *st, std::string *err, const char *who, const ResidentView &v);
+// words [snapshots][n_modes][2][3], either pointer may be NULL; LJMD_ERR_RANGE while the sticky word is set
+int rhok_fetch(RhokState *st, std::string *err, const char *who, const ResidentView &v, int64_t *words, int64_t *n_snapshots);
+// rho [snapshots][n_modes][2]: fixed_to_double of every integer
+int rhok_read(RhokState *st, std::string *err, const char *who, const ResidentView &v, double *rho, int64_t *n_snapshots);
+int rhok_reset(RhokState *st, std::string *err, const char *who, const ResidentView &v);
+int rhok_profile_read(RhokState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms);
+void rhok_release(RhokState *st, hipStream_t stream);
+
+}  // namespace ljmdc
 #endif

@@ -35,6 +35,8 @@ module ljmd_c_api
   public :: ljmd_stress_profile_read, ljmd_stress_from_exact, ljmd_time_origin_average
   public :: ljmd_heatflux_configure, ljmd_heatflux_accumulate, ljmd_heatflux_read, ljmd_heatflux_read_exact
   public :: ljmd_heatflux_reset, ljmd_heatflux_profile_read, ljmd_heatflux_from_exact
+  public :: ljmd_rhok_select_modes, ljmd_rhok_configure, ljmd_rhok_accumulate, ljmd_rhok_read, ljmd_rhok_read_exact
+  public :: ljmd_rhok_reset, ljmd_rhok_profile_read
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_stress_configure, ljmd_batch_stress_accumulate, ljmd_batch_stress_read, ljmd_batch_stress_read_exact
@@ -62,6 +64,10 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_BATCH_STRESS_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_HEATFLUX_MAX_SNAPSHOTS = 262144
+  integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_MODES = 4096
+  integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_INDEX = 1023
+  integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_SNAPSHOTS = 262144
+  integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_ENTRIES = 16777216
 
   interface
     function ljmd_compute_lj_potential_energy(n, box_length, rc, rx, ry, rz, ax, ay, az, &
@@ -578,6 +584,58 @@ module ljmd_c_api
       import :: c_int, c_double, c_ptr
       type(c_ptr), value :: words, j3, parts9
       real(c_double), value :: box_length
+      integer(c_int) :: status
+    end function
+
+    ! density modes of the system resident on a one-rank engine handle (ljmd.h: ljmd_rhok_*); modes = c_loc of
+    ! [3, n_modes] 32-bit integers, rho = c_loc of [2, n_modes, n_snapshots] doubles (Re, Im), words = c_loc of
+    ! [3, 2, n_modes, n_snapshots] 64-bit words in Fortran order; c_null_ptr skips an output
+    function ljmd_rhok_select_modes(n2_max, per_shell, capacity, modes, n_modes) bind(C, name="ljmd_rhok_select_modes") &
+        result(status)
+      import :: c_int, c_int32_t, c_ptr
+      integer(c_int32_t), value :: n2_max, per_shell, capacity
+      type(c_ptr), value :: modes
+      integer(c_int32_t), intent(out) :: n_modes
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rhok_configure(handle, n_modes, modes, max_snapshots) bind(C, name="ljmd_rhok_configure") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle, modes
+      integer(c_int32_t), value :: n_modes, max_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rhok_accumulate(handle) bind(C, name="ljmd_rhok_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rhok_read(handle, rho, n_snapshots) bind(C, name="ljmd_rhok_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, rho
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rhok_read_exact(handle, words, n_snapshots) bind(C, name="ljmd_rhok_read_exact") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rhok_reset(handle) bind(C, name="ljmd_rhok_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_rhok_profile_read(handle, kernel_ms) bind(C, name="ljmd_rhok_profile_read") result(status)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: handle
+      real(c_double), intent(out) :: kernel_ms
       integer(c_int) :: status
     end function
 

@@ -14,9 +14,12 @@
 !   (ljmd_heatflux_*) and its Green-Kubo autocorrelation (write_heat_flux_file, write_heat_flux_acf_file).
 !   <dir>/van_hove_gpu.dat: the van Hove self-correlation md_simulation_gpu accumulated on the device (ljmd_vanhove_*):
 !   per lag the moments, the non-Gaussian parameter and the counts of |displacement| (write_van_hove_file).
+!   <dir>/density_modes_gpu.dat, <dir>/structure_factor_gpu.dat, <dir>/intermediate_scattering_gpu.dat: the density
+!   modes rho_k md_simulation_gpu recorded on the device (ljmd_rhok_*), S(k) and F(k, tau) per shell of equal |n|^2
+!   (write_density_modes_file, write_structure_factor_file, write_intermediate_scattering_file).
 !==============================================================================
 module md_run_outputs
-  use, intrinsic :: iso_c_binding, only: c_int64_t
+  use, intrinsic :: iso_c_binding, only: c_int64_t, c_int32_t
   use define_precision, only: dp_kind, int_kind
   use md_types,         only: sim_params
   use md_stats
@@ -24,6 +27,7 @@ module md_run_outputs
   private
   public :: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, write_stress_acf_file
   public :: write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file
+  public :: write_density_modes_file, density_mode_shells, write_structure_factor_file, write_intermediate_scattering_file
 
 contains
 
@@ -263,6 +267,108 @@ contains
     end do
     close(iu_a)
   end subroutine write_heat_flux_acf_file
+
+  ! density_modes_gpu.dat: a header line listing the modes (nx,ny,nz), then per sampling instant the time and Re, Im of
+  ! rho_k of every mode in list order
+  subroutine write_density_modes_file(filename, n_modes, modes, n_snapshots, times, rho)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: n_modes, n_snapshots
+    integer(c_int32_t), intent(in) :: modes(3, n_modes)
+    real(kind=dp_kind), intent(in) :: times(n_snapshots), rho(2, n_modes, n_snapshots)
+    integer :: iu_r, ierr, k, m
+    open(newunit=iu_r, file=filename, status='replace', action='write', recl=26 * (2 * n_modes + 1) + 64 + 24 * n_modes, &
+         iostat=ierr)
+    if (ierr /= 0) stop 'write_density_modes_file(): cannot open density_modes_gpu.dat.'
+    write(iu_r, '(a)', advance='no') '# time   Re Im of rho_k, modes:'
+    do m = 1, n_modes
+      write(iu_r, '(a,i0,a,i0,a,i0,a)', advance='no') ' (', modes(1, m), ',', modes(2, m), ',', modes(3, m), ')'
+    end do
+    write(iu_r, '(a)') ''
+    do k = 1, n_snapshots
+      write(iu_r, '(es24.16e3)', advance='no') times(k)
+      do m = 1, n_modes
+        write(iu_r, '(2(2x,es24.16e3))', advance='no') rho(1, m, k), rho(2, m, k)
+      end do
+      write(iu_r, '(a)') ''
+    end do
+    close(iu_r)
+  end subroutine write_density_modes_file
+
+  ! the shells of a mode list grouped by |n|^2 (ljmd_rhok_select_modes): first(s) .. first(s + 1) - 1 are the modes of
+  ! shell s; returns the number of shells
+  subroutine density_mode_shells(n_modes, modes, n_shells, first)
+    integer, intent(in) :: n_modes
+    integer(c_int32_t), intent(in) :: modes(3, n_modes)
+    integer, intent(out) :: n_shells, first(n_modes + 1)
+    integer :: m, n2, prev
+    n_shells = 0
+    prev = -1
+    do m = 1, n_modes
+      n2 = int(modes(1, m))**2 + int(modes(2, m))**2 + int(modes(3, m))**2
+      if (n2 /= prev) then
+        n_shells = n_shells + 1
+        first(n_shells) = m
+        prev = n2
+      end if
+    end do
+    first(n_shells + 1) = n_modes + 1
+  end subroutine density_mode_shells
+
+  ! structure_factor_gpu.dat: per shell |n|^2, k = 2 pi sqrt(|n|^2) / L, the number of modes and S(k) = <|rho_k|^2> / N
+  ! over the snapshots and the shell's modes (per snapshot the mean over the modes, then the mean over the snapshots)
+  subroutine write_structure_factor_file(filename, n, box_length, n_modes, modes, n_snapshots, rho)
+    character(len=*), intent(in) :: filename
+    integer(kind=int_kind), intent(in) :: n
+    real(kind=dp_kind), intent(in) :: box_length
+    integer, intent(in) :: n_modes, n_snapshots
+    integer(c_int32_t), intent(in) :: modes(3, n_modes)
+    real(kind=dp_kind), intent(in) :: rho(2, n_modes, n_snapshots)
+    integer :: iu_s, ierr, s, m, k, n_shells, n2, cnt
+    integer, allocatable :: first(:)
+    real(kind=dp_kind) :: acc, snap
+    real(kind=dp_kind), parameter :: two_pi = 6.283185307179586476925286766559d0
+    allocate(first(n_modes + 1))
+    call density_mode_shells(n_modes, modes, n_shells, first)
+    open(newunit=iu_s, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_structure_factor_file(): cannot open structure_factor_gpu.dat.'
+    write(iu_s, '(a)') '# n2   k   modes   S(k)'
+    do s = 1, n_shells
+      m = first(s)
+      n2 = int(modes(1, m))**2 + int(modes(2, m))**2 + int(modes(3, m))**2
+      cnt = first(s + 1) - first(s)
+      acc = 0.d0
+      do k = 1, n_snapshots
+        snap = 0.d0
+        do m = first(s), first(s + 1) - 1
+          snap = snap + (rho(1, m, k) * rho(1, m, k) + rho(2, m, k) * rho(2, m, k))
+        end do
+        acc = acc + snap / dble(cnt) / dble(n)
+      end do
+      write(iu_s, '(i0,2x,es24.16e3,2x,i0,2x,es24.16e3)') n2, two_pi * sqrt(dble(n2)) / box_length, cnt, acc / dble(n_snapshots)
+    end do
+    close(iu_s)
+  end subroutine write_structure_factor_file
+
+  ! intermediate_scattering_gpu.dat: per lag, lag, tau = lag * output_interval * dt, then F(k, tau) of every shell
+  subroutine write_intermediate_scattering_file(filename, n_shells, max_lag, output_interval, dt, f)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: n_shells, max_lag
+    integer(kind=int_kind), intent(in) :: output_interval
+    real(kind=dp_kind), intent(in) :: dt
+    real(kind=dp_kind), intent(in) :: f(0:max_lag, n_shells)
+    integer :: iu_f, ierr, lag, s
+    open(newunit=iu_f, file=filename, status='replace', action='write', recl=26 * (n_shells + 1) + 64, iostat=ierr)
+    if (ierr /= 0) stop 'write_intermediate_scattering_file(): cannot open intermediate_scattering_gpu.dat.'
+    write(iu_f, '(a)') '# lag   tau   F(k, tau) per shell, in the order of structure_factor_gpu.dat'
+    do lag = 0, max_lag
+      write(iu_f, '(i0,2x,es24.16e3)', advance='no') lag, dble(lag) * dble(output_interval) * dt
+      do s = 1, n_shells
+        write(iu_f, '(2x,es24.16e3)', advance='no') f(lag, s)
+      end do
+      write(iu_f, '(a)') ''
+    end do
+    close(iu_f)
+  end subroutine write_intermediate_scattering_file
 
   subroutine write_curve(filename, header, errmsg, lag_max, c, cn)
     character(len=*), intent(in) :: filename, header, errmsg

@@ -44,7 +44,17 @@
 ! LJMD_VANHOVE_BINS bins (default 128) up to LJMD_VANHOVE_RMAX (default half the box) -- and
 ! outputs/one_run/van_hove_gpu.dat gets, per lag with at least one origin, lag, tau, the number of origins, <r^2>, <r^4>,
 ! the non-Gaussian parameter, the overflow count and the row of counts; one-rank engines only: with LJMD_GPUS > 1 the
-! program stops before an engine is created; every other output file is the same with and without it).
+! program stops before an engine is created; every other output file is the same with and without it),
+! LJMD_RHOK_N2MAX (default 0 = off; > 0: the collective density modes rho_k of the resident system are recorded on the
+! device -- ljmd_rhok_* -- at the same sampling instants, for the modes ljmd_rhok_select_modes gives: the half-space
+! triples with |n|^2 <= LJMD_RHOK_N2MAX, at most LJMD_RHOK_PER_SHELL (default 8) per shell of equal |n|^2;
+! outputs/one_run/density_modes_gpu.dat gets a header line listing the modes and per instant the time, then Re and Im
+! of every mode; outputs/one_run/structure_factor_gpu.dat per shell |n|^2, k, the number of modes and S(k) =
+! <|rho_k|^2> / N; with LJMD_RHOK_MAX_LAG > 0 outputs/one_run/intermediate_scattering_gpu.dat also gets, per lag up to
+! that many sampling instants, lag, tau and per shell the time-origin averaged F(k, tau) = <Re rho_k(t0 + tau)
+! rho_k*(t0)> / N -- ljmd_time_origin_average with the shell's modes as the particles and (Re, Im, 0) as the velocity;
+! one-rank engines only: with LJMD_GPUS > 1 the program stops before an engine is created; every other output file is
+! the same with and without it).
 !==============================================================================
 program md_simulation_gpu
   use, intrinsic :: iso_c_binding
@@ -55,7 +65,9 @@ program md_simulation_gpu
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
   use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
-                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file
+                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file, &
+                              write_density_modes_file, density_mode_shells, write_structure_factor_file, &
+                              write_intermediate_scattering_file
   implicit none
 
   type(sim_params) :: params
@@ -100,6 +112,14 @@ program md_simulation_gpu
   real(c_double), allocatable, target :: vh_r2(:), vh_r4(:)                ! [vh_max_lag + 1]
   integer(c_int64_t), allocatable, target :: vh_counts(:), vh_hist(:, :)   ! [vh_max_lag + 1], [vh_bins + 1, vh_max_lag + 1]
   integer(c_int64_t) :: vh_snapshots
+  integer :: rhok_n2max, rhok_per_shell, rhok_max_lag, rhok_lags, rhok_shells, rhok_s, rhok_cnt
+  integer(c_int32_t) :: rhok_n_modes
+  integer(c_int) :: rhok_status
+  integer(c_int32_t), allocatable, target :: rhok_modes(:, :)              ! [3, n_modes]
+  integer, allocatable :: rhok_first(:)
+  real(c_double), allocatable, target :: rhok_rho(:, :, :), rhok_times(:)  ! [2, n_modes, snapshots], [snapshots]
+  real(c_double), allocatable, target :: rhok_re(:, :), rhok_im(:, :), rhok_zero(:, :), rhok_f(:, :), rhok_row(:)
+  integer(c_int64_t) :: rhok_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -166,6 +186,18 @@ program md_simulation_gpu
   vh_rmax = 0.5d0 * params%box_length
   call get_environment_variable('LJMD_VANHOVE_RMAX', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) vh_rmax
+  rhok_n2max = 0
+  call get_environment_variable('LJMD_RHOK_N2MAX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rhok_n2max
+  if (rhok_n2max < 0) stop 'md_simulation: LJMD_RHOK_N2MAX must be >= 0.'
+  rhok_per_shell = 8
+  call get_environment_variable('LJMD_RHOK_PER_SHELL', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rhok_per_shell
+  if (rhok_per_shell < 1) stop 'md_simulation: LJMD_RHOK_PER_SHELL must be >= 1.'
+  rhok_max_lag = 0
+  call get_environment_variable('LJMD_RHOK_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rhok_max_lag
+  if (rhok_max_lag < 0) stop 'md_simulation: LJMD_RHOK_MAX_LAG must be >= 0.'
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
@@ -175,6 +207,8 @@ program md_simulation_gpu
     error stop 'md_simulation: LJMD_HEATFLUX needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1 .and. vh_max_lag > 0) &
     error stop 'md_simulation: LJMD_VANHOVE_MAX_LAG needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
+  if (n_gpus > 1 .and. rhok_n2max > 0) &
+    error stop 'md_simulation: LJMD_RHOK_N2MAX needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1) then
     allocate(device_list(n_gpus))
     device_list = [(int(k - 1, c_int32_t), k = 1, n_gpus)]
@@ -213,6 +247,22 @@ program md_simulation_gpu
       stop 'md_simulation: more sampling instants than LJMD_HEATFLUX_MAX_SNAPSHOTS.'
     call ljmd_check(ljmd_heatflux_configure(engine, int(n_snapshots_expected, c_int32_t)), engine, 'ljmd_heatflux_configure')
     allocate(heatflux_times(n_snapshots_expected))
+  end if
+  if (rhok_n2max > 0) then
+    n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
+    if (n_snapshots_expected < 1) stop 'md_simulation: LJMD_RHOK_N2MAX needs at least one sampling instant.'
+    if (n_snapshots_expected > LJMD_RHOK_MAX_SNAPSHOTS) stop 'md_simulation: more sampling instants than LJMD_RHOK_MAX_SNAPSHOTS.'
+    ! the count first (the call fails by design: capacity 0), then the list
+    rhok_status = ljmd_rhok_select_modes(int(rhok_n2max, c_int32_t), int(rhok_per_shell, c_int32_t), 0_c_int32_t, c_null_ptr, &
+                                         rhok_n_modes)
+    if (rhok_status == LJMD_OK .or. rhok_n_modes < 1) call ljmd_check(rhok_status, c_null_ptr, 'ljmd_rhok_select_modes')
+    if (rhok_n_modes > LJMD_RHOK_MAX_MODES) stop 'md_simulation: more modes than LJMD_RHOK_MAX_MODES: lower LJMD_RHOK_N2MAX.'
+    allocate(rhok_modes(3, rhok_n_modes))
+    call ljmd_check(ljmd_rhok_select_modes(int(rhok_n2max, c_int32_t), int(rhok_per_shell, c_int32_t), rhok_n_modes, &
+                                           c_loc(rhok_modes), rhok_n_modes), c_null_ptr, 'ljmd_rhok_select_modes')
+    call ljmd_check(ljmd_rhok_configure(engine, rhok_n_modes, c_loc(rhok_modes), int(n_snapshots_expected, c_int32_t)), engine, &
+                    'ljmd_rhok_configure')
+    allocate(rhok_times(n_snapshots_expected))
   end if
   ! t = 0 forces and energies (:236-243)
   call ljmd_check(ljmd_compute_forces(engine, epot, d_epot, dd_epot), engine, 'ljmd_compute_forces')
@@ -267,6 +317,10 @@ program md_simulation_gpu
       call ljmd_check(ljmd_heatflux_accumulate(engine), engine, 'ljmd_heatflux_accumulate')
       heatflux_times(num_samples + 1) = time
     end if
+    if (sample_now .and. rhok_n2max > 0) then
+      call ljmd_check(ljmd_rhok_accumulate(engine), engine, 'ljmd_rhok_accumulate')
+      rhok_times(num_samples + 1) = time
+    end if
     count = segment_length(step)
     if (async_io .and. count > 0) call enqueue_segment(count)
     if (sample_now) then
@@ -311,6 +365,11 @@ program md_simulation_gpu
     call ljmd_check(ljmd_heatflux_read(engine, c_loc(heatflux_j), c_loc(heatflux_parts), heatflux_snapshots), engine, &
                     'ljmd_heatflux_read')
     if (heatflux_snapshots /= num_samples) stop 'md_simulation: the heat flux series and the samples disagree.'
+  end if
+  if (rhok_n2max > 0) then
+    allocate(rhok_rho(2, rhok_n_modes, max(num_samples, 1)))
+    call ljmd_check(ljmd_rhok_read(engine, c_loc(rhok_rho), rhok_snapshots), engine, 'ljmd_rhok_read')
+    if (rhok_snapshots /= num_samples) stop 'md_simulation: the density mode series and the samples disagree.'
   end if
   call ljmd_destroy(engine)
 
@@ -365,6 +424,33 @@ program md_simulation_gpu
       call stats_mean_std(stats, Q_T, mean_temp, std_temp)
       call write_heat_flux_acf_file('outputs/one_run/heat_flux_acf_gpu.dat', heatflux_lags, output_interval, params%dt, &
                                     params%volume, mean_temp, heatflux_acf)
+    end if
+  end if
+  if (rhok_n2max > 0) then
+    call write_density_modes_file('outputs/one_run/density_modes_gpu.dat', int(rhok_n_modes), rhok_modes, int(num_samples), &
+                                  rhok_times, rhok_rho)
+    call write_structure_factor_file('outputs/one_run/structure_factor_gpu.dat', params%n, params%box_length, int(rhok_n_modes), &
+                                     rhok_modes, int(num_samples), rhok_rho)
+    if (rhok_max_lag > 0 .and. num_samples >= 2) then
+      ! per shell its modes as the particles and (Re, Im, 0) as the velocity: [modes of the shell, snapshots] each
+      allocate(rhok_first(rhok_n_modes + 1))
+      call density_mode_shells(int(rhok_n_modes), rhok_modes, rhok_shells, rhok_first)
+      rhok_lags = min(rhok_max_lag, int(num_samples) - 1)
+      allocate(rhok_f(0:rhok_lags, rhok_shells), rhok_row(0:rhok_lags))
+      do rhok_s = 1, rhok_shells
+        rhok_cnt = rhok_first(rhok_s + 1) - rhok_first(rhok_s)
+        allocate(rhok_re(rhok_cnt, num_samples), rhok_im(rhok_cnt, num_samples), rhok_zero(rhok_cnt, num_samples))
+        rhok_re = rhok_rho(1, rhok_first(rhok_s):rhok_first(rhok_s + 1) - 1, 1:num_samples)
+        rhok_im = rhok_rho(2, rhok_first(rhok_s):rhok_first(rhok_s + 1) - 1, 1:num_samples)
+        rhok_zero = 0.d0
+        call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(num_samples, c_int32_t), int(rhok_cnt, c_int32_t), &
+                                                 c_loc(rhok_re), c_loc(rhok_im), c_loc(rhok_zero), int(rhok_lags, c_int32_t), &
+                                                 1_c_int32_t, c_loc(rhok_row)), c_null_ptr, 'ljmd_time_origin_average')
+        rhok_f(:, rhok_s) = rhok_row / dble(params%n)
+        deallocate(rhok_re, rhok_im, rhok_zero)
+      end do
+      call write_intermediate_scattering_file('outputs/one_run/intermediate_scattering_gpu.dat', rhok_shells, rhok_lags, &
+                                              output_interval, params%dt, rhok_f)
     end if
   end if
   write(*, '(a,i0,a,i0,a,f10.2,a,es11.4,a)') 'md_simulation_gpu: N=', params%n, ' steps=', total_steps, &

@@ -608,6 +608,84 @@ class Engine:
         self._ck(self._lib.ljmd_heatflux_profile_read(self._h, C.byref(vis), C.byref(tot), C.byref(ms)))
         return {"tile_pairs_visited": vis.value, "tile_pairs_total": tot.value, "kernel_ms": ms.value}
 
+    # -- density modes of the resident system (include/ljmd.h: ljmd_rhok_*) -------------------
+    @staticmethod
+    def rhok_select_modes(n2_max: int, per_shell: int) -> np.ndarray:
+        """ljmd_rhok_select_modes -> modes[n_modes, 3] (int32): the half-space triples with 1 <= |n|^2 <= n2_max by
+        shell, at most per_shell of each shell, evenly spaced in lexicographic order.  Host code: needs no engine."""
+        lib = _lib.load()
+        count = C.c_int32()
+        rc = lib.ljmd_rhok_select_modes(int(n2_max), int(per_shell), 0, None, C.byref(count))
+        if rc != _lib.LJMD_OK and count.value <= 0:
+            _lib.check(rc)
+        modes = np.empty((max(count.value, 1), 3), dtype=np.int32)
+        _lib.check(lib.ljmd_rhok_select_modes(int(n2_max), int(per_shell), count.value,
+                                              modes.ctypes.data_as(_lib.c_int32_p), C.byref(count)))
+        return modes[:count.value].copy()
+
+    def rhok_configure(self, modes, max_snapshots: int) -> None:
+        """ljmd_rhok_configure: the mode list (integer triples [n_modes, 3], k = 2 pi n / L) and room for max_snapshots
+        snapshots of rho_k on the device; max_snapshots = 0 switches the feature off.  The series starts empty.
+        One-rank engines only."""
+        if isinstance(max_snapshots, bool) or not isinstance(max_snapshots, (int, np.integer)):
+            raise TypeError(f"rhok_configure: max_snapshots must be an integer, got {max_snapshots!r}")
+        m = np.asarray(modes if modes is not None else np.zeros((0, 3)))
+        if m.size and not np.issubdtype(m.dtype, np.integer):
+            raise TypeError("rhok_configure: modes must be integers")
+        if m.ndim != 2 or m.shape[1] != 3:
+            raise ValueError(f"rhok_configure: modes must have shape [n_modes, 3], got {m.shape}")
+        if m.size and np.abs(m).max() > np.iinfo(np.int32).max:
+            raise ValueError("rhok_configure: modes must lie within the int32 range")
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        self._ck(self._lib.ljmd_rhok_configure(self._h, m.shape[0], m.ctypes.data_as(_lib.c_int32_p) if m.size else None,
+                                               int(max_snapshots)))
+        self._rhok_modes = m.shape[0] if int(max_snapshots) > 0 else 0
+
+    def rhok_accumulate(self) -> None:
+        """appends rho_k of the positions resident now to the series (stream-ordered: no host wait)"""
+        self._ck(self._lib.ljmd_rhok_accumulate(self._h))
+
+    def _rhok_count(self) -> int:
+        """snapshots in the series (ljmd_rhok_read_exact without a buffer); raises as the reads do"""
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_rhok_read_exact(self._h, None, C.byref(snaps)))
+        return snaps.value
+
+    def rhok_read(self) -> np.ndarray:
+        """-> rho[n_snapshots, n_modes] complex: sum_j (cos k.r_j + i sin k.r_j), each part one rounding of its exact
+        integer; nothing is cleared."""
+        n, m = max(self._rhok_count(), 1), max(getattr(self, "_rhok_modes", 0), 1)
+        rho = np.empty((n, m, 2), dtype=np.float64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_rhok_read(self._h, rho.ctypes.data_as(c_double_p), C.byref(snaps)))
+        return rho[:snaps.value].copy().view(np.complex128)[..., 0]
+
+    def rhok_read_exact(self, raw: bool = False):
+        """-> sums[n_snapshots, n_modes, 2]: the exact integer sums of Q(cos) and Q(sin), Q(t) = RNE(t 2^64), as Python
+        ints in an object array -- or, raw=True, the library's int64 words [n_snapshots, n_modes, 2, 3] (three
+        little-endian limbs of a signed 192-bit integer)."""
+        m = max(getattr(self, "_rhok_modes", 0), 1)
+        words = np.empty((max(self._rhok_count(), 1), m, 2, 3), dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_rhok_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        words = words[:snaps.value].copy()
+        if raw:
+            return words
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:3], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums
+
+    def rhok_reset(self) -> None:
+        self._ck(self._lib.ljmd_rhok_reset(self._h))
+
+    def rhok_profile(self) -> dict:
+        """ljmd_rhok_profile_read for the most recent rhok_accumulate -> {'kernel_ms'}"""
+        ms = C.c_double()
+        self._ck(self._lib.ljmd_rhok_profile_read(self._h, C.byref(ms)))
+        return {"kernel_ms": ms.value}
+
     # -- measurement -----------------------------------------------------------
     def profile_enable(self, on: bool = True) -> None:
         self._ck(self._lib.ljmd_profile_enable(self._h, 1 if on else 0))
