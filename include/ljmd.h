@@ -1079,6 +1079,56 @@ int ljmd_batch_vanhove_read(ljmd_batch_t *h, uint64_t *hist /* [B][max_lag+1][nb
 int ljmd_batch_vanhove_read_exact(ljmd_batch_t *h, uint64_t *hist, int64_t *words /* [B][2][max_lag+1][3]: S2 then S4 */,
                                   int64_t *counts, int64_t *n_snapshots);
 int ljmd_batch_vanhove_reset(ljmd_batch_t *h);
+/*
+ * Collective density modes rho_k of every replica, a series of snapshots on the device (ljmd_batch_rhok_*): per replica,
+ * integer for integer, what ljmd_rhok_* above records for one system -- the ensemble whose averaged S(k) and F(k, tau)
+ * have an error bar (analysis.static_structure_factor_ensemble, analysis.intermediate_scattering_ensemble).
+ *
+ * Definition.  One list of modes is shared by the handle.  Per replica b one snapshot is, per mode of the list in list
+ * order, exactly the two signed 192-bit integers Re then Im of ljmd_rhok_* above, for that replica's own n_b and L_b and
+ * its resident wrapped r (what ljmd_batch_get_state returns as r): the arithmetic of a term, Q(t) = RNE(t 2^64), the
+ * range rule, the symmetries and the limb layout are those of that comment; 48 bytes per mode.  The integers depend on
+ * the replica's particle set and the mode alone: not on B, the replica's slot, the other replicas, launch grouping, group
+ * streams, precision mode, the order of the particles or the rest of the list.  The series is sample-major like the
+ * scalars of ljmd_batch_steps: words[snapshot][B][n_modes][2][3] and rho[snapshot][B][n_modes][2], rho = (R(Re), R(Im))
+ * with R(x) = RNE(x) 2^-64, the one rounding of ljmd_rhok_read.
+ * configure: 0 <= max_snapshots <= LJMD_BATCH_RHOK_MAX_SNAPSHOTS, every >= 0; max_snapshots = 0 switches the feature off
+ * and frees it, whatever the mode arguments; otherwise the mode rules of ljmd_rhok_configure (1 <= n_modes <=
+ * LJMD_RHOK_MAX_MODES triples of |n_a| <= LJMD_RHOK_MAX_INDEX, (0, 0, 0), negatives and duplicates included; the list
+ * of ljmd_rhok_select_modes is the drivers') and max_snapshots * B * n_modes <= LJMD_BATCH_RHOK_MAX_ENTRIES; copies the
+ * list to the device, allocates and zeroes 48 B n_modes max_snapshots bytes and a sticky range word per replica; calling
+ * it again reconfigures and zeroes.  A failed guard returns LJMD_ERR_INVALID_ARG and leaves the earlier configuration in
+ * place; a failed allocation LJMD_ERR_ALLOC with the feature off.  ljmd_batch_set_state, the other setters, the other
+ * five observables' calls and ljmd_batch_prepare leave configuration and series alone, and it leaves theirs alone; the
+ * warm-up of ljmd_batch_prepare takes no snapshot.
+ * accumulate: appends one snapshot of every replica, stream-ordered (no host wait).  LJMD_ERR_STATE before configure,
+ * before ljmd_batch_set_state, on a poisoned handle, and then when the series is full, before anything is launched.  It
+ * needs no accelerations, reads r and writes only its own buffers.
+ * every > 0: ljmd_batch_steps appends the state after steps every, 2 every, ... of each call; its nsteps must then be a
+ * multiple of every (LJMD_ERR_INVALID_ARG), and a call whose snapshots do not all fit the series is refused with
+ * LJMD_ERR_STATE, both before anything is launched; the density modes launch of a group, one per snapshot, is the last of
+ * a step.  r, ru, v, a, the sampled scalars and the other five observables stay bitwise what they are without the
+ * feature; ljmd_batch_profile_read counts the new launches and their time.  A call that fails half-way (a poisoned
+ * handle) leaves the snapshot count where it was.  Off: no launch, no allocation, nothing else changes.
+ * read_exact / read: wait for the device; the n snapshots taken since configure / reset, and n -- any pointer may be
+ * NULL; they clear nothing, and a poisoned handle may still be read.  While any replica's sticky word is set they return
+ * LJMD_ERR_RANGE, the message naming the lowest such replica ("replica <b>"), until ljmd_batch_rhok_reset; the handle is
+ * not poisoned and stepping goes on.  read_exact has then filled `words` all the same (a term that was not finite
+ * entered as zeros; the other replicas' rows are whole) and left n_snapshots alone; read has written nothing.  reset:
+ * empties the series and clears the words.
+ * profile_read, for the most recent ljmd_batch_rhok_accumulate (zero before the first): the time of its launches from HIP
+ * events; the pointer may be NULL; waits for the device.
+ * accumulate, read_exact, read, reset and profile_read return LJMD_ERR_STATE before configure.
+ */
+#define LJMD_BATCH_RHOK_MAX_SNAPSHOTS 262144
+#define LJMD_BATCH_RHOK_MAX_ENTRIES (1 << 24)   /* max_snapshots * B * n_modes: 805 MB of series */
+int ljmd_batch_rhok_configure(ljmd_batch_t *h, int32_t n_modes, const int32_t *modes /* [n_modes][3] */, int32_t max_snapshots,
+                              int32_t every);
+int ljmd_batch_rhok_accumulate(ljmd_batch_t *h);
+int ljmd_batch_rhok_read_exact(ljmd_batch_t *h, int64_t *words /* [n][B][n_modes][2][3]: Re then Im */, int64_t *n_snapshots);
+int ljmd_batch_rhok_read(ljmd_batch_t *h, double *rho /* [n][B][n_modes][2] */, int64_t *n_snapshots);
+int ljmd_batch_rhok_reset(ljmd_batch_t *h);
+int ljmd_batch_rhok_profile_read(ljmd_batch_t *h, double *kernel_ms);
 
 /*
  * Independent initial configurations on the device (ljmd_batch_prepare): per replica b, with n = n_b, L = L_b and k the

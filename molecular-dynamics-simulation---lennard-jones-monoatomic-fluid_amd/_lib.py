@@ -188,6 +188,12 @@ PROTOTYPES = {
     "ljmd_batch_vanhove_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_double_p, c_double_p, c_int64_p, c_int64_p]),
     "ljmd_batch_vanhove_read_exact": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p, c_int64_p, c_int64_p]),
     "ljmd_batch_vanhove_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_rhok_configure": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_int32]),
+    "ljmd_batch_rhok_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_rhok_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ljmd_batch_rhok_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
+    "ljmd_batch_rhok_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_batch_rhok_profile_read": (C.c_int, [C.c_void_p, c_double_p]),
     "ljmd_batch_prepare": (C.c_int, [C.c_void_p, c_int32_p, c_double_p, C.c_int32, c_double_p, c_double_p]),
     "ljmd_tcf_from_exact": (C.c_int, [c_int64_p, C.c_int32, C.c_int64, c_double_p]),
 }
@@ -211,6 +217,8 @@ RHOK_MAX_SNAPSHOTS = 262144
 RHOK_MAX_ENTRIES = 1 << 24
 BATCH_STRESS_MAX_SNAPSHOTS = 262144
 BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
+BATCH_RHOK_MAX_SNAPSHOTS = 262144
+BATCH_RHOK_MAX_ENTRIES = 1 << 24
 
 _lib = None
 

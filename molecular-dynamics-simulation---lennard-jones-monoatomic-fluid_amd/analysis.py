@@ -240,6 +240,62 @@ def intermediate_scattering(rho, n: int, modes, max_lag=None, origin_stride: int
     return np.stack(rows)
 
 
+def _rhok_ensemble(rho, n, L, who: str):
+    """-> (rho [n_snap, B, n_modes] complex, n[B], L[B] or None, whether the replicas share one n and one L)"""
+    rho = np.asarray(rho, dtype=np.complex128)
+    if rho.ndim != 3 or rho.shape[0] < 1 or rho.shape[1] < 1:
+        raise ValueError(f"{who}: rho must have shape (n_snap >= 1, B >= 1, n_modes), got {rho.shape}")
+    B = rho.shape[1]
+    n = np.asarray(n)
+    if n.shape not in ((), (B,)) or not np.issubdtype(n.dtype, np.integer):
+        raise ValueError(f"{who}: n must be an integer or {B} integers")
+    n = np.broadcast_to(n, (B,))
+    same = bool(np.all(n == n[0]))
+    if L is not None:
+        L = np.asarray(L, dtype=np.float64)
+        if L.shape not in ((), (B,)):
+            raise ValueError(f"{who}: L must be a number or {B} numbers")
+        L = np.broadcast_to(L, (B,))
+        same = same and bool(np.all(L == L[0]))
+    return rho, n, L, same
+
+
+def _replica_mean(per, same: bool):
+    """per [B, ...] -> (mean, stderr) over the replicas: sample standard deviation (ddof = 1) over sqrt(B), NaN with
+    B = 1; (None, None) when the replicas are not runs of one state point"""
+    if not same:
+        return None, None
+    mean = per.mean(axis=0)
+    if per.shape[0] < 2:
+        return mean, np.full_like(mean, np.nan)
+    return mean, per.std(axis=0, ddof=1) / np.sqrt(per.shape[0])
+
+
+def static_structure_factor_ensemble(rho, n, modes, L):
+    """rho [n_snap, B, n_modes]: the density modes of a batch of B replicas (BatchEngine.rhok_read), n and L a scalar or
+    one value per replica -> (per, mean, stderr).  per[b] = static_structure_factor(rho[:, b], n_b, modes, L_b), the tuple
+    (k, S, stderr over the snapshots, n_modes_of) of that function.  For replicas of one n and one L, mean[n_shells] is
+    the mean of S over the replicas and stderr[n_shells] its standard error, the sample standard deviation (ddof = 1)
+    over sqrt(B) (NaN with B = 1): the replicas are taken as independent runs of one state point, so the error falls as
+    1 / sqrt(B).  Otherwise mean and stderr are None (k differs from replica to replica)."""
+    rho, n, L, same = _rhok_ensemble(rho, n, L, "static_structure_factor_ensemble")
+    per = [static_structure_factor(rho[:, b], int(n[b]), modes, float(L[b])) for b in range(rho.shape[1])]
+    mean, err = _replica_mean(np.stack([p[1] for p in per]), same)
+    return per, mean, err
+
+
+def intermediate_scattering_ensemble(rho, n, modes, max_lag=None, origin_stride: int = 1):
+    """rho [n_snap, B, n_modes] (BatchEngine.rhok_read), n a scalar or one value per replica -> (per, mean, stderr).
+    per[b] = intermediate_scattering(rho[:, b], n_b, modes, max_lag, origin_stride), stacked to [B, n_shells,
+    max_lag + 1].  For replicas of one n, mean[n_shells, max_lag + 1] and stderr are the mean over the replicas and its
+    standard error as in static_structure_factor_ensemble; otherwise None.  (F is a function of the shell and the lag in
+    snapshots: replicas of one n and different L or dt are averaged only if the caller means that.)"""
+    rho, n, _L, same = _rhok_ensemble(rho, n, None, "intermediate_scattering_ensemble")
+    per = np.stack([intermediate_scattering(rho[:, b], int(n[b]), modes, max_lag, origin_stride) for b in range(rho.shape[1])])
+    mean, err = _replica_mean(per, same)
+    return per, mean, err
+
+
 # -- van Hove self-correlation (Engine.vanhove_read: hist[max_lag + 1, nbins + 1] with the overflow column last) --------
 def _vanhove_rows(hist, counts, n: int):
     """-> (inside [rows, nbins] float64, overflow fraction [rows], 1 / (n count) [rows], 0 where count == 0)"""

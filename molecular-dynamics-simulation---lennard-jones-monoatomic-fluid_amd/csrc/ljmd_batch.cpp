@@ -4,7 +4,8 @@
 // loop and the combination of the per-replica step records, in the fp64 mode and in the reproducible mode (exact integer
 // records, a sticky range flag per replica: ljmd_batch_fixed.hip).  The accumulators the step loop serves are
 // ljmd_batch_rdf.cpp (g(r)), ljmd_batch_tcf.cpp (MSD / VACF) and, through the handle alone, ljmd_stress_batch.cpp (the
-// pressure tensor), ljmd_heatflux_batch.cpp (the heat flux) and ljmd_vanhove_batch.cpp (the van Hove function);
+// pressure tensor), ljmd_heatflux_batch.cpp (the heat flux), ljmd_vanhove_batch.cpp (the van Hove function) and
+// ljmd_rhok_batch.cpp (the density modes);
 // ljmd_batch_host.h is what these files share.
 #include "ljmd_batch_host.h"
 
@@ -19,6 +20,7 @@ int ljmdb::enter(ljmd_batch *h, const char *who, unsigned need)
     if ((need & kNeedStress) && h->stress.max_snapshots == 0) return state("call ljmd_batch_stress_configure first");
     if ((need & kNeedHeatflux) && h->heatflux.max_snapshots == 0) return state("call ljmd_batch_heatflux_configure first");
     if ((need & kNeedVanhove) && h->vanhove.max_lag == 0) return state("call ljmd_batch_vanhove_configure first");
+    if ((need & kNeedRhok) && h->rhok.max_snapshots == 0) return state("call ljmd_batch_rhok_configure first");
     if ((need & kNeedState) && !h->have_state) return state("no state has been set");
     if ((need & kNeedAccel) && !h->have_accel)
         return state("no valid accelerations; call ljmd_batch_compute_forces or ljmd_batch_set_accel first");
@@ -386,6 +388,7 @@ void ljmd_batch_destroy(ljmd_batch_t *h)
     if (h->stress.release) h->stress.release(h);
     if (h->heatflux.release) h->heatflux.release(h);
     if (h->vanhove.release) h->vanhove.release(h);
+    if (h->rhok.release) h->rhok.release(h);
     for (hipEvent_t e : h->ev)
         if (e) (void)hipEventDestroy(e);
     if (h->fork) (void)hipEventDestroy(h->fork);

@@ -2,8 +2,9 @@
 // ljmd_batch_rdf.cpp: g(r); ljmd_batch_origins.cpp: the one core of the time-origin observables, driven by the
 // descriptors of ljmd_batch_tcf.cpp: MSD / VACF, and ljmd_vanhove_batch.cpp: van Hove; ljmd_batch_series.cpp: the one
 // core of the series observables, driven by the descriptors of ljmd_stress_batch.cpp: pressure tensor, and
-// ljmd_heatflux_batch.cpp: heat flux): the handle, the entry guard, the poison and allocation helpers, and the form in
-// which the step loop sees an accumulator.  Host code only; the kernels' side is ljmd_batch.h.
+// ljmd_heatflux_batch.cpp: heat flux; ljmd_rhok_batch.cpp: the density modes, a core of its own): the handle, the entry
+// guard, the poison and allocation helpers, and the form in which the step loop sees an accumulator.  Host code only; the
+// kernels' side is ljmd_batch.h.
 #ifndef LJMD_BATCH_HOST_H
 #define LJMD_BATCH_HOST_H
 
@@ -97,6 +98,22 @@ struct BatchOrigins {
 using BatchTcf = BatchOrigins;
 using BatchVanhove = BatchOrigins;
 
+// the density modes rho_k (ljmd_rhok_batch.cpp, a core of its own: the snapshot's width 6 n_modes is set at run time):
+// off while max_snapshots == 0, and every is 0 then.  acc and release (default-constructed: nothing is called) are how
+// the step loop and ljmd_batch_destroy reach the file, which is not linked everywhere
+struct BatchRhok {
+    int32_t max_snapshots = 0, every = 0, n_modes = 0;
+    int waves = 0;                    // waves of a workgroup of the kernel (LJMD_BATCH_RHOK_WAVES; else kBatchRhokWaves)
+    int64_t count = 0;                // snapshots in the series
+    uint64_t *d_words = nullptr;      // [max_snapshots][B][n_modes][6] signed 192-bit: Re then Im
+    int32_t *d_modes = nullptr;       // [n_modes][3]
+    int32_t *d_range = nullptr;       // [B] sticky until ljmd_batch_rhok_reset
+    hipEvent_t ev[2] = {nullptr, nullptr};   // around the launches of the last ljmd_batch_rhok_accumulate
+    bool timed = false;
+    BatchAccumulator acc;
+    void (*release)(ljmd_batch *h) = nullptr;
+};
+
 }  // namespace ljmdb
 
 struct ljmd_batch {
@@ -128,6 +145,7 @@ struct ljmd_batch {
     ljmdb::BatchStress stress;
     ljmdb::BatchHeatflux heatflux;
     ljmdb::BatchVanhove vanhove;
+    ljmdb::BatchRhok rhok;
     std::string err;
 };
 
@@ -139,10 +157,11 @@ inline bool reproducible(const ljmd_batch *h) { return h->mode == LJMD_PRECISION
 inline double *plane(ljmd_batch *h, int which, int axis) { return h->d_state + ((size_t)which * 3 + axis) * h->total; }
 
 // What an entry point requires before it starts, checked in this order after the NULL handle: configured g(r),
-// configured MSD / VACF, configured pressure tensor, configured heat flux, configured van Hove, a state, valid
-// accelerations, no poison (LJMD_ERR_STATE each); kNeedDevice: the handle's device is then made current (ljmd_batch.cpp)
+// configured MSD / VACF, configured pressure tensor, configured heat flux, configured van Hove, configured density
+// modes, a state, valid accelerations, no poison (LJMD_ERR_STATE each); kNeedDevice: the handle's device is then made
+// current (ljmd_batch.cpp)
 enum BatchNeed : unsigned { kNeedRdf = 1, kNeedTcf = 2, kNeedState = 4, kNeedAccel = 8, kNeedSound = 16, kNeedDevice = 32,
-                         kNeedStress = 64, kNeedHeatflux = 128, kNeedVanhove = 256 };
+                         kNeedStress = 64, kNeedHeatflux = 128, kNeedVanhove = 256, kNeedRhok = 512 };
 int enter(ljmd_batch *h, const char *who, unsigned need);
 
 // fails the call as fail() does and poisons the handle: LJMD_ERR_STATE from the guarded calls until ljmd_batch_set_state
@@ -179,14 +198,15 @@ int host_alloc(const ljmd_batch *h, const char *who, F &&grow)
 
 BatchAccumulator rdf_accumulator(const ljmd_batch *h);    // ljmd_batch_rdf.cpp
 BatchAccumulator tcf_accumulator(const ljmd_batch *h);    // ljmd_batch_tcf.cpp
-using BatchAccumulators = std::array<BatchAccumulator, 5>;
-inline BatchAccumulators accumulators(const ljmd_batch *h)     // van Hove last: the earlier launch sequences are unchanged
+using BatchAccumulators = std::array<BatchAccumulator, 6>;
+inline BatchAccumulators accumulators(const ljmd_batch *h)     // the newest last: the earlier launch sequences are unchanged
 {
-    BatchAccumulator stress = h->stress.acc, heatflux = h->heatflux.acc, vanhove = h->vanhove.acc;
+    BatchAccumulator stress = h->stress.acc, heatflux = h->heatflux.acc, vanhove = h->vanhove.acc, rhok = h->rhok.acc;
     stress.every = h->stress.every;
     heatflux.every = h->heatflux.every;
     vanhove.every = h->vanhove.every;
-    return {rdf_accumulator(h), tcf_accumulator(h), stress, heatflux, vanhove};
+    rhok.every = h->rhok.every;
+    return {rdf_accumulator(h), tcf_accumulator(h), stress, heatflux, vanhove, rhok};
 }
 
 // one snapshot of the resident state outside ljmd_batch_steps, on the handle's stream (ljmd_batch_*_accumulate)

@@ -122,6 +122,7 @@ Knobs read_knobs()
     k.multi_migrate_every = std::max(0, env_int("LJMD_MULTI_MIGRATE_EVERY", k.multi_migrate_every));
     k.multi_threads = flag("LJMD_MULTI_THREADS", k.multi_threads);
     k.batch_group_streams = !is("LJMD_BATCH_GROUP_STREAMS", "0");
+    k.batch_rhok_waves = env_int("LJMD_BATCH_RHOK_WAVES", k.batch_rhok_waves);
     return k;
 }
 

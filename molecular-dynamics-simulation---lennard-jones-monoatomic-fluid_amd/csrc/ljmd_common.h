@@ -139,6 +139,8 @@ struct Knobs {
     int multi_migrate_every = 2000;         // LJMD_MULTI_MIGRATE_EVERY: steps between two ownership migrations (0 = never)
     bool multi_threads = true;              // LJMD_MULTI_THREADS: one host thread per rank for the step loop
     bool batch_group_streams = true;        // LJMD_BATCH_GROUP_STREAMS=0: the batch engine's groups one after another
+    int batch_rhok_waves = 0;               // LJMD_BATCH_RHOK_WAVES: waves per workgroup of the batch density modes kernel
+                                            // (2, 4, 8; else the built-in choice: tools/batch_rhok_rate.py)
 };
 Knobs read_knobs();
 

@@ -131,16 +131,18 @@ extern "C" int ljmd_batch_prepare(ljmd_batch_t *h, const int32_t *seeds, const d
     // e: the warm-up on the step path, the accumulators' intervals set aside so that it takes no snapshot; ru <- r
     if (warmup_steps > 0) {
         const int32_t rdf_every = h->rdf.every, tcf_every = h->tcf.every, stress_every = h->stress.every,
-                      heatflux_every = h->heatflux.every;
+                      heatflux_every = h->heatflux.every, rhok_every = h->rhok.every;
         h->rdf.every = 0;
         h->tcf.every = 0;
         h->stress.every = 0;
         h->heatflux.every = 0;
+        h->rhok.every = 0;
         const int rc_ = ljmd_batch_steps(h, warmup_steps, 1, nullptr, nullptr, nullptr, nullptr);
         h->rdf.every = rdf_every;
         h->tcf.every = tcf_every;
         h->stress.every = stress_every;
         h->heatflux.every = heatflux_every;
+        h->rhok.every = rhok_every;
         LJMD_TRY(rc_);
         LJMD_HIP(h, hipMemcpyAsync(plane(h, LJMD_RU, 0), plane(h, LJMD_R, 0), 3 * h->total * sizeof(double),
                                     hipMemcpyDeviceToDevice, h->stream));

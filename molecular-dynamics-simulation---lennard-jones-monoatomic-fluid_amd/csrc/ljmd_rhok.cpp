@@ -160,10 +160,7 @@ int rhok_read(RhokState *st, std::string *err, const char *who, const ResidentVi
         }
     }
     LJMD_TRY(rhok_fetch(st, err, who, v, rho ? w.data() : nullptr, n_snapshots));
-    for (size_t k = 0; rho && k < w.size() / 3; ++k) {
-        const uint64_t u[3] = {(uint64_t)w[3 * k], (uint64_t)w[3 * k + 1], (uint64_t)w[3 * k + 2]};
-        rho[k] = ljmdk::fixed_to_double(u);
-    }
+    if (rho) rhok_doubles(w.data(), w.size() / 3, rho);
     return LJMD_OK;
 }
 

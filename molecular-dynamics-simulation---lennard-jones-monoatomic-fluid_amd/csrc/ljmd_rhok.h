@@ -8,7 +8,10 @@
 #define LJMD_RHOK_H
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
+
+#include "ljmd_internal.h"
 
 namespace ljmdc {
 
@@ -77,6 +80,16 @@ inline bool rhok_fold_ok(const RhokFoldArgs &a)
 {
     return a.part && a.flag && a.row && a.range && a.n_modes >= 1 && a.n_modes <= kRhokMaxModes && a.pchunks >= 1 &&
            a.pchunks <= kRhokMaxChunks && a.mchunks == (a.n_modes + kRhokModeChunk - 1) / kRhokModeChunk;
+}
+
+// the doubles of ljmd_rhok_read and ljmd_batch_rhok_read: `count` signed 192-bit integers of three limbs each -> one
+// correctly rounded conversion of each
+inline void rhok_doubles(const int64_t *words, size_t count, double *rho)
+{
+    for (size_t k = 0; k < count; ++k) {
+        const uint64_t u[3] = {(uint64_t)words[3 * k], (uint64_t)words[3 * k + 1], (uint64_t)words[3 * k + 2]};
+        rho[k] = ljmdk::fixed_to_double(u);
+    }
 }
 
 hipError_t launch_rhok_terms(const RhokTermsArgs &a, hipStream_t s);

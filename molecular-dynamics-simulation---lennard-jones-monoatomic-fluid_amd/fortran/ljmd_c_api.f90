@@ -45,6 +45,8 @@ module ljmd_c_api
   public :: ljmd_batch_heatflux_read_exact, ljmd_batch_heatflux_reset
   public :: ljmd_batch_vanhove_configure, ljmd_batch_vanhove_accumulate, ljmd_batch_vanhove_read
   public :: ljmd_batch_vanhove_read_exact, ljmd_batch_vanhove_reset
+  public :: ljmd_batch_rhok_configure, ljmd_batch_rhok_accumulate, ljmd_batch_rhok_read, ljmd_batch_rhok_read_exact
+  public :: ljmd_batch_rhok_reset, ljmd_batch_rhok_profile_read
   public :: ljmd_batch_check, ljmd_batch_error_text
 
   integer(c_int), parameter, public :: LJMD_OK = 0
@@ -68,6 +70,8 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_INDEX = 1023
   integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_ENTRIES = 16777216
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_RHOK_MAX_SNAPSHOTS = 262144
+  integer(c_int32_t), parameter, public :: LJMD_BATCH_RHOK_MAX_ENTRIES = 16777216
 
   interface
     function ljmd_compute_lj_potential_energy(n, box_length, rc, rx, ry, rz, ax, ay, az, &
@@ -763,6 +767,50 @@ module ljmd_c_api
     function ljmd_batch_vanhove_reset(handle) bind(C, name="ljmd_batch_vanhove_reset") result(status)
       import :: c_int, c_ptr
       type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    ! density modes of every replica of a batch handle (ljmd.h: ljmd_batch_rhok_*); modes = c_loc of [3, n_modes] 32-bit
+    ! integers, rho = c_loc of [2, n_modes, B, n_snapshots] doubles (Re, Im), words = c_loc of
+    ! [3, 2, n_modes, B, n_snapshots] 64-bit words in Fortran order; c_null_ptr skips an output
+    function ljmd_batch_rhok_configure(handle, n_modes, modes, max_snapshots, every) &
+        bind(C, name="ljmd_batch_rhok_configure") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle, modes
+      integer(c_int32_t), value :: n_modes, max_snapshots, every
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rhok_accumulate(handle) bind(C, name="ljmd_batch_rhok_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rhok_read(handle, rho, n_snapshots) bind(C, name="ljmd_batch_rhok_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, rho
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rhok_read_exact(handle, words, n_snapshots) bind(C, name="ljmd_batch_rhok_read_exact") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rhok_reset(handle) bind(C, name="ljmd_batch_rhok_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_batch_rhok_profile_read(handle, kernel_ms) bind(C, name="ljmd_batch_rhok_profile_read") result(status)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: handle
+      real(c_double), intent(out) :: kernel_ms
       integer(c_int) :: status
     end function
 

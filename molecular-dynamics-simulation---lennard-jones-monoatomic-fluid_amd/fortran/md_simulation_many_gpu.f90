@@ -43,6 +43,13 @@
 ! LJMD_VANHOVE_ORIGIN_STRIDE-th of them (default 1) an origin, LJMD_VANHOVE_BINS bins (default 128) up to
 ! LJMD_VANHOVE_RMAX (default half of each run's box); outputs/run_NNNN/van_hove_gpu.dat is the file of md_simulation_gpu
 ! (md_run_outputs: write_van_hove_file); every other file stays byte-identical),
+! LJMD_RHOK_N2MAX (default 0 = off; > 0: the collective density modes rho_k of every run are recorded on the device,
+! ljmd_batch_rhok_*, at every sampling instant that writes an rva.dat record, for the one mode list
+! ljmd_rhok_select_modes gives: the half-space triples with |n|^2 <= LJMD_RHOK_N2MAX, at most LJMD_RHOK_PER_SHELL
+! (default 8) per shell, k = 2 pi n / L of the run's own box; outputs/run_NNNN/density_modes_gpu.dat and
+! structure_factor_gpu.dat and, with LJMD_RHOK_MAX_LAG > 0, intermediate_scattering_gpu.dat are the files of
+! md_simulation_gpu (md_run_outputs: write_density_modes_file, write_structure_factor_file,
+! write_intermediate_scattering_file); every other file stays byte-identical),
 ! LJMD_SEED_BASE (unset: the rv_init.dat files above are read; s >= 1: NO rv_init.dat is read -- run i is prepared on the
 ! device, ljmd_batch_prepare, with seed s + i - 1: the reference's FCC lattice, its generator's velocities, centre of
 ! mass removed, scaled to the target_total_energy of the run's own or the shared input file, then that file's
@@ -61,7 +68,9 @@ program md_simulation_many_gpu
   use lj_potential_energy, only: use_tail_corrections     ! the reference's compile-time switch (lj_potential_energy.f90:36)
   use md_stats,         only: run_statistics, stats_begin, stats_push, stats_mean_std, Q_T
   use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
-                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file
+                              write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file, &
+                              write_density_modes_file, write_structure_factor_file, write_intermediate_scattering_file, &
+                              density_mode_shells
   implicit none
 
   character(len=*), parameter :: runs_list = 'outputs/several_runs.txt'
@@ -114,6 +123,13 @@ program md_simulation_many_gpu
   real(c_double), allocatable, target :: vh_r2(:, :), vh_r4(:, :)           ! [vh_max_lag + 1, n_runs]
   integer(c_int64_t), allocatable, target :: vh_counts(:), vh_hist(:, :, :) ! [vh_max_lag + 1], [vh_bins + 1, vh_max_lag + 1, n_runs]
   integer(c_int64_t) :: vh_snapshots
+  integer :: rhok_n2max, rhok_per_shell, rhok_max_lag
+  integer(c_int32_t) :: rhok_n_modes
+  integer(c_int) :: rhok_status
+  integer(c_int32_t), allocatable, target :: rhok_modes(:, :)              ! [3, n_modes]
+  real(c_double), allocatable, target :: rhok_rho(:, :, :, :)              ! [2, n_modes, n_runs, snapshots]
+  real(c_double), allocatable :: rhok_times(:, :)                          ! [snapshots, n_runs]
+  integer(c_int64_t) :: rhok_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -175,6 +191,18 @@ program md_simulation_many_gpu
     read(env, *) vh_rmax_env
     vh_rmax_given = .true.
   end if
+  rhok_n2max = 0
+  call get_environment_variable('LJMD_RHOK_N2MAX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rhok_n2max
+  if (rhok_n2max < 0) stop 'md_simulation_many: LJMD_RHOK_N2MAX must be >= 0.'
+  rhok_per_shell = 8
+  call get_environment_variable('LJMD_RHOK_PER_SHELL', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rhok_per_shell
+  if (rhok_per_shell < 1) stop 'md_simulation_many: LJMD_RHOK_PER_SHELL must be >= 1.'
+  rhok_max_lag = 0
+  call get_environment_variable('LJMD_RHOK_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) rhok_max_lag
+  if (rhok_max_lag < 0) stop 'md_simulation_many: LJMD_RHOK_MAX_LAG must be >= 0.'
 
   seed_base = 0
   call get_environment_variable('LJMD_SEED_BASE', env, status=ios)
@@ -273,6 +301,23 @@ program md_simulation_many_gpu
                           'ljmd_batch_heatflux_configure')
     allocate(heatflux_times(n_snapshots_expected, n_runs))
   end if
+  if (rhok_n2max > 0) then
+    ! one mode list for all runs; one snapshot per sampling instant that writes an rva.dat record, taken by hand
+    if (n_snapshots_expected < 1) stop 'md_simulation_many: LJMD_RHOK_N2MAX needs at least one sampling instant.'
+    if (n_snapshots_expected > LJMD_BATCH_RHOK_MAX_SNAPSHOTS) &
+      stop 'md_simulation_many: more sampling instants than LJMD_BATCH_RHOK_MAX_SNAPSHOTS.'
+    rhok_status = ljmd_rhok_select_modes(int(rhok_n2max, c_int32_t), int(rhok_per_shell, c_int32_t), 0_c_int32_t, c_null_ptr, &
+                                         rhok_n_modes)
+    if (rhok_status == LJMD_OK .or. rhok_n_modes < 1) call ljmd_check(rhok_status, c_null_ptr, 'ljmd_rhok_select_modes')
+    if (rhok_n_modes > LJMD_RHOK_MAX_MODES) stop 'md_simulation_many: more modes than LJMD_RHOK_MAX_MODES: lower LJMD_RHOK_N2MAX.'
+    allocate(rhok_modes(3, rhok_n_modes))
+    call ljmd_check(ljmd_rhok_select_modes(int(rhok_n2max, c_int32_t), int(rhok_per_shell, c_int32_t), rhok_n_modes, &
+                                           c_loc(rhok_modes), rhok_n_modes), c_null_ptr, 'ljmd_rhok_select_modes')
+    call ljmd_batch_check(ljmd_batch_rhok_configure(batch, rhok_n_modes, c_loc(rhok_modes), &
+                                                    int(n_snapshots_expected, c_int32_t), 0_c_int32_t), batch, &
+                          'ljmd_batch_rhok_configure')
+    allocate(rhok_times(n_snapshots_expected, n_runs))
+  end if
   do i = 1, n_runs
     open(newunit=iu_rva(i), file=trim(run_dir(i)) // '/rva.dat', form='unformatted', status='replace', &
          action='write', iostat=ios)
@@ -311,6 +356,10 @@ program md_simulation_many_gpu
     if (heatflux_on) then
       call ljmd_batch_check(ljmd_batch_heatflux_accumulate(batch), batch, 'ljmd_batch_heatflux_accumulate')
       heatflux_times(num_samples, :) = time_run
+    end if
+    if (rhok_n2max > 0) then
+      call ljmd_batch_check(ljmd_batch_rhok_accumulate(batch), batch, 'ljmd_batch_rhok_accumulate')
+      rhok_times(num_samples, :) = time_run
     end if
     call ljmd_batch_check(ljmd_batch_get_state(batch, c_loc(rx), c_loc(ry), c_loc(rz), c_loc(ux), c_loc(uy), &
                                                c_loc(uz), c_loc(vx), c_loc(vy), c_loc(vz), c_loc(ax), c_loc(ay), &
@@ -358,6 +407,11 @@ program md_simulation_many_gpu
     call ljmd_batch_check(ljmd_batch_vanhove_read(batch, c_loc(vh_hist), c_loc(vh_r2), c_loc(vh_r4), c_loc(vh_counts), &
                                                   vh_snapshots), batch, 'ljmd_batch_vanhove_read')
   end if
+  if (rhok_n2max > 0) then
+    allocate(rhok_rho(2, rhok_n_modes, n_runs, max(num_samples, 1)))
+    call ljmd_batch_check(ljmd_batch_rhok_read(batch, c_loc(rhok_rho), rhok_snapshots), batch, 'ljmd_batch_rhok_read')
+    if (rhok_snapshots /= num_samples) stop 'md_simulation_many: the density mode series and the samples disagree.'
+  end if
   call ljmd_batch_destroy(batch)
   do i = 1, n_runs
     close(iu_out(i))
@@ -399,6 +453,11 @@ program md_simulation_many_gpu
     do i = 1, n_runs
       call write_van_hove_file(trim(run_dir(i)) // '/van_hove_gpu.dat', rparams(i)%n, vh_max_lag, vh_bins, vh_rmax(i), &
                                output_interval, rparams(i)%dt, vh_counts, vh_r2(:, i), vh_r4(:, i), vh_hist(:, :, i))
+    end do
+  end if
+  if (rhok_n2max > 0) then
+    do i = 1, n_runs
+      call write_density_modes(i)
     end do
   end if
   if (any_own) then
@@ -513,6 +572,42 @@ contains
     call write_heat_flux_acf_file(trim(run_dir(irun)) // '/heat_flux_acf_gpu.dat', lags, output_interval, rparams(irun)%dt, &
                                   rparams(irun)%volume, mean_temp, acf)
   end subroutine write_heat_flux
+
+  ! run i's density_modes_gpu.dat, structure_factor_gpu.dat and, with LJMD_RHOK_MAX_LAG > 0, intermediate_scattering_gpu.dat:
+  ! what md_simulation_gpu writes for one run (md_run_outputs), from the run's rows of the series
+  subroutine write_density_modes(irun)
+    integer, intent(in) :: irun
+    real(c_double), allocatable, target :: rho(:, :, :), re(:, :), im(:, :), zero(:, :), f(:, :), row(:)
+    integer, allocatable :: first(:)
+    integer :: ns, nm, lags, shells, sh, cnt
+    ns = int(num_samples)
+    nm = int(rhok_n_modes)
+    allocate(rho(2, nm, ns))
+    rho = rhok_rho(:, :, irun, 1:ns)
+    call write_density_modes_file(trim(run_dir(irun)) // '/density_modes_gpu.dat', nm, rhok_modes, ns, rhok_times(1:ns, irun), rho)
+    call write_structure_factor_file(trim(run_dir(irun)) // '/structure_factor_gpu.dat', rparams(irun)%n, &
+                                     rparams(irun)%box_length, nm, rhok_modes, ns, rho)
+    if (rhok_max_lag <= 0 .or. ns < 2) return
+    ! per shell its modes as the particles and (Re, Im, 0) as the velocity: [modes of the shell, snapshots] each
+    allocate(first(nm + 1))
+    call density_mode_shells(nm, rhok_modes, shells, first)
+    lags = min(rhok_max_lag, ns - 1)
+    allocate(f(0:lags, shells), row(0:lags))
+    do sh = 1, shells
+      cnt = first(sh + 1) - first(sh)
+      allocate(re(cnt, ns), im(cnt, ns), zero(cnt, ns))
+      re = rho(1, first(sh):first(sh + 1) - 1, 1:ns)
+      im = rho(2, first(sh):first(sh + 1) - 1, 1:ns)
+      zero = 0.d0
+      call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(ns, c_int32_t), int(cnt, c_int32_t), c_loc(re), c_loc(im), &
+                                               c_loc(zero), int(lags, c_int32_t), 1_c_int32_t, c_loc(row)), c_null_ptr, &
+                      'ljmd_time_origin_average')
+      f(:, sh) = row / dble(rparams(irun)%n)
+      deallocate(re, im, zero)
+    end do
+    call write_intermediate_scattering_file(trim(run_dir(irun)) // '/intermediate_scattering_gpu.dat', shells, lags, &
+                                            output_interval, rparams(irun)%dt, f)
+  end subroutine write_density_modes
 
   ! LJMD_SEED_BASE: every run's initial configuration on the device (seed_base + i - 1, the run's target_total_energy,
   ! the shared warmup_steps), then each run's rv_init_gpu.dat: the two records of rv_init.dat

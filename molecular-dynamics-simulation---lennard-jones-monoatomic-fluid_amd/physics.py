@@ -1166,6 +1166,74 @@ class BatchEngine:
     def vanhove_reset(self) -> None:
         self._ck(self._lib.ljmd_batch_vanhove_reset(self._h))
 
+    # -- density modes on the device (include/ljmd.h: ljmd_batch_rhok_*) ---------
+    def rhok_configure(self, modes, max_snapshots: int, every: int = 0) -> None:
+        """ljmd_batch_rhok_configure: one mode list for the handle (integer triples [n_modes, 3], k_b = 2 pi n / L_b;
+        Engine.rhok_select_modes gives the drivers' list) and room for max_snapshots snapshots of every replica's rho_k
+        on the device; every > 0: steps() appends the state after steps every, 2 every, ... by itself.  max_snapshots = 0
+        switches the feature off.  The series starts empty."""
+        for name, val in (("max_snapshots", max_snapshots), ("every", every)):
+            if isinstance(val, bool) or not isinstance(val, (int, np.integer)):
+                raise TypeError(f"rhok_configure: {name} must be an integer, got {val!r}")
+            if not -2 ** 31 <= int(val) <= 2 ** 31 - 1:
+                raise ValueError(f"rhok_configure: {name} must lie within the int32 range")
+        m = np.asarray(modes if modes is not None else np.zeros((0, 3)))
+        if m.size and not np.issubdtype(m.dtype, np.integer):
+            raise TypeError("rhok_configure: modes must be integers")
+        if m.ndim != 2 or m.shape[1] != 3:
+            raise ValueError(f"rhok_configure: modes must have shape [n_modes, 3], got {m.shape}")
+        if m.size and np.abs(m).max() > np.iinfo(np.int32).max:
+            raise ValueError("rhok_configure: modes must lie within the int32 range")
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        self._ck(self._lib.ljmd_batch_rhok_configure(self._h, m.shape[0], m.ctypes.data_as(_lib.c_int32_p) if m.size else None,
+                                                     int(max_snapshots), int(every)))
+        self._rhok_modes = m.shape[0] if int(max_snapshots) > 0 else 0
+
+    def rhok_accumulate(self) -> None:
+        """appends rho_k of every replica's resident positions to the series (no host wait)"""
+        self._ck(self._lib.ljmd_batch_rhok_accumulate(self._h))
+
+    def _rhok_count(self) -> int:
+        """snapshots in the series (ljmd_batch_rhok_read_exact without a buffer); raises as the reads do"""
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_rhok_read_exact(self._h, None, C.byref(snaps)))
+        return snaps.value
+
+    def rhok_read(self) -> np.ndarray:
+        """-> rho[n_snapshots, B, n_modes] complex: sum_j (cos k.r_j + i sin k.r_j) per replica, each part one rounding
+        of its exact integer; nothing is cleared"""
+        n, m = max(self._rhok_count(), 1), max(getattr(self, "_rhok_modes", 0), 1)
+        rho = np.empty((n, self.n_replicas, m, 2), dtype=np.float64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_rhok_read(self._h, _ptr(rho), C.byref(snaps)))
+        return rho[:snaps.value].copy().view(np.complex128)[..., 0]
+
+    def rhok_read_exact(self, raw: bool = False):
+        """-> sums[n_snapshots, B, n_modes, 2]: the exact integer sums of Q(cos) and Q(sin), Q(t) = RNE(t 2^64), as
+        Python ints in an object array -- or, raw=True, the library's int64 words [n_snapshots, B, n_modes, 2, 3] (three
+        little-endian limbs of a signed 192-bit integer)"""
+        m = max(getattr(self, "_rhok_modes", 0), 1)
+        words = np.empty((max(self._rhok_count(), 1), self.n_replicas, m, 2, 3), dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_batch_rhok_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        words = words[:snaps.value].copy()
+        if raw:
+            return words
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:4], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums
+
+    def rhok_reset(self) -> None:
+        self._ck(self._lib.ljmd_batch_rhok_reset(self._h))
+
+    def rhok_profile(self) -> dict:
+        """ljmd_batch_rhok_profile_read for the most recent rhok_accumulate -> {'kernel_ms'}"""
+        ms = C.c_double()
+        self._ck(self._lib.ljmd_batch_rhok_profile_read(self._h, C.byref(ms)))
+        return {"kernel_ms": ms.value}
+
     @staticmethod
     def per_replica(params_list, device: int = 0,
                     precision_mode: int = _lib.PRECISION_FP64) -> "PerReplicaBatchEngine":
