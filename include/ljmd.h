@@ -754,6 +754,71 @@ int ljmd_rhok_read(ljmd_t *h, double *rho /* [n][n_modes][2] */, int64_t *n_snap
 int ljmd_rhok_reset(ljmd_t *h);
 int ljmd_rhok_profile_read(ljmd_t *h, double *kernel_ms);
 
+/*
+ * Collective current modes of the resident system, j_k(t) = sum_j v_j(t) exp(i k . r_j(t)) with k = (2 pi / L) n for a
+ * list of integer triples n, one snapshot per call, recorded where r and v live (ljmd_current_*): no snapshot leaves the
+ * device.  The projections of j_k along and across k give the longitudinal and transverse current correlation functions
+ * C_L(k, tau) and C_T(k, tau) and the wave-vector dependent shear viscosity eta(k) on the host
+ * (analysis.current_correlations, analysis.current_equal_time, analysis.transverse_viscosity).  One-rank engines only
+ * (ljmd_create with n_ranks = 1); n <= 2^23.  Independent of ljmd_rhok_*: either, both or neither may be configured.
+ *
+ * Definition.  One snapshot is, per mode of the list in list order, six signed 192-bit integers in the order x Re, x Im,
+ * y Re, y Im, z Re, z Im, each three int64 limbs, least significant first: words[snapshot][n_modes][3][2][3], 144 bytes
+ * per mode.  Everything is fp64 with separate roundings, no fused multiply-add anywhere.  Per live particle and mode, with
+ * x, y, z and v_x, v_y, v_z the r and v that ljmd_get_state returns:
+ *     (C, S)      exactly the (C, S) of ljmd_rhok_* above for these positions and this mode
+ *     P_a = v_a * C ;  R_a = v_a * S                            (a = x, y, z; one product each, rounded once)
+ *     Re_a[m] += Q(P_a) ;  Im_a[m] += Q(R_a)                     with Q(t) = RNE(t 2^64), |Q| < 2^104
+ *   Range: the (particle, mode) term is out of range when C or S is not finite, or when any of the six products is not
+ *   finite or has magnitude >= 2^40; it then enters all six sums as zero and sets a sticky word.  An arithmetic flag:
+ *   nothing wraps, nothing faults.  Padding slots of the engine's layout are not particles: they add nothing and set no
+ *   flag.
+ *   Bound: with B the bound of the density modes' term above, P_a and R_a, as the numbers Q(.) 2^-64, are within
+ *   |v_a| (B + 2^-53 (1 + B)) + 2^-65 of the true v_a cos k.r and v_a sin k.r: |v_a| times B, one product rounding,
+ *   one quantisation.
+ *   Consequences, each exact: (1) mode -n has the same Re words and exactly negated Im words; (2) mode (0, 0, 0) has
+ *   Re_a = sum_j Q(v_a) and Im_a = 0, the total momentum with no padding slot counted; (3) with every velocity equal to
+ *   (1, -1, 2) the x words are the words of ljmd_rhok_* for the same positions and modes and the y words their negation
+ *   (a product by +-1 is exact and Q is odd); the z words are the sums of Q(2 C) and Q(2 S), exactly twice the words of
+ *   ljmd_rhok_* where every term is 0 or has magnitude >= 2^-12 -- t 2^64 is then an integer and Q(2 t) = 2 Q(t) -- and
+ *   within one unit per smaller term of twice them otherwise (RNE(2 x) = 2 RNE(x) only for x within 1/4 of an integer);
+ *   (4) the velocities are those ljmd_get_state returns as v, paired with its r.
+ *   Doubles: j[m][a] = (R(Re_a[m]), R(Im_a[m])) with R(x) = RNE(x) 2^-64, ONE rounding of each integer.
+ * The integers depend on the positions, the velocities and the mode list alone: not on slot order, re-sorts, grid shape,
+ * precision mode or knobs; a mode's words do not depend on the rest of the list.
+ * The mode list obeys the rules of ljmd_rhok_configure (LJMD_RHOK_MAX_MODES, LJMD_RHOK_MAX_INDEX; (0, 0, 0), negatives
+ * and duplicates included), and ljmd_rhok_select_modes gives the drivers' shell-wise list.
+ * configure: 1 <= max_snapshots <= LJMD_CURRENT_MAX_SNAPSHOTS, max_snapshots * n_modes <= LJMD_CURRENT_MAX_ENTRIES and
+ * n <= 2^23; copies the list to the device, allocates and zeroes the series there; calling it again reconfigures and
+ * zeroes; max_snapshots = 0 switches the feature off and frees everything, whatever the other arguments.  A failed guard
+ * returns LJMD_ERR_INVALID_ARG and leaves the earlier configuration in place; a failed allocation LJMD_ERR_ALLOC with the
+ * feature off.  Works with or without a state.  On a rank engine (n_ranks > 1) or a multi-device handle configure with
+ * max_snapshots > 0 returns LJMD_ERR_INVALID_ARG ("... n_ranks = <G>: a rank holds only its own particles ..."), and the
+ * other calls LJMD_ERR_STATE ("not configured").  The setters, ljmd_migrate and the other six observables leave
+ * configuration and series alone, and it leaves theirs alone.
+ * accumulate: appends one snapshot, stream-ordered on the engine's stream behind everything enqueued so far, no host
+ * wait.  It needs a state but no accelerations: LJMD_ERR_STATE before configure, without a state, on a poisoned handle
+ * and between ljmd_step_begin and ljmd_step_finish; then LJMD_ERR_STATE when the series is full, before anything is
+ * launched.  It reads the exchange buffer, the velocities and the slot permutation and writes only buffers of its own:
+ * r, ru, v, a, the step records, the other six observables and every later result stay bitwise what they are without
+ * the call.  Switched off it launches nothing, and no existing kernel knows of it.
+ * read_exact / read: wait for the device; words[n][n_modes][3][2][3] (read_exact) or j[n][n_modes][3][2] (read) for the
+ * n snapshots taken since configure / reset, and n -- any pointer may be NULL; they clear nothing.  While the sticky word
+ * is set they return LJMD_ERR_RANGE, until ljmd_current_reset; the handle is not poisoned and stepping is unaffected.
+ * reset: empties the series and clears the sticky word.
+ * profile_read, for the most recent accumulate (zero before the first): the time of its launches from HIP events; the
+ * pointer may be NULL; waits for the device.
+ * read_exact, read, reset and profile_read return LJMD_ERR_STATE before configure.
+ */
+#define LJMD_CURRENT_MAX_SNAPSHOTS 262144
+#define LJMD_CURRENT_MAX_ENTRIES (1 << 22)   /* max_snapshots * n_modes: 604 MB of series at 144 bytes per entry */
+int ljmd_current_configure(ljmd_t *h, int32_t n_modes, const int32_t *modes /* [n_modes][3] */, int32_t max_snapshots);
+int ljmd_current_accumulate(ljmd_t *h);
+int ljmd_current_read_exact(ljmd_t *h, int64_t *words /* [n][n_modes][3][2][3] */, int64_t *n_snapshots);
+int ljmd_current_read(ljmd_t *h, double *j /* [n][n_modes][3][2] */, int64_t *n_snapshots);
+int ljmd_current_reset(ljmd_t *h);
+int ljmd_current_profile_read(ljmd_t *h, double *kernel_ms);
+
 /* ---- batch engine: many independent small systems on one device ------------------------------------------------
  *
  * One ljmd_batch_t holds B replicas on one device -- the ensemble runs of the reference's run-many framework

@@ -164,6 +164,12 @@ PROTOTYPES = {
     "ljmd_rhok_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
     "ljmd_rhok_reset": (C.c_int, [C.c_void_p]),
     "ljmd_rhok_profile_read": (C.c_int, [C.c_void_p, c_double_p]),
+    "ljmd_current_configure": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32]),
+    "ljmd_current_accumulate": (C.c_int, [C.c_void_p]),
+    "ljmd_current_read_exact": (C.c_int, [C.c_void_p, c_int64_p, c_int64_p]),
+    "ljmd_current_read": (C.c_int, [C.c_void_p, c_double_p, c_int64_p]),
+    "ljmd_current_reset": (C.c_int, [C.c_void_p]),
+    "ljmd_current_profile_read": (C.c_int, [C.c_void_p, c_double_p]),
     "ljmd_batch_rdf_configure": (C.c_int, [C.c_void_p, C.c_int32, c_double_p, C.c_int32]),
     "ljmd_batch_rdf_accumulate": (C.c_int, [C.c_void_p]),
     "ljmd_batch_rdf_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), c_int64_p]),
@@ -215,6 +221,8 @@ RHOK_MAX_MODES = 4096
 RHOK_MAX_INDEX = 1023
 RHOK_MAX_SNAPSHOTS = 262144
 RHOK_MAX_ENTRIES = 1 << 24
+CURRENT_MAX_SNAPSHOTS = 262144
+CURRENT_MAX_ENTRIES = 1 << 22
 BATCH_STRESS_MAX_SNAPSHOTS = 262144
 BATCH_HEATFLUX_MAX_SNAPSHOTS = 262144
 BATCH_RHOK_MAX_SNAPSHOTS = 262144

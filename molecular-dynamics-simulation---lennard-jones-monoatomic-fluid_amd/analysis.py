@@ -296,6 +296,114 @@ def intermediate_scattering_ensemble(rho, n, modes, max_lag=None, origin_stride:
     return per, mean, err
 
 
+# -- collective current modes (Engine.current_read: j[n_snap, n_modes, 3] complex, modes[n_modes, 3] integer triples) ----
+def _current_series(j, n, modes, who: str):
+    """-> (j_L [n_snap, n_modes] complex, j_T [n_snap, n_modes, 3] complex, |n|^2 [n_shells], members) with the shell of
+    |n|^2 = 0 left out: its direction is undefined.  k^ = n / |n|, j_L = k^ . j, j_T = j - k^ j_L."""
+    j = np.asarray(j, dtype=np.complex128)
+    shells, members = rhok_shells(modes)
+    modes = np.asarray(modes)
+    if j.ndim != 3 or j.shape[0] < 1 or j.shape[1] != modes.shape[0] or j.shape[2] != 3:
+        raise ValueError(f"{who}: j must have shape (n_snap >= 1, n_modes = {modes.shape[0]}, 3), got {j.shape}")
+    if n < 1:
+        raise ValueError(f"{who}: n >= 1")
+    keep = [i for i, s in enumerate(shells) if s > 0]
+    if not keep:
+        raise ValueError(f"{who}: no mode with |n|^2 > 0")
+    nd = modes.astype(np.float64)
+    norm = np.sqrt((nd * nd).sum(axis=1))
+    khat = np.zeros_like(nd)
+    np.divide(nd, norm[:, None], out=khat, where=norm[:, None] > 0)
+    j_L = (j * khat[None, :, :]).sum(axis=2)
+    j_T = j - khat[None, :, :] * j_L[:, :, None]
+    return j_L, j_T, shells[keep], [members[i] for i in keep]
+
+
+def _independent_modes(modes, member):
+    """the members of a shell grouped so that a mode, its conjugate -n and their duplicates form one group: j_-k = j_k*
+    carries nothing that j_k does not"""
+    groups = {}
+    for m in member:
+        t = tuple(int(c) for c in np.asarray(modes)[m])
+        neg = tuple(-c for c in t)
+        groups.setdefault(max(t, neg), []).append(m)
+    return list(groups.values())
+
+
+def current_equal_time(j, n: int, modes, L: float):
+    """j [n_snap, n_modes, 3]: a series of current modes of n particles in a box of side L -> (k, C_L0, C_T0, stderr_L,
+    stderr_T, n_modes_of), one entry per shell of equal |n|^2 > 0 in ascending order, the layout of
+    static_structure_factor: k = 2 pi sqrt(|n|^2) / L, C_L0 = <|j_L|^2> / n and C_T0 = 1/2 <|j_T|^2> / n over the snapshots
+    and the shell's modes (both are the mean square of one Cartesian velocity component in equilibrium), and the
+    standard errors of these means: over the snapshots, as static_structure_factor has it, or with ONE snapshot over the
+    shell's independent modes, a mode, its conjugate -n and their duplicates counting once (sample standard deviation,
+    ddof = 1, over the square root of their number; NaN with fewer than two)."""
+    j_L, j_T, shells, members = _current_series(j, n, modes, "current_equal_time")
+    if not L > 0.0:
+        raise ValueError("current_equal_time: n >= 1 and L > 0")
+    n_snap = j_L.shape[0]
+    val_L = (j_L.real ** 2 + j_L.imag ** 2) / n                              # [n_snap, n_modes]
+    val_T = 0.5 * (j_T.real ** 2 + j_T.imag ** 2).sum(axis=2) / n
+    C_L0 = np.array([val_L[:, m].mean(axis=1).mean() for m in members])
+    C_T0 = np.array([val_T[:, m].mean(axis=1).mean() for m in members])
+    err_L, err_T = np.full_like(C_L0, np.nan), np.full_like(C_T0, np.nan)
+    for s, m in enumerate(members):
+        if n_snap > 1:
+            err_L[s] = val_L[:, m].mean(axis=1).std(ddof=1) / np.sqrt(n_snap)
+            err_T[s] = val_T[:, m].mean(axis=1).std(ddof=1) / np.sqrt(n_snap)
+            continue
+        groups = _independent_modes(modes, m)
+        if len(groups) > 1:
+            err_L[s] = np.array([val_L[0, g].mean() for g in groups]).std(ddof=1) / np.sqrt(len(groups))
+            err_T[s] = np.array([val_T[0, g].mean() for g in groups]).std(ddof=1) / np.sqrt(len(groups))
+    k = 2.0 * np.pi * np.sqrt(shells.astype(np.float64)) / L
+    return k, C_L0, C_T0, err_L, err_T, np.array([len(m) for m in members], dtype=np.int64)
+
+
+def current_correlations(j, n: int, modes, L: float, max_lag=None, origin_stride: int = 1):
+    """j [n_snap, n_modes, 3] -> (k, C_L[n_shells, max_lag + 1], C_T[n_shells, max_lag + 1]): the longitudinal and
+    transverse current correlation functions C_L(k, tau) = <Re j_L(t0 + tau) j_L*(t0)> / n and C_T(k, tau) = 1/2 <Re
+    j_T(t0 + tau) . j_T*(t0)> / n over the time origins and the shell's modes, the shells in the order of
+    current_equal_time.  Formula, origin convention and counts are those of compute_vacf_tau_timeorig with the shell's
+    modes as the particles, as intermediate_scattering has them; at tau = 0 they are current_equal_time over the origins
+    used."""
+    j_L, j_T, shells, members = _current_series(j, n, modes, "current_correlations")
+    if not L > 0.0:
+        raise ValueError("current_correlations: n >= 1 and L > 0")
+    rows_L, rows_T = [], []
+    for m in members:
+        re, im = np.ascontiguousarray(j_L[:, m].real), np.ascontiguousarray(j_L[:, m].imag)
+        rows_L.append(compute_vacf_tau_timeorig(re, im, np.zeros_like(re), max_lag, origin_stride) / n)
+        re = [np.ascontiguousarray(j_T[:, m, a].real) for a in range(3)]
+        im = [np.ascontiguousarray(j_T[:, m, a].imag) for a in range(3)]
+        rows_T.append(0.5 * (compute_vacf_tau_timeorig(*re, max_lag, origin_stride)
+                             + compute_vacf_tau_timeorig(*im, max_lag, origin_stride)) / n)
+    k = 2.0 * np.pi * np.sqrt(shells.astype(np.float64)) / L
+    return k, np.stack(rows_L), np.stack(rows_T)
+
+
+def transverse_viscosity(C_T, k, dt_sample: float, number_density: float) -> np.ndarray:
+    """C_T [n_shells, n_lags] (current_correlations), k [n_shells] -> eta[n_shells, n_lags]: the running wave-vector
+    dependent shear viscosity
+        eta(k, t) = rho C_T(k, 0) / (k^2 integral_0^t C_T(k, s) ds),
+    rho the number density, the integral the trapezoid running integral on the sampling grid like viscosity_green_kubo's;
+    reduced units (m = 1).  For C_T(k, t) = C_T(k, 0) exp(-k^2 eta t / rho), the hydrodynamic form, eta(k, t) -> eta as
+    t -> infinity; its k -> 0 limit is the shear viscosity of viscosity_green_kubo.  Where the integral is 0 (t = 0) the
+    value is +inf."""
+    C_T = np.asarray(C_T, dtype=np.float64)
+    k = np.asarray(k, dtype=np.float64)
+    if C_T.ndim != 2 or C_T.shape[1] < 1 or k.shape != (C_T.shape[0],):
+        raise ValueError(f"transverse_viscosity: C_T must have shape (n_shells, n_lags) and k (n_shells,), got {C_T.shape} "
+                         f"and {k.shape}")
+    if not dt_sample > 0.0 or not number_density > 0.0 or not np.all(k > 0.0):
+        raise ValueError("transverse_viscosity: dt_sample > 0, number_density > 0 and k > 0")
+    run = np.zeros_like(C_T)
+    run[:, 1:] = np.cumsum(0.5 * (C_T[:, 1:] + C_T[:, :-1]) * dt_sample, axis=1)
+    out = np.full_like(C_T, np.inf)
+    np.divide(number_density * C_T[:, :1] / (k * k)[:, None], run, out=out, where=run != 0.0)
+    return out
+
+
 # -- van Hove self-correlation (Engine.vanhove_read: hist[max_lag + 1, nbins + 1] with the overflow column last) --------
 def _vanhove_rows(hist, counts, n: int):
     """-> (inside [rows, nbins] float64, overflow fraction [rows], 1 / (n count) [rows], 0 where count == 0)"""

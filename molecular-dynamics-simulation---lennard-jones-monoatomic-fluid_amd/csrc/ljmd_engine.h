@@ -235,6 +235,8 @@ struct ljmd : ljmdh::SimParams {      // parameters (type(sim_params), md_types.
     ljmdv::VanHoveState vanhove;
     // density modes (ljmd_rhok_*, core ljmd_rhok.cpp): one-rank engines only
     ljmdc::RhokState rhok;
+    // current modes (ljmd_current_*, core ljmd_current.cpp): one-rank engines only
+    ljmdc::CurrentState current;
     bool step_open = false;           // between ljmd_step_begin and ljmd_step_finish (split-phase API)
 
     bool profiling = false;
@@ -260,8 +262,8 @@ IntegrateArgs integrate_args(ljmd_t *h);
 // the caller releases whatever exists
 int allocate_engine(ljmd_t *h);
 void release(ljmd_t *h);
-// what ljmd_rdf_configure, ljmd_tcf_configure, ljmd_stress_configure, ljmd_heatflux_configure, ljmd_vanhove_configure
-// and ljmd_rhok_configure allocated; the engine's device is current
+// what ljmd_rdf_configure, ljmd_tcf_configure, ljmd_stress_configure, ljmd_heatflux_configure, ljmd_vanhove_configure,
+// ljmd_rhok_configure and ljmd_current_configure allocated; the engine's device is current
 // (ljmd_resident.cpp; called by release)
 void release_resident(ljmd_t *h);
 // HBM -> host of any of r, ru, v, a (dsts[3 w + k], NULL = skip) and of the last n_records scalar records

@@ -1,10 +1,10 @@
-// ljmd_resident.cpp -- the C entry points of the six observables of the system resident on the single / sharded
-// engine (include/ljmd.h: ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_*, ljmd_heatflux_*, ljmd_vanhove_*, ljmd_rhok_*) and the
-// release of what they allocated.  Each runs the entry checks, builds the view of the engine and calls the observable's
-// core (ljmd_rdf.cpp, ljmd_tcf.cpp, ljmd_stress.cpp, ljmd_heatflux.cpp, ljmd_vanhove.cpp, ljmd_rhok.cpp); g(r) and the
-// pressure tensor dispatch a multi-device parent to its rank engines.  MSD / VACF, the heat flux, the van Hove function
-// and the density modes take one-rank engines only: their cores refuse every other handle at configure, so a parent
-// never has them configured.
+// ljmd_resident.cpp -- the C entry points of the seven observables of the system resident on the single / sharded
+// engine (include/ljmd.h: ljmd_rdf_*, ljmd_tcf_*, ljmd_stress_*, ljmd_heatflux_*, ljmd_vanhove_*, ljmd_rhok_*,
+// ljmd_current_*) and the release of what they allocated.  Each runs the entry checks, builds the view of the engine and
+// calls the observable's core (ljmd_rdf.cpp, ljmd_tcf.cpp, ljmd_stress.cpp, ljmd_heatflux.cpp, ljmd_vanhove.cpp,
+// ljmd_rhok.cpp, ljmd_current.cpp); g(r) and the pressure tensor dispatch a multi-device parent to its rank engines.
+// MSD / VACF, the heat flux, the van Hove function, the density modes and the current modes take one-rank engines only:
+// their cores refuse every other handle at configure, so a parent never has them configured.
 #include "ljmd_engine.h"
 #include "ljmd_multi.h"
 
@@ -27,7 +27,7 @@ ResidentView view_of(const ljmd_t *h)
     return v;
 }
 
-// one of the six: whether it is configured on a handle, and the failure where it is not
+// one of the seven: whether it is configured on a handle, and the failure where it is not
 struct Observable {
     bool (*configured)(const ljmd_t *h);
     int (*not_configured)(std::string *err, const char *who);
@@ -38,6 +38,7 @@ const Observable kStress = {[](const ljmd_t *h) { return h->stress.max_snapshots
 const Observable kHeatflux = {[](const ljmd_t *h) { return h->heatflux.max_snapshots != 0; }, ljmdq::not_configured};
 const Observable kVanHove = {[](const ljmd_t *h) { return h->vanhove.max_lag != 0; }, ljmdv::not_configured};
 const Observable kRhok = {[](const ljmd_t *h) { return h->rhok.max_snapshots != 0; }, ljmdc::not_configured};
+const Observable kCurrent = {[](const ljmd_t *h) { return h->current.max_snapshots != 0; }, ljmdc::current_not_configured};
 
 // a handle, and the observable configured on it
 int configured(ljmd_t *h, const char *who, const Observable &o)
@@ -142,6 +143,7 @@ void ljmdh::release_resident(ljmd_t *h)
     ljmdq::heatflux_release(&h->heatflux, h->stream);
     ljmdv::vanhove_release(&h->vanhove, h->stream);
     ljmdc::rhok_release(&h->rhok, h->stream);
+    ljmdc::current_release(&h->current, h->stream);
 }
 
 extern "C" {
@@ -520,6 +522,61 @@ int ljmd_rhok_profile_read(ljmd_t *h, double *kernel_ms)
     LJMD_TRY(configured(h, who, kRhok));
     LJMD_HIP(h, hipSetDevice(h->device));
     return ljmdc::rhok_profile_read(&h->rhok, &h->err, who, view_of(h), kernel_ms);
+}
+
+// ---- current modes ----------------------------------------------------------
+// one-rank engines only, as MSD / VACF: the core refuses every other handle at configure
+
+int ljmd_current_configure(ljmd_t *h, int32_t n_modes, const int32_t *modes, int32_t max_snapshots)
+{
+    static const char *who = "ljmd_current_configure";
+    LJMD_TRY(entry_checks(h, who, kHandle));
+    if (!h->multi) LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdc::current_configure(&h->current, &h->err, who, view_of(h), n_modes, modes, max_snapshots);
+}
+
+int ljmd_current_accumulate(ljmd_t *h)
+{
+    static const char *who = "ljmd_current_accumulate";
+    LJMD_TRY(configured(h, who, kCurrent));
+    // the positions and velocities alone: a state, but no accelerations
+    LJMD_TRY(entry_checks(h, who, kHaveState | kNotPoisoned));
+    if (h->step_open || h->forces_pending)
+        return fail(h, LJMD_ERR_STATE, "%s: inside a split-phase step (call ljmd_step_finish first)", who);
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdc::current_accumulate(&h->current, &h->err, who, view_of(h));
+}
+
+int ljmd_current_read_exact(ljmd_t *h, int64_t *words, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_current_read_exact";
+    LJMD_TRY(configured(h, who, kCurrent));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdc::current_fetch(&h->current, &h->err, who, view_of(h), words, n_snapshots);
+}
+
+int ljmd_current_read(ljmd_t *h, double *j, int64_t *n_snapshots)
+{
+    static const char *who = "ljmd_current_read";
+    LJMD_TRY(configured(h, who, kCurrent));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdc::current_read(&h->current, &h->err, who, view_of(h), j, n_snapshots);
+}
+
+int ljmd_current_reset(ljmd_t *h)
+{
+    static const char *who = "ljmd_current_reset";
+    LJMD_TRY(configured(h, who, kCurrent));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdc::current_reset(&h->current, &h->err, who, view_of(h));
+}
+
+int ljmd_current_profile_read(ljmd_t *h, double *kernel_ms)
+{
+    static const char *who = "ljmd_current_profile_read";
+    LJMD_TRY(configured(h, who, kCurrent));
+    LJMD_HIP(h, hipSetDevice(h->device));
+    return ljmdc::current_profile_read(&h->current, &h->err, who, view_of(h), kernel_ms);
 }
 
 }  // extern "C"

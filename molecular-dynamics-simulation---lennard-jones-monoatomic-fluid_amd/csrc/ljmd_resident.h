@@ -1,17 +1,19 @@
-// ljmd_resident.h -- host side of the six observables of the system resident on the single / sharded engine: g(r)
+// ljmd_resident.h -- host side of the seven observables of the system resident on the single / sharded engine: g(r)
 // (ljmd_rdf.cpp); the pressure tensor (ljmd_stress.cpp) and the heat flux (ljmd_heatflux.cpp), which are two descriptors
 // over the one series core (ljmd_series.cpp); MSD / VACF (ljmd_tcf.cpp) and the van Hove self-correlation
 // (ljmd_vanhove.cpp), which are two descriptors over the one time-origin core (ljmd_origins.cpp); the density modes
-// (ljmd_rhok.cpp).  What the cores share
+// (ljmd_rhok.cpp); the current modes (ljmd_current.cpp).  What the cores share
 // -- the view through which they see an engine, their named device buffers, the timer around one accumulate -- and each
 // core's state and functions.  A core knows nothing of struct ljmd and links without the engine (tests/rdf_host,
-// tests/tcf_host, tests/stress_host, tests/heatflux_host, tests/vanhove_host, tests/rhok_host); every C entry point that
-// takes a handle is in ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h, ljmd_stress.h,
-// ljmd_heatflux.h, ljmd_rhok.h, ljmd_tcf.h and ljmd_vanhove.h, the latter two over ljmd_origins.h.
+// tests/tcf_host, tests/stress_host, tests/heatflux_host, tests/vanhove_host, tests/rhok_host, tests/current_host); every
+// C entry point that takes a handle is in ljmd_resident.cpp.  Host code only: the kernels' side is ljmd_rdf.h,
+// ljmd_stress.h, ljmd_heatflux.h, ljmd_rhok.h, ljmd_current.h, ljmd_tcf.h and ljmd_vanhove.h, the latter two over
+// ljmd_origins.h.
 #ifndef LJMD_RESIDENT_H
 #define LJMD_RESIDENT_H
 
 #include "ljmd_common.h"
+#include "ljmd_current.h"
 #include "ljmd_heatflux.h"
 #include "ljmd_rdf.h"
 #include "ljmd_rhok.h"
@@ -390,6 +392,34 @@ int rhok_read(RhokState *st, std::string *err, const char *who, const ResidentVi
 int rhok_reset(RhokState *st, std::string *err, const char *who, const ResidentView &v);
 int rhok_profile_read(RhokState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms);
 void rhok_release(RhokState *st, hipStream_t stream);
+
+// The current modes (ljmd_current.cpp): the density modes' series with eighteen words per mode, on their grid (RhokPlan).
+struct CurrentState {
+    int max_snapshots = 0;          // 0 = not configured
+    int n_modes = 0, n = 0, T = 0;  // the list's length, and the engine configure saw
+    RhokPlan plan;
+    uint64_t *d_series = nullptr;   // [max_snapshots][n_modes][kCurrentRowWords]
+    int32_t *d_modes = nullptr;     // [n_modes][3]
+    uint64_t *d_part = nullptr;     // [pchunks][mchunks 64][kCurrentRowWords]
+    unsigned *d_flag = nullptr;     // [pchunks][mchunks]
+    int32_t *d_range = nullptr;
+    ljmdh::KernelTimer timer;
+    int64_t snapshots = 0;
+};
+
+int current_not_configured(std::string *err, const char *who);
+// refuses a multi-device handle and a rank engine of G > 1 itself; copies the list to the device before it returns
+int current_configure(CurrentState *st, std::string *err, const char *who, const ResidentView &v, int32_t n_modes,
+                      const int32_t *modes, int32_t max_snapshots);
+int current_accumulate(CurrentState *st, std::string *err, const char *who, const ResidentView &v);
+// words [snapshots][n_modes][3][2][3], either pointer may be NULL; LJMD_ERR_RANGE while the sticky word is set
+int current_fetch(CurrentState *st, std::string *err, const char *who, const ResidentView &v, int64_t *words,
+                  int64_t *n_snapshots);
+// j [snapshots][n_modes][3][2]: fixed_to_double of every integer
+int current_read(CurrentState *st, std::string *err, const char *who, const ResidentView &v, double *j, int64_t *n_snapshots);
+int current_reset(CurrentState *st, std::string *err, const char *who, const ResidentView &v);
+int current_profile_read(CurrentState *st, std::string *err, const char *who, const ResidentView &v, double *kernel_ms);
+void current_release(CurrentState *st, hipStream_t stream);
 
 }  // namespace ljmdc
 #endif

@@ -37,6 +37,8 @@ module ljmd_c_api
   public :: ljmd_heatflux_reset, ljmd_heatflux_profile_read, ljmd_heatflux_from_exact
   public :: ljmd_rhok_select_modes, ljmd_rhok_configure, ljmd_rhok_accumulate, ljmd_rhok_read, ljmd_rhok_read_exact
   public :: ljmd_rhok_reset, ljmd_rhok_profile_read
+  public :: ljmd_current_configure, ljmd_current_accumulate, ljmd_current_read, ljmd_current_read_exact
+  public :: ljmd_current_reset, ljmd_current_profile_read
   public :: ljmd_batch_tcf_configure, ljmd_batch_tcf_accumulate, ljmd_batch_tcf_read, ljmd_batch_tcf_read_exact
   public :: ljmd_batch_tcf_reset, ljmd_tcf_from_exact, ljmd_batch_prepare
   public :: ljmd_batch_stress_configure, ljmd_batch_stress_accumulate, ljmd_batch_stress_read, ljmd_batch_stress_read_exact
@@ -70,6 +72,8 @@ module ljmd_c_api
   integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_INDEX = 1023
   integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_RHOK_MAX_ENTRIES = 16777216
+  integer(c_int32_t), parameter, public :: LJMD_CURRENT_MAX_SNAPSHOTS = 262144
+  integer(c_int32_t), parameter, public :: LJMD_CURRENT_MAX_ENTRIES = 4194304
   integer(c_int32_t), parameter, public :: LJMD_BATCH_RHOK_MAX_SNAPSHOTS = 262144
   integer(c_int32_t), parameter, public :: LJMD_BATCH_RHOK_MAX_ENTRIES = 16777216
 
@@ -637,6 +641,49 @@ module ljmd_c_api
     end function
 
     function ljmd_rhok_profile_read(handle, kernel_ms) bind(C, name="ljmd_rhok_profile_read") result(status)
+      import :: c_int, c_double, c_ptr
+      type(c_ptr), value :: handle
+      real(c_double), intent(out) :: kernel_ms
+      integer(c_int) :: status
+    end function
+
+    ! current modes of the system resident on a one-rank engine handle (ljmd.h: ljmd_current_*); modes = c_loc of
+    ! [3, n_modes] 32-bit integers, j = c_loc of [2, 3, n_modes, n_snapshots] doubles ((Re, Im) of x, y, z), words = c_loc
+    ! of [3, 2, 3, n_modes, n_snapshots] 64-bit words in Fortran order; c_null_ptr skips an output
+    function ljmd_current_configure(handle, n_modes, modes, max_snapshots) bind(C, name="ljmd_current_configure") result(status)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle, modes
+      integer(c_int32_t), value :: n_modes, max_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_current_accumulate(handle) bind(C, name="ljmd_current_accumulate") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_current_read(handle, j, n_snapshots) bind(C, name="ljmd_current_read") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, j
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_current_read_exact(handle, words, n_snapshots) bind(C, name="ljmd_current_read_exact") result(status)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle, words
+      integer(c_int64_t), intent(out) :: n_snapshots
+      integer(c_int) :: status
+    end function
+
+    function ljmd_current_reset(handle) bind(C, name="ljmd_current_reset") result(status)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: status
+    end function
+
+    function ljmd_current_profile_read(handle, kernel_ms) bind(C, name="ljmd_current_profile_read") result(status)
       import :: c_int, c_double, c_ptr
       type(c_ptr), value :: handle
       real(c_double), intent(out) :: kernel_ms

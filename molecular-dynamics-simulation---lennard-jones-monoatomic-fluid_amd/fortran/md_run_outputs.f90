@@ -17,6 +17,9 @@
 !   <dir>/density_modes_gpu.dat, <dir>/structure_factor_gpu.dat, <dir>/intermediate_scattering_gpu.dat: the density
 !   modes rho_k md_simulation_gpu recorded on the device (ljmd_rhok_*), S(k) and F(k, tau) per shell of equal |n|^2
 !   (write_density_modes_file, write_structure_factor_file, write_intermediate_scattering_file).
+!   <dir>/current_modes_gpu.dat, <dir>/current_correlations_gpu.dat: the current modes j_k md_simulation_gpu recorded on
+!   the device (ljmd_current_*) and C_L(k, tau), C_T(k, tau) per shell of equal |n|^2 (write_current_modes_file,
+!   current_projections, current_equal_time, write_current_correlations_file).
 !==============================================================================
 module md_run_outputs
   use, intrinsic :: iso_c_binding, only: c_int64_t, c_int32_t
@@ -28,6 +31,7 @@ module md_run_outputs
   public :: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, write_stress_acf_file
   public :: write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file
   public :: write_density_modes_file, density_mode_shells, write_structure_factor_file, write_intermediate_scattering_file
+  public :: write_current_modes_file, current_projections, current_equal_time, write_current_correlations_file
 
 contains
 
@@ -369,6 +373,111 @@ contains
     end do
     close(iu_f)
   end subroutine write_intermediate_scattering_file
+
+  ! current_modes_gpu.dat: a header line listing the modes (nx,ny,nz), then per sampling instant the time and, of every
+  ! mode in list order, Re and Im of the x, the y and the z component of j_k
+  subroutine write_current_modes_file(filename, n_modes, modes, n_snapshots, times, j)
+    character(len=*), intent(in) :: filename
+    integer, intent(in) :: n_modes, n_snapshots
+    integer(c_int32_t), intent(in) :: modes(3, n_modes)
+    real(kind=dp_kind), intent(in) :: times(n_snapshots), j(2, 3, n_modes, n_snapshots)
+    integer :: iu_j, ierr, k, m
+    open(newunit=iu_j, file=filename, status='replace', action='write', recl=26 * (6 * n_modes + 1) + 64 + 24 * n_modes, &
+         iostat=ierr)
+    if (ierr /= 0) stop 'write_current_modes_file(): cannot open current_modes_gpu.dat.'
+    write(iu_j, '(a)', advance='no') '# time   Re Im of j_k x, y, z, modes:'
+    do m = 1, n_modes
+      write(iu_j, '(a,i0,a,i0,a,i0,a)', advance='no') ' (', modes(1, m), ',', modes(2, m), ',', modes(3, m), ')'
+    end do
+    write(iu_j, '(a)') ''
+    do k = 1, n_snapshots
+      write(iu_j, '(es24.16e3)', advance='no') times(k)
+      do m = 1, n_modes
+        write(iu_j, '(6(2x,es24.16e3))', advance='no') j(:, :, m, k)
+      end do
+      write(iu_j, '(a)') ''
+    end do
+    close(iu_j)
+  end subroutine write_current_modes_file
+
+  ! the longitudinal and transverse parts of a current series: k^ = n / |n|, j_L = k^ . j, j_T = j - k^ j_L, each in the
+  ! order of analysis.current_correlations (products and sums over x, y, z in turn).  Modes with |n|^2 = 0 give zeros.
+  subroutine current_projections(n_modes, modes, n_snapshots, j, j_l, j_t)
+    integer, intent(in) :: n_modes, n_snapshots
+    integer(c_int32_t), intent(in) :: modes(3, n_modes)
+    real(kind=dp_kind), intent(in) :: j(2, 3, n_modes, n_snapshots)
+    real(kind=dp_kind), intent(out) :: j_l(2, n_modes, n_snapshots), j_t(2, 3, n_modes, n_snapshots)
+    integer :: k, m, a, c
+    real(kind=dp_kind) :: nd(3), norm, khat(3)
+    do m = 1, n_modes
+      nd = dble(modes(:, m))
+      norm = sqrt((nd(1) * nd(1) + nd(2) * nd(2)) + nd(3) * nd(3))
+      khat = 0.d0
+      if (norm > 0.d0) khat = nd / norm
+      do k = 1, n_snapshots
+        do c = 1, 2
+          j_l(c, m, k) = (j(c, 1, m, k) * khat(1) + j(c, 2, m, k) * khat(2)) + j(c, 3, m, k) * khat(3)
+          do a = 1, 3
+            j_t(c, a, m, k) = j(c, a, m, k) - khat(a) * j_l(c, m, k)
+          end do
+        end do
+      end do
+    end do
+  end subroutine current_projections
+
+  ! the equal-time values per shell of |n|^2 > 0 (analysis.current_equal_time): C_L0 = <|j_L|^2> / N and C_T0 = 1/2
+  ! <|j_T|^2> / N over the snapshots and the shell's modes (per snapshot the mean over the modes, then over the snapshots)
+  subroutine current_equal_time(n, n_modes, n_snapshots, j_l, j_t, n_shells, first, c_l, c_t)
+    integer(kind=int_kind), intent(in) :: n
+    integer, intent(in) :: n_modes, n_snapshots, n_shells, first(n_modes + 1)
+    real(kind=dp_kind), intent(in) :: j_l(2, n_modes, n_snapshots), j_t(2, 3, n_modes, n_snapshots)
+    real(kind=dp_kind), intent(out) :: c_l(n_shells), c_t(n_shells)
+    integer :: s, m, k, cnt
+    real(kind=dp_kind) :: acc_l, acc_t, snap_l, snap_t
+    do s = 1, n_shells
+      cnt = first(s + 1) - first(s)
+      acc_l = 0.d0
+      acc_t = 0.d0
+      do k = 1, n_snapshots
+        snap_l = 0.d0
+        snap_t = 0.d0
+        do m = first(s), first(s + 1) - 1
+          snap_l = snap_l + (j_l(1, m, k)**2 + j_l(2, m, k)**2) / dble(n)
+          snap_t = snap_t + 0.5d0 * sum(j_t(1, :, m, k)**2 + j_t(2, :, m, k)**2) / dble(n)
+        end do
+        acc_l = acc_l + snap_l / dble(cnt)
+        acc_t = acc_t + snap_t / dble(cnt)
+      end do
+      c_l(s) = acc_l / dble(n_snapshots)
+      c_t(s) = acc_t / dble(n_snapshots)
+    end do
+  end subroutine current_equal_time
+
+  ! current_correlations_gpu.dat: per shell of |n|^2 > 0 and per lag, |n|^2, k = 2 pi sqrt(|n|^2) / L, lag, tau = lag *
+  ! output_interval * dt, C_L(k, tau) and C_T(k, tau); first_shell = the first shell of the mode list with |n|^2 > 0
+  subroutine write_current_correlations_file(filename, box_length, n_modes, modes, n_shells, first, first_shell, max_lag, &
+                                             output_interval, dt, c_l, c_t)
+    character(len=*), intent(in) :: filename
+    real(kind=dp_kind), intent(in) :: box_length, dt
+    integer, intent(in) :: n_modes, n_shells, first(n_modes + 1), first_shell, max_lag
+    integer(c_int32_t), intent(in) :: modes(3, n_modes)
+    integer(kind=int_kind), intent(in) :: output_interval
+    real(kind=dp_kind), intent(in) :: c_l(0:max_lag, n_shells), c_t(0:max_lag, n_shells)
+    integer :: iu_c, ierr, s, m, n2, lag
+    real(kind=dp_kind), parameter :: two_pi = 6.283185307179586476925286766559d0
+    open(newunit=iu_c, file=filename, status='replace', action='write', iostat=ierr)
+    if (ierr /= 0) stop 'write_current_correlations_file(): cannot open current_correlations_gpu.dat.'
+    write(iu_c, '(a)') '# n2   k   lag   tau   C_L(k, tau)   C_T(k, tau)'
+    do s = first_shell, n_shells
+      m = first(s)
+      n2 = int(modes(1, m))**2 + int(modes(2, m))**2 + int(modes(3, m))**2
+      do lag = 0, max_lag
+        write(iu_c, '(i0,2x,es24.16e3,2x,i0,3(2x,es24.16e3))') n2, two_pi * sqrt(dble(n2)) / box_length, lag, &
+            dble(lag) * dble(output_interval) * dt, c_l(lag, s), c_t(lag, s)
+      end do
+    end do
+    close(iu_c)
+  end subroutine write_current_correlations_file
 
   subroutine write_curve(filename, header, errmsg, lag_max, c, cn)
     character(len=*), intent(in) :: filename, header, errmsg

@@ -54,7 +54,17 @@
 ! that many sampling instants, lag, tau and per shell the time-origin averaged F(k, tau) = <Re rho_k(t0 + tau)
 ! rho_k*(t0)> / N -- ljmd_time_origin_average with the shell's modes as the particles and (Re, Im, 0) as the velocity;
 ! one-rank engines only: with LJMD_GPUS > 1 the program stops before an engine is created; every other output file is
-! the same with and without it).
+! the same with and without it),
+! LJMD_CURRENT_N2MAX (default 0 = off; > 0: the collective current modes j_k of the resident system are recorded on the
+! device -- ljmd_current_* -- at the same sampling instants, for the modes ljmd_rhok_select_modes gives with
+! LJMD_CURRENT_N2MAX and LJMD_CURRENT_PER_SHELL (default 8), as LJMD_RHOK_N2MAX / PER_SHELL choose theirs;
+! outputs/one_run/current_modes_gpu.dat gets a header line listing the modes and per instant the time, then Re and Im of
+! the x, y and z component of every mode; outputs/one_run/current_correlations_gpu.dat per shell and lag |n|^2, k, lag,
+! tau, C_L(k, tau) and C_T(k, tau): with LJMD_CURRENT_MAX_LAG > 0 and at least two instants the time-origin averages up
+! to that many sampling instants -- ljmd_time_origin_average with the shell's modes as the particles, (Re j_L, Im j_L, 0)
+! and the real and the imaginary part of j_T as the velocities -- otherwise lag 0 alone, the equal-time values over all
+! instants; one-rank engines only: with LJMD_GPUS > 1 the program stops before an engine is created; every other output
+! file is the same with and without it).
 !==============================================================================
 program md_simulation_gpu
   use, intrinsic :: iso_c_binding
@@ -67,7 +77,8 @@ program md_simulation_gpu
   use md_run_outputs,   only: write_run_statistics, write_rdf_file, write_msd_vacf_file, write_pressure_tensor_file, &
                               write_stress_acf_file, write_heat_flux_file, write_heat_flux_acf_file, write_van_hove_file, &
                               write_density_modes_file, density_mode_shells, write_structure_factor_file, &
-                              write_intermediate_scattering_file
+                              write_intermediate_scattering_file, write_current_modes_file, current_projections, &
+                              current_equal_time, write_current_correlations_file
   implicit none
 
   type(sim_params) :: params
@@ -120,6 +131,15 @@ program md_simulation_gpu
   real(c_double), allocatable, target :: rhok_rho(:, :, :), rhok_times(:)  ! [2, n_modes, snapshots], [snapshots]
   real(c_double), allocatable, target :: rhok_re(:, :), rhok_im(:, :), rhok_zero(:, :), rhok_f(:, :), rhok_row(:)
   integer(c_int64_t) :: rhok_snapshots
+  integer :: cur_n2max, cur_per_shell, cur_max_lag, cur_lags, cur_shells, cur_s, cur_cnt, cur_a, cur_first_shell
+  integer(c_int32_t) :: cur_n_modes
+  integer(c_int) :: cur_status
+  integer(c_int32_t), allocatable, target :: cur_modes(:, :)               ! [3, n_modes]
+  integer, allocatable :: cur_first(:)
+  real(c_double), allocatable, target :: cur_j(:, :, :, :), cur_times(:)   ! [2, 3, n_modes, snapshots], [snapshots]
+  real(c_double), allocatable :: cur_jl(:, :, :), cur_jt(:, :, :, :), cur_cl(:, :), cur_ct(:, :)
+  real(c_double), allocatable, target :: cur_x(:, :), cur_y(:, :), cur_z(:, :), cur_row(:), cur_row2(:)
+  integer(c_int64_t) :: cur_snapshots
 
   call read_simulation_parameters('inputs/input_simulation_parameters.txt', params, total_steps, &
                                   output_interval, warmup_steps, rc_over_L, target_total_energy)
@@ -198,6 +218,18 @@ program md_simulation_gpu
   call get_environment_variable('LJMD_RHOK_MAX_LAG', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) rhok_max_lag
   if (rhok_max_lag < 0) stop 'md_simulation: LJMD_RHOK_MAX_LAG must be >= 0.'
+  cur_n2max = 0
+  call get_environment_variable('LJMD_CURRENT_N2MAX', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) cur_n2max
+  if (cur_n2max < 0) stop 'md_simulation: LJMD_CURRENT_N2MAX must be >= 0.'
+  cur_per_shell = 8
+  call get_environment_variable('LJMD_CURRENT_PER_SHELL', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) cur_per_shell
+  if (cur_per_shell < 1) stop 'md_simulation: LJMD_CURRENT_PER_SHELL must be >= 1.'
+  cur_max_lag = 0
+  call get_environment_variable('LJMD_CURRENT_MAX_LAG', env, status=ios)
+  if (ios == 0 .and. len_trim(env) > 0) read(env, *) cur_max_lag
+  if (cur_max_lag < 0) stop 'md_simulation: LJMD_CURRENT_MAX_LAG must be >= 0.'
   n_gpus = 1
   call get_environment_variable('LJMD_GPUS', env, status=ios)
   if (ios == 0 .and. len_trim(env) > 0) read(env, *) n_gpus
@@ -209,6 +241,8 @@ program md_simulation_gpu
     error stop 'md_simulation: LJMD_VANHOVE_MAX_LAG needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1 .and. rhok_n2max > 0) &
     error stop 'md_simulation: LJMD_RHOK_N2MAX needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
+  if (n_gpus > 1 .and. cur_n2max > 0) &
+    error stop 'md_simulation: LJMD_CURRENT_N2MAX needs a one-rank engine (n_ranks = 1): unset it or run with LJMD_GPUS=1.'
   if (n_gpus > 1) then
     allocate(device_list(n_gpus))
     device_list = [(int(k - 1, c_int32_t), k = 1, n_gpus)]
@@ -263,6 +297,23 @@ program md_simulation_gpu
     call ljmd_check(ljmd_rhok_configure(engine, rhok_n_modes, c_loc(rhok_modes), int(n_snapshots_expected, c_int32_t)), engine, &
                     'ljmd_rhok_configure')
     allocate(rhok_times(n_snapshots_expected))
+  end if
+  if (cur_n2max > 0) then
+    n_snapshots_expected = (total_steps / output_interval) - (warmup_steps / output_interval)
+    if (n_snapshots_expected < 1) stop 'md_simulation: LJMD_CURRENT_N2MAX needs at least one sampling instant.'
+    if (n_snapshots_expected > LJMD_CURRENT_MAX_SNAPSHOTS) &
+      stop 'md_simulation: more sampling instants than LJMD_CURRENT_MAX_SNAPSHOTS.'
+    ! the count first (the call fails by design: capacity 0), then the list
+    cur_status = ljmd_rhok_select_modes(int(cur_n2max, c_int32_t), int(cur_per_shell, c_int32_t), 0_c_int32_t, c_null_ptr, &
+                                        cur_n_modes)
+    if (cur_status == LJMD_OK .or. cur_n_modes < 1) call ljmd_check(cur_status, c_null_ptr, 'ljmd_rhok_select_modes')
+    if (cur_n_modes > LJMD_RHOK_MAX_MODES) stop 'md_simulation: more modes than LJMD_RHOK_MAX_MODES: lower LJMD_CURRENT_N2MAX.'
+    allocate(cur_modes(3, cur_n_modes))
+    call ljmd_check(ljmd_rhok_select_modes(int(cur_n2max, c_int32_t), int(cur_per_shell, c_int32_t), cur_n_modes, &
+                                           c_loc(cur_modes), cur_n_modes), c_null_ptr, 'ljmd_rhok_select_modes')
+    call ljmd_check(ljmd_current_configure(engine, cur_n_modes, c_loc(cur_modes), int(n_snapshots_expected, c_int32_t)), engine, &
+                    'ljmd_current_configure')
+    allocate(cur_times(n_snapshots_expected))
   end if
   ! t = 0 forces and energies (:236-243)
   call ljmd_check(ljmd_compute_forces(engine, epot, d_epot, dd_epot), engine, 'ljmd_compute_forces')
@@ -321,6 +372,10 @@ program md_simulation_gpu
       call ljmd_check(ljmd_rhok_accumulate(engine), engine, 'ljmd_rhok_accumulate')
       rhok_times(num_samples + 1) = time
     end if
+    if (sample_now .and. cur_n2max > 0) then
+      call ljmd_check(ljmd_current_accumulate(engine), engine, 'ljmd_current_accumulate')
+      cur_times(num_samples + 1) = time
+    end if
     count = segment_length(step)
     if (async_io .and. count > 0) call enqueue_segment(count)
     if (sample_now) then
@@ -370,6 +425,11 @@ program md_simulation_gpu
     allocate(rhok_rho(2, rhok_n_modes, max(num_samples, 1)))
     call ljmd_check(ljmd_rhok_read(engine, c_loc(rhok_rho), rhok_snapshots), engine, 'ljmd_rhok_read')
     if (rhok_snapshots /= num_samples) stop 'md_simulation: the density mode series and the samples disagree.'
+  end if
+  if (cur_n2max > 0) then
+    allocate(cur_j(2, 3, cur_n_modes, max(num_samples, 1)))
+    call ljmd_check(ljmd_current_read(engine, c_loc(cur_j), cur_snapshots), engine, 'ljmd_current_read')
+    if (cur_snapshots /= num_samples) stop 'md_simulation: the current mode series and the samples disagree.'
   end if
   call ljmd_destroy(engine)
 
@@ -452,6 +512,50 @@ program md_simulation_gpu
       call write_intermediate_scattering_file('outputs/one_run/intermediate_scattering_gpu.dat', rhok_shells, rhok_lags, &
                                               output_interval, params%dt, rhok_f)
     end if
+  end if
+  if (cur_n2max > 0) then
+    call write_current_modes_file('outputs/one_run/current_modes_gpu.dat', int(cur_n_modes), cur_modes, int(num_samples), &
+                                  cur_times, cur_j)
+    allocate(cur_first(cur_n_modes + 1), cur_jl(2, cur_n_modes, num_samples), cur_jt(2, 3, cur_n_modes, num_samples))
+    call density_mode_shells(int(cur_n_modes), cur_modes, cur_shells, cur_first)
+    call current_projections(int(cur_n_modes), cur_modes, int(num_samples), cur_j, cur_jl, cur_jt)
+    cur_first_shell = 1                 ! the list of ljmd_rhok_select_modes has no (0, 0, 0): every shell has a direction
+    if (cur_max_lag > 0 .and. num_samples >= 2) then
+      ! per shell its modes as the particles: (Re j_L, Im j_L, 0), then the real and the imaginary part of j_T
+      cur_lags = min(cur_max_lag, int(num_samples) - 1)
+      allocate(cur_cl(0:cur_lags, cur_shells), cur_ct(0:cur_lags, cur_shells), cur_row(0:cur_lags), cur_row2(0:cur_lags))
+      do cur_s = 1, cur_shells
+        cur_cnt = cur_first(cur_s + 1) - cur_first(cur_s)
+        allocate(cur_x(cur_cnt, num_samples), cur_y(cur_cnt, num_samples), cur_z(cur_cnt, num_samples))
+        cur_x = cur_jl(1, cur_first(cur_s):cur_first(cur_s + 1) - 1, 1:num_samples)
+        cur_y = cur_jl(2, cur_first(cur_s):cur_first(cur_s + 1) - 1, 1:num_samples)
+        cur_z = 0.d0
+        call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(num_samples, c_int32_t), int(cur_cnt, c_int32_t), &
+                                                 c_loc(cur_x), c_loc(cur_y), c_loc(cur_z), int(cur_lags, c_int32_t), &
+                                                 1_c_int32_t, c_loc(cur_row)), c_null_ptr, 'ljmd_time_origin_average')
+        cur_cl(:, cur_s) = cur_row / dble(params%n)
+        cur_row2 = 0.d0
+        do cur_a = 1, 2
+          cur_x = cur_jt(cur_a, 1, cur_first(cur_s):cur_first(cur_s + 1) - 1, 1:num_samples)
+          cur_y = cur_jt(cur_a, 2, cur_first(cur_s):cur_first(cur_s + 1) - 1, 1:num_samples)
+          cur_z = cur_jt(cur_a, 3, cur_first(cur_s):cur_first(cur_s + 1) - 1, 1:num_samples)
+          call ljmd_check(ljmd_time_origin_average(1_c_int32_t, int(num_samples, c_int32_t), int(cur_cnt, c_int32_t), &
+                                                   c_loc(cur_x), c_loc(cur_y), c_loc(cur_z), int(cur_lags, c_int32_t), &
+                                                   1_c_int32_t, c_loc(cur_row)), c_null_ptr, 'ljmd_time_origin_average')
+          cur_row2 = cur_row2 + cur_row
+        end do
+        cur_ct(:, cur_s) = 0.5d0 * cur_row2 / dble(params%n)
+        deallocate(cur_x, cur_y, cur_z)
+      end do
+    else
+      cur_lags = 0
+      allocate(cur_cl(0:0, cur_shells), cur_ct(0:0, cur_shells))
+      call current_equal_time(params%n, int(cur_n_modes), int(num_samples), cur_jl, cur_jt, cur_shells, cur_first, &
+                              cur_cl(0, :), cur_ct(0, :))
+    end if
+    call write_current_correlations_file('outputs/one_run/current_correlations_gpu.dat', params%box_length, int(cur_n_modes), &
+                                         cur_modes, cur_shells, cur_first, cur_first_shell, cur_lags, output_interval, &
+                                         params%dt, cur_cl, cur_ct)
   end if
   write(*, '(a,i0,a,i0,a,f10.2,a,es11.4,a)') 'md_simulation_gpu: N=', params%n, ' steps=', total_steps, &
     '  ', dble(total_steps) * dble(crate) / dble(max(c1 - c0, 1_8)), ' steps/s  ', &

@@ -686,6 +686,70 @@ class Engine:
         self._ck(self._lib.ljmd_rhok_profile_read(self._h, C.byref(ms)))
         return {"kernel_ms": ms.value}
 
+    # -- current modes of the resident system (include/ljmd.h: ljmd_current_*) -----------------
+    def current_configure(self, modes, max_snapshots: int) -> None:
+        """ljmd_current_configure: the mode list (integer triples [n_modes, 3], k = 2 pi n / L; rhok_select_modes gives
+        the drivers' list) and room for max_snapshots snapshots of j_k on the device; max_snapshots = 0 switches the
+        feature off.  The series starts empty.  One-rank engines only; independent of rhok_configure."""
+        if isinstance(max_snapshots, bool) or not isinstance(max_snapshots, (int, np.integer)):
+            raise TypeError(f"current_configure: max_snapshots must be an integer, got {max_snapshots!r}")
+        m = np.asarray(modes if modes is not None else np.zeros((0, 3)))
+        if m.size and not np.issubdtype(m.dtype, np.integer):
+            raise TypeError("current_configure: modes must be integers")
+        if m.ndim != 2 or m.shape[1] != 3:
+            raise ValueError(f"current_configure: modes must have shape [n_modes, 3], got {m.shape}")
+        if m.size and np.abs(m).max() > np.iinfo(np.int32).max:
+            raise ValueError("current_configure: modes must lie within the int32 range")
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        self._ck(self._lib.ljmd_current_configure(self._h, m.shape[0], m.ctypes.data_as(_lib.c_int32_p) if m.size else None,
+                                                  int(max_snapshots)))
+        self._current_modes = m.shape[0] if int(max_snapshots) > 0 else 0
+
+    def current_accumulate(self) -> None:
+        """appends j_k of the positions and velocities resident now to the series (stream-ordered: no host wait)"""
+        self._ck(self._lib.ljmd_current_accumulate(self._h))
+
+    def _current_count(self) -> int:
+        """snapshots in the series (ljmd_current_read_exact without a buffer); raises as the reads do"""
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_current_read_exact(self._h, None, C.byref(snaps)))
+        return snaps.value
+
+    def current_read(self) -> np.ndarray:
+        """-> j[n_snapshots, n_modes, 3] complex: sum_j v_a (cos k.r_j + i sin k.r_j) for a = x, y, z, each part one
+        rounding of its exact integer; nothing is cleared."""
+        n, m = max(self._current_count(), 1), max(getattr(self, "_current_modes", 0), 1)
+        j = np.empty((n, m, 3, 2), dtype=np.float64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_current_read(self._h, j.ctypes.data_as(c_double_p), C.byref(snaps)))
+        return j[:snaps.value].copy().view(np.complex128)[..., 0]
+
+    def current_read_exact(self, raw: bool = False):
+        """-> sums[n_snapshots, n_modes, 3, 2]: the exact integer sums of Q(v_a cos) and Q(v_a sin), Q(t) = RNE(t 2^64),
+        as Python ints in an object array -- or, raw=True, the library's int64 words [n_snapshots, n_modes, 3, 2, 3]
+        (three little-endian limbs of a signed 192-bit integer)."""
+        m = max(getattr(self, "_current_modes", 0), 1)
+        words = np.empty((max(self._current_count(), 1), m, 3, 2, 3), dtype=np.int64)
+        snaps = C.c_int64()
+        self._ck(self._lib.ljmd_current_read_exact(self._h, words.ctypes.data_as(_lib.c_int64_p), C.byref(snaps)))
+        words = words[:snaps.value].copy()
+        if raw:
+            return words
+        u = words.view(np.uint64)
+        sums = np.empty(words.shape[:4], dtype=object)
+        for idx in np.ndindex(*sums.shape):
+            sums[idx] = (int(words[idx][2]) << 128) + (int(u[idx][1]) << 64) + int(u[idx][0])
+        return sums
+
+    def current_reset(self) -> None:
+        self._ck(self._lib.ljmd_current_reset(self._h))
+
+    def current_profile(self) -> dict:
+        """ljmd_current_profile_read for the most recent current_accumulate -> {'kernel_ms'}"""
+        ms = C.c_double()
+        self._ck(self._lib.ljmd_current_profile_read(self._h, C.byref(ms)))
+        return {"kernel_ms": ms.value}
+
     # -- measurement -----------------------------------------------------------
     def profile_enable(self, on: bool = True) -> None:
         self._ck(self._lib.ljmd_profile_enable(self._h, 1 if on else 0))
